@@ -42,6 +42,7 @@ FACES_PER_FRAME = 4                    # O-Net cap (C2 keeps F =
 MFMA_PEAK_TFLOPS = 2500.0              # dense f16/bf16 (MI355X_MICROARCH.md)
 MFMA_PEAK_TFLOPS_F8 = 5000.0           # dense fp8 (block-scaled MFMA with unit scales)
 PMC_FILE = "profiles/r05_pmc_traffic.json"
+DUMP_BYTES = 64 << 20                  # --dump-outputs: size cap of all files together
 
 
 def synth_frames(n, h, w, seed, device):
@@ -179,6 +180,49 @@ def c1_latency(app, device, n=30):
     return out
 
 
+def step_outputs(keep, cap):
+    """--dump-outputs: host copies of what one timed step handed its caller (``keep``: match ids, scores, decisions, the
+    detect_embed_slots dict and the normalised embedding rows the match scanned with), float32 (row ids float64).  Slots
+    beyond a frame's face count are undefined on the device: written as 0, row id -1."""
+    idx, score, dec, r, normed = keep[:5]
+    counts = r["counts"].cpu()
+    n = counts.numel()
+    valid = torch.arange(cap)[None, :] < counts[:, None]            # [frames, cap]
+    rows = valid.reshape(-1)
+    out = {"counts": counts.to(torch.float32)}
+    for k in ("bbox", "kps", "det_score"):
+        t = r[k].cpu().to(torch.float32)
+        out[k] = torch.where(valid.reshape(n, cap, *([1] * (t.dim() - 2))), t, 0.0)
+    emb = {"embedding": r["embedding"]} if "embedding" in r else {}     # embed groups hand on the normalised rows only
+    for k, t in {**emb, "normed_embedding": normed}.items():
+        out[k] = torch.where(rows[:, None], t.cpu().to(torch.float32), 0.0)
+    out["match_idx"] = torch.where(rows, idx.cpu().to(torch.float64), -1.0)
+    out["match_score"] = torch.where(rows, score.cpu().to(torch.float32), 0.0)
+    out["decision"] = torch.where(rows, dec.cpu().to(torch.float32), 0.0)
+    return {k: v.numpy() for k, v in out.items()}
+
+
+def dump_outputs(d, arrays):
+    """Write ``arrays`` (step_outputs) as d/<name>.npy.  Past DUMP_BYTES, a fixed seeded sample of whole frames is kept
+    (every array is cut to the same frames; their indices in sample_frames.npy).  Returns the record for the result line."""
+    frames = arrays["counts"].shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    sample = None
+    if total > DUMP_BYTES:
+        keep = max(1, int((DUMP_BYTES - (1 << 16)) // (total / frames + 8)))
+        sample = np.sort(np.random.default_rng(0).choice(frames, keep, replace=False))
+        for k, a in arrays.items():
+            per = a.shape[0] // frames                                   # 1: per frame, cap: per face slot
+            sel = (sample[:, None] * per + np.arange(per)[None, :]).reshape(-1)
+            arrays[k] = a[sel]
+        arrays["sample_frames"] = sample.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
+    return {"dir": d, "files": sorted(k + ".npy" for k in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "frames": frames, "sampled_frames": None if sample is None else int(sample.size)}
+
+
 class stdout_to_stderr:
     """RCCL prints a version banner on file descriptor 1 when a communicator is created; the driver wants ONE JSON line
     on stdout.  Route fd 1 to fd 2 around the process-group set-up (and its first collective)."""
@@ -274,6 +318,14 @@ def main():
     ap.add_argument("--det-sides", type=int, default=None, help="A/B: side streams the detector deals pyramid levels 1.. over")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its LAST step (rank 0's batch) as "
+                         "DIR/<name>.npy (float32; row ids float64): the detector's counts / bbox / kps / det_score, the "
+                         "embedding rows, the matched gallery row, its score and the decision.  Slots beyond a frame's face count "
+                         "are undefined on the device and written as 0 (row id -1).  Frames, gallery and planted rows are "
+                         "seeded, so the same arguments give the same inputs on every run; the planted rows are taken from this "
+                         f"build's own embeddings.  At most {DUMP_BYTES >> 20} MB: past that, a seeded sample of whole frames "
+                         "(sample_frames.npy holds their indices)")
     ap.add_argument("--workload", default=None, choices=["C1", "C2", "C3", "C4", "C5"],
                     help="BASELINE.json config.  Default: C2 on one GPU (the headline: 64x1080p, 4 faces/frame, 10k rows) "
                          "and C4 on several (the same frames per GPU, ONE shared 1 000 000-row gallery row-sharded over "
@@ -281,6 +333,8 @@ def main():
                          "640x480, 1 face, 100 rows), C3 (8 x 4K, 16 faces/frame) and C5 (fp8 embed convs + fp8 scan of "
                          "a 10 M-row gallery row-sharded 8 ways: 1.25 M rows per GPU) are side measurements for DESIGN.md")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.workload is None:
         args.workload = "C4" if int(os.environ.get("WORLD_SIZE", str(max(args.gpus, 1)))) > 1 else "C2"
     global FRAMES, H, W, FACES_PER_FRAME, GALLERY_ROWS
@@ -397,6 +451,7 @@ def main():
     # embed groups (G > 1): the aligned crops of G consecutive steps side by side, one buffer per stream pair (a pair's launches
     # are ordered: the next group's warps come behind this group's embed forward)
     group_crops = [torch.empty((G * q_rows, 112, 112, 8), dtype=torch.float16, device=device) for _ in pipes] if G > 1 else None
+    last_step = {}
 
     def run_loop(ingest, steps, warmup):
         """warmup untimed steps, then `steps` timed steps bracketed by barrier + synchronize on both sides.
@@ -419,7 +474,7 @@ def main():
             host["counts"].copy_(r["counts"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(s_emb)
-            return host, ev, (idx, dec, r, s_emb), t_in, source(i)
+            return host, ev, (idx, score, dec, r, emb_rows, s_emb), t_in, source(i)
 
         def enqueue(i, flush):
             """One step, enqueued without any host synchronisation: fixed per-frame face slots, device-side counts,
@@ -454,10 +509,12 @@ def main():
 
         def fetch(pending):
             """ids on the host = end of the step; faces = detected faces (slots beyond a frame's count are ignored)."""
-            host, ev, _keep, t_in, src = pending
+            host, ev, keep, t_in, src = pending
             ev.synchronize()
             batch_ms.append((time.perf_counter() - t_in) * 1e3)      # frames handed over -> ids on the host
             results.append((host["idx"].clone(), host["dec"].clone(), host["counts"].clone(), src))   # 3 KB, for the self-check
+            if args.dump_outputs:
+                last_step["keep"] = keep            # the device outputs of the latest step fetched (--dump-outputs)
             return int(host["counts"].sum())
 
         def step(i, pending, flush):
@@ -497,6 +554,10 @@ def main():
         torch.cuda.synchronize()
 
     dt, faces, batch_ms, results = run_loop(ingest, args.steps, args.warmup)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before anything else runs the detector or the match again
+        dumped = dump_outputs(args.dump_outputs, step_outputs(last_step.pop("keep"), FACES_PER_FRAME))
+    last_step.clear()
     tot = torch.tensor([dt, float(faces)], dtype=torch.float64, device=device)
     if world > 1:
         tmax = tot.clone(); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -705,6 +766,8 @@ def main():
                                         "the rows are planted from the GPU's own embeddings, so it shows that every timed step "
                                         "reproduces them through the scan, not that they are right - oracle_check does that"},
                "roofline": roofline}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         fail = None
         if det_path.get("exact_list_overflow"):
             fail = "the detector's exact R-/O-Net work list overflowed its capacity (MTCNNHIP.ro_list_cap)"
