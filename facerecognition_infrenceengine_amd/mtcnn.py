@@ -438,7 +438,28 @@ class MTCNNHIP:
         exact = (self.rnet if net == 0 else self.onet)(None, lcap, lc, lcap, x1=x1)
         self.lib.fr_ro_scatter_rows(_lib.ptr(exact), _lib.ptr(lst), _lib.ptr(lc), lcap, nh, _lib.ptr(head), self._s)
         self._ro_lists = getattr(self, "_ro_lists", {})
-        self._ro_lists[net] = lc            # diagnostics / tests: how many crops the exact pass took
+        self._ro_lists[net] = lc            # diagnostics / bench.py: how many crops the exact pass took (last call of ANY thread)
+        # this thread's record of the call (every chunk of it): the device counter beside its capacity, read by exact_lists()
+        self._tls.path["exact_lists"].append((net, lcap))
+        self._tls.exact_counters.append(lc)
+
+    def exact_lists(self):
+        """The exact R-/O-Net work lists of this thread's last ``detect_batch`` call, one entry per list in launch order (R-Net,
+        O-Net, for every chunk of the call): dicts {"net": "rnet" | "onet", "count": crops that qualified, "cap": list capacity}.
+        Synchronises the device.  A count above its cap is an overflow: the crops past the cap kept their split-precision
+        heads (include/frhip.h fr_ro_margin_list)."""
+        nets = ("rnet", "onet")
+        path = getattr(self._tls, "path", None)
+        if not path:
+            return []
+        torch.cuda.synchronize(self.device)
+        return [{"net": nets[net], "count": int(lc[0]), "cap": cap}
+                for (net, cap), lc in zip(path["exact_lists"], self._tls.exact_counters)]
+
+    def exact_list_overflow(self):
+        """The nets ("rnet", "onet") whose exact work list overflowed in this thread's last call (any chunk); [] when none did.
+        Synchronises the device."""
+        return sorted({e["net"] for e in self.exact_lists() if e["count"] > e["cap"]}, key=("rnet", "onet").index)
 
     def rnet(self, x, B, counts=None, cap=0, x1=None, x2=None):
         """counts / cap: only the first counts[frame] of a frame's cap crop slots are computed (device-side).
@@ -506,8 +527,9 @@ class MTCNNHIP:
         counts i32 [N] (faces per frame, in descending-score order).
 
         ``_tls.path`` (this thread's last call): which arithmetic ran - {"frames", "batch", "chunks", "fused_levels", "band_levels",
-        "pconv1_mfma_levels" [(h, w) of the conv1 maps computed on the f16 matrix cores], "unfused_levels", "split_ro"} - so that a
-        test can assert the path it means to test was the one taken."""
+        "pconv1_mfma_levels" [(h, w) of the conv1 maps computed on the f16 matrix cores], "unfused_levels", "split_ro",
+        "exact_lists" [(net, list capacity) of every exact R-/O-Net pass, all chunks]} - so that a test can assert the path it means
+        to test was the one taken; ``exact_lists()`` / ``exact_list_overflow()`` read the lists' counters."""
         assert frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3 and frames.is_contiguous()
         N, H, W, _ = frames.shape
         lib, t0, t1, t2 = self.lib, *self.thresholds
@@ -515,7 +537,8 @@ class MTCNNHIP:
         few = N <= self.solo_max_frames and not batch
         if not _chunk:
             self._tls.path = {"frames": N, "batch": batch, "chunks": 1, "fused_levels": 0, "band_levels": 0, "pconv1_mfma_levels": [],
-                              "unfused_levels": 0, "split_ro": False}
+                              "unfused_levels": 0, "split_ro": False, "exact_lists": []}
+            self._tls.exact_counters = []       # device counters of the exact lists of path["exact_lists"] (no sync here)
         # The fused P-Net addresses a level's split conv1 map [N, h, w, 64 B] with 32-bit offsets.  A batch whose largest level
         # exceeds them (64 x 4K frames: 3.05e9 B) is cut into the fewest equal groups of frames that fit - frames are independent, every
         # group's final NMS writes its rows of the result tensors - rather than dropping that level to the layer-by-layer f32 path.

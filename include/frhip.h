@@ -364,9 +364,11 @@ int fr_ro_gemm_split(int layer, const float* x, const void* w_packed, const floa
  * logit_thr = ln(t / (1 - t)) (t: the stage's probability threshold) are appended to list (any order); *list_count = how
  * many there are (may exceed list_cap: entries past it are dropped, consumers clamp).  head f32 [nframes*cap][nhead].
  * *list_count must be 0 on entry (fr_ro_conv2_split's zero_word, or the caller's memset).
- * OVERFLOW: the slots dropped past list_cap keep their split-precision heads - their threshold decision is then NOT the f32
- * one.  Nothing signals it on the device; a caller that must know compares *list_count with list_cap after the cascade
- * (MTCNNHIP._ro_lists; the batch-path tests and bench.py's line do) and raises list_cap or re-runs the stage on the f32 layers.
+ * OVERFLOW (*list_count > list_cap): list holds list_cap distinct qualifying slots, which ones is unspecified (atomic order);
+ * *list_count is still the full number of qualifying slots.  The slots dropped past list_cap keep their split-precision heads -
+ * their threshold decision is then NOT the f32 one.  Nothing signals it on the device; a caller that must know compares
+ * *list_count with list_cap after the cascade (MTCNNHIP.exact_list_overflow(): per thread, every frame group of a call; the
+ * batch-path tests and bench.py's line do) and raises list_cap or re-runs the stage on the f32 layers.
  * The f32 layers that follow take the list's own counter as their `counts` with cap = list_cap: fr_dconv_mfma_f32 and
  * fr_ro_gemm_split only test slot < counts[f], so a counter ABOVE list_cap is tolerated there (every one of the list_cap rows
  * is computed, none beyond). */

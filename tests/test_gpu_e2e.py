@@ -735,8 +735,13 @@ def _assert_batch_path(det, nframes, nlevels, mfma_levels_min):
     assert len(p["pconv1_mfma_levels"]) >= mfma_levels_min * p["chunks"], p
     assert all(h * w >= det.split_pconv1_min_px for h, w in p["pconv1_mfma_levels"]), p
     assert p["split_ro"], p
-    lists = {net: int(lc[0]) for net, lc in det._ro_lists.items()}          # crops the exact f32 R-/O-Net pass took (last chunk)
-    assert set(lists) == {0, 1} and all(0 <= lists[n] <= det.ro_list_cap[n] for n in lists), (lists, det.ro_list_cap)
+    # crops the exact f32 R-/O-Net pass took, every chunk of the call: R-Net then O-Net per chunk, none past its list's capacity
+    rec = det.exact_lists()
+    assert [e["net"] for e in rec] == ["rnet", "onet"] * p["chunks"], (rec, p)
+    assert [e["cap"] for e in rec] == list(det.ro_list_cap) * p["chunks"], (rec, det.ro_list_cap)
+    assert all(0 <= e["count"] <= e["cap"] for e in rec) and det.exact_list_overflow() == [], rec
+    lists = {net: int(lc[0]) for net, lc in det._ro_lists.items()}          # (what bench.py reads: the last chunk's lists)
+    assert lists == {0: rec[-2]["count"], 1: rec[-1]["count"]}, (lists, rec)
     return p, lists
 
 
@@ -876,9 +881,89 @@ def test_sixty_four_4k_frames_are_cut_into_groups_that_fit_the_fused_pnet():
     torch.cuda.synchronize()
     p = det._tls.path
     assert p["chunks"] == 2 and p["unfused_levels"] == 0 and p["fused_levels"] == 28 and p["split_ro"], p
+    rec = det.exact_lists()                                     # the exact lists of BOTH chunks, none overflowed
+    assert [e["net"] for e in rec] == ["rnet", "onet", "rnet", "onet"] and det.exact_list_overflow() == [], rec
+    assert all(0 <= e["count"] <= e["cap"] for e in rec) and rec[0]["count"] > 0 and rec[2]["count"] > 0, rec
     assert int(want[3].sum()) >= 16
     for f in range(64):
         n = int(want[3][f % 8])
         assert int(got[3][f]) == n
         for a, b in zip(want[:3], got[:3]):
             assert torch.equal(a[f % 8, :n], b[f, :n]), f
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The edges of the pixel gate (MTCNNHIP.batch_min_pixels = 22 M) at other shapes than C2 / C3 / C5: fewer than 8 frames on the
+# batch path (3 x 4K; one frame of 24 Mpixel through get(), eager and replayed from a HIP graph) and many small frames just below it.
+def test_three_4k_frames_take_the_batch_path_vs_oracle():
+    """3 x 4K = 24.9 Mpixel: the smallest 4K batch on the batch path, through detect_embed_slots; every frame against the CPU
+    oracle at the 4K tolerances of the C3 test (detections and embeddings)."""
+    from facerecognition_infrenceengine_amd import FaceAnalysis
+    from make_golden import synth_frame
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        a16 = FaceAnalysis(name="synthetic", arch="r100", cap_o=16).prepare(ctx_id=0)
+    frs = np.ascontiguousarray(np.stack([synth_frame(2160, 3840, 610 + i) for i in range(3)]))
+    assert 3 * 2160 * 3840 >= a16.det.batch_min_pixels > 2 * 2160 * 3840
+    r = a16.detect_embed_slots(torch.from_numpy(frs).cuda())
+    torch.cuda.synchronize()
+    p, lists = _assert_batch_path(a16.det, 3, 14, 3)
+    assert p["chunks"] == 1
+    faces, worst = _check_slots_vs_oracle(r, frs, range(3), 16, 2e-2)
+    print(f"\n3 x 4K batch path: {len(faces)} faces vs oracle, max 1-cos {worst:.2e}; exact crops {lists}")
+    assert len(faces) >= 12
+
+
+def test_one_24_mpixel_frame_through_get_eager_and_graph_vs_oracle(app):
+    """One synthetic 6000 x 4000 frame (24 Mpixel, 16 pyramid levels: the merged level NMS list exactly full) through get():
+    eagerly and replayed from a HIP graph (enable_graphs), both on the batch path, both against the CPU oracle, and equal to each
+    other bit for bit (cap_o = 4: the eager and the captured embed forward run in the same batch-size mode, as in
+    test_graph_replay_equals_eager)."""
+    from facerecognition_infrenceengine_amd.mtcnn import pyramid_scales
+    from make_golden import synth_frame
+    eng = app.clone_with(cap_o=4)
+    frame = synth_frame(4000, 6000, 620)
+    assert len(pyramid_scales(4000, 6000)) * eng.det.keep_scale == 4096
+    old = _oracle_threads()
+    try:
+        ob, os_, ok, oemb = _oracle_frame(frame, cap_o=4)
+    finally:
+        torch.set_num_threads(old)
+    assert len(os_) >= 2
+    eager = eng.get(frame)
+    _assert_batch_path(eng.det, 1, 16, 5)
+    try:
+        eng.enable_graphs(True)
+        graphed = [eng.get(frame) for _ in range(2)]
+        assert eng.det._tls.path["batch"] and eng.det._tls.path["frames"] == 1      # what the captured call ran
+    finally:
+        eng.enable_graphs(False)
+    for faces in [eager] + graphed:
+        assert len(faces) == len(os_)
+        np.testing.assert_allclose(np.stack([f.bbox for f in faces]), ob, atol=2e-2)
+        np.testing.assert_allclose(np.array([f.det_score for f in faces]), os_, atol=5e-5)
+        np.testing.assert_allclose(np.stack([f.kps for f in faces]), ok, atol=2e-2)
+        emb = np.stack([f.embedding for f in faces])
+        cos = (emb * oemb).sum(1) / (np.linalg.norm(emb, axis=1) * np.linalg.norm(oemb, axis=1))
+        assert (1 - cos).max() < 1e-3, cos
+    for got in graphed:
+        for a, b in zip(eager, got):
+            assert np.array_equal(a.bbox, b.bbox) and np.array_equal(a.kps, b.kps) and a.det_score == b.det_score
+            assert np.array_equal(a.embedding, b.embedding) and np.array_equal(a.normed_embedding, b.normed_embedding)
+
+
+def test_sixty_four_480p_frames_stay_below_the_gate_vs_oracle(app):
+    """64 x 640 x 480 = 19.7 Mpixel, just below the gate: the all-f32 detector (``_tls.path["batch"]`` False, no split R-/O-Net,
+    no exact lists), four of the frames against the CPU oracle."""
+    from make_golden import synth_frame
+    frs = np.ascontiguousarray(np.stack([synth_frame(480, 640, 700 + i) for i in range(64)]))
+    det = app.det
+    assert 64 * 480 * 640 < det.batch_min_pixels
+    r = app.detect_embed_slots(torch.from_numpy(frs).cuda())
+    torch.cuda.synchronize()
+    p = det._tls.path
+    assert p["frames"] == 64 and not p["batch"] and not p["split_ro"] and p["exact_lists"] == [], p
+    assert det.exact_lists() == [] and det.exact_list_overflow() == []
+    faces, worst = _check_slots_vs_oracle(r, frs, (0, 21, 42, 63), det.cap_o, 5e-3)
+    print(f"\n64 x 480p (below the gate): {len(faces)} faces of 4 frames vs oracle, max 1-cos {worst:.2e}")
+    assert len(faces) >= 4

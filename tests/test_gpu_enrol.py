@@ -33,8 +33,12 @@ def test_mean_and_row_blob_vs_reference(golden):
     d = golden("gallery_row_kat.npz")
     avg = Enroller(_FakeApp()).mean_embedding(list(d["poses"]))
     assert avg.dtype == np.float32
-    np.testing.assert_allclose(avg, d["avg"], rtol=0, atol=1e-7)                # np.mean pairwise vs sequential sum
+    # fr_mean_rows_f32 sums the rows in order and divides by K in f32, as np.mean over axis 0 does: the same bits
+    assert avg.shape == d["avg"].shape and np.array_equal(avg, d["avg"])
     assert len(pickle.dumps(avg)) == len(d["blob"]) == 2200
+    row = pickle.loads(d["blob"].tobytes())                                      # the gallery row blob the reference stores
+    assert row.dtype == avg.dtype and row.shape == avg.shape and np.array_equal(row, avg)
+    assert pickle.dumps(avg) == d["blob"].tobytes()
 
 
 def test_first_above_lowest_row_and_inclusive():
@@ -60,7 +64,8 @@ def test_unknown_clustering_vs_reference(golden):
     assign = [uc.assign(e) for e in d["seq"]]
     assert assign == list(d["assign"])
     assert uc.counts == list(d["counts"])
-    np.testing.assert_allclose(uc.avg[:len(uc.hist)].cpu().numpy(), d["final_avg"], atol=1e-7)
+    # the running means go through fr_mean_rows_f32 too: in-order f32 sum / K, bit for bit the reference's np.mean
+    assert np.array_equal(uc.avg[:len(uc.hist)].cpu().numpy(), d["final_avg"])
 
 
 def test_enrol_end_to_end():
