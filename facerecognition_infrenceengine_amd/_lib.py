@@ -221,16 +221,6 @@ class Lib:
             raise AttributeError(name)
 
 
-def use_library(path):
-    """Developer tools only (tools/stamp_*.py): bind the diagnostic twin ``libfrhip_debug.so`` (``make debug``)
-    instead of the product library.  Must be called before the first ``load()``."""
-    global LIB_PATH, _lib
-    with _lock:
-        if _lib is not None:
-            raise FrError("use_library() must be called before the library is loaded")
-        LIB_PATH = path
-
-
 def load():
     """Load the in-tree libfrhip.so.  Raises FrError if it has not been built."""
     global _lib

@@ -28,20 +28,6 @@ void fr_set_error(const char* fmt, ...);
         }                                                                         \
     } while (0)
 
-// Diagnostic switches (in-kernel cycle stamps, alternative kernel variants) exist only in the DEBUG build
-// (`make debug` -> libfrhip_debug.so, -DFR_DEBUG_BUILD), where they are read from the environment on every call.
-// The product library reads no environment variable and instantiates no stamped kernel.
-#ifdef FR_DEBUG_BUILD
-#include <cstdlib>
-static inline int fr_dbg_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-static inline void* fr_dbg_ptr(const char* name) { const char* e = getenv(name); return e ? (void*)strtoll(e, nullptr, 0) : nullptr; }
-constexpr bool FR_DEBUG = true;
-#else
-static inline int fr_dbg_int(const char*, int dflt) { return dflt; }
-static inline void* fr_dbg_ptr(const char*) { return nullptr; }
-constexpr bool FR_DEBUG = false;
-#endif
-
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: one atomic bit per device ordinal
 // remembers where it has been raised (idempotent; the only process-wide state the library keeps).
 struct FrDevLatch { std::atomic<unsigned long long> mask{0}; };

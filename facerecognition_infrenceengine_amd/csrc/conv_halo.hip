@@ -6,12 +6,11 @@
 // ONCE per chunk (9 K steps) and only the weight tile streams per step.
 //
 // Tile = TH whole image rows of one image (196 pixels at 14x14 / 7x28, 224 at 4x56 / 2x112) x BN couts;
-// 512 threads = 8 waves = WN (64 couts each) x WP pixel groups.  LDS: halo chunk [NXBUF][XROWS][64 ch]
+// 512 threads = 8 waves = WN (64 couts each) x WP pixel groups.  LDS: one halo chunk [XROWS][64 ch]
 // (zero border by out-of-range LDS-DMA), weight tile [2][BN][64]; rows of 128 B with a 16-B chunk XOR.
-// Variants in use (fr_conv_halo_try): LEAN <2,13,256|320,1,4,true> for 14x14 / 28x28 (BN = 128, one halo
-// buffer, <= 128 VGPRs, two blocks per CU, 13th pixel tile shared by cout = SPLIT); single-chunk
-// <1,14,384|512,1,4> for Cin = 64 at 56x56 / 112x112; the pipelined two-halo-buffer schedule
-// (<4|2,13,320,2,2>, one block per CU) is kept behind FR_HALO_LEAN=0.
+// Variants (fr_conv_halo_try, fr_conv_nhwc_f8): LEAN <2,13,384|256|320,true> for 7x7 / 14x14 / 28x28 (BN = 128,
+// <= 128 VGPRs, two blocks per CU, 13th pixel tile shared by cout = SPLIT), also in fp8; the pipelined schedule
+// <1,14,384|512> for the single-chunk layers (Cin = 64) at 56x56 / 112x112.
 // Lean schedule per K step q = chunk*9 + tap: vmcnt(0) -> raw barrier -> issue W(q+1) (LDS-DMA, scalar
 // offset only) -> 2 x (A and B fragments via ds_read_b128, 13 MFMAs); at a chunk end: barrier + halo reload.
 // No gather arithmetic in the loop: per-lane halo bases are fixed, taps are scalar row offsets.
@@ -27,8 +26,6 @@ struct HaloP {
     int TH, tiles_per_img;      // output rows per tile, H / TH
     int G;                      // images per tile (1; 4 at 7x7, where TH = H: a tile = G whole images, each with its own halo)
     unsigned xbytes, wbytes;
-    unsigned long long* stamps; // diagnostic build only (FR_DBG_STAMPS=<device ptr>): per-wave segment cycle sums
-    int stagger;                // diagnostic build only (FR_HALO_STAGGER): start delay of every second block, in 512-cycle units
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -45,8 +42,6 @@ __device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
 }
 
 #define HK 64          // channels per chunk
-#define HALO_NW4_DEFAULT 0
-
 
 // scheduling pattern for one half step: 4+PT ds_read_b128 (+ ~3 address VALU each) spread over 4*PT MFMAs
 #define INTERLEAVE_READS_MFMA()                                            \
@@ -59,20 +54,10 @@ __device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
         __builtin_amdgcn_sched_group_barrier(0x008, 4 * PT - 2 * (4 + PT), 0); \
     } while (0)
 
-#define STAMP(var)                                                                          \
-    do {                                                                                    \
-        if (STAMPS) {                                                                       \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
-
 // WN: 64-cout groups per block; NPT: 16-pixel MFMA tiles per M tile; XROWS: halo row capacity (multiple of 64,
-// >= (TH+2)*(W+2)); NXBUF: halo buffers (1 when Cin == 64: a single chunk); MINW: waves per SIMD to fit
-// (4 = two blocks per CU).
-// LEAN: one halo buffer, one fragment set, <= 128 VGPRs -> TWO blocks per CU (16 waves): the fixed cost of a
-// block (first loads, epilogue: ~30 % of a 28x28 tile) and its barrier stalls are covered by the neighbour.
+// >= (TH+2)*(W+2)).  Every variant fits four waves per SIMD (two blocks per CU).
+// LEAN: one fragment set, <= 128 VGPRs -> TWO blocks per CU (16 waves): the fixed cost of a block (first loads,
+// epilogue: ~30 % of a 28x28 tile) and its barrier stalls are covered by the neighbour.
 // NA: 16-cout MFMA tiles per wave (4 = 64 couts).  (A 32-cout / 2-pixel-group split was tried for balance: it spilled at
 // 128 VGPRs and was replaced by SPLIT below.)
 // F8: fp8 e4m3 activations and weights on v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales; twice the f16 MFMA
@@ -80,15 +65,12 @@ __device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
 // pair, fed by the same two ds_read_b128 per operand as the f16 step's two K = 32 MFMAs (lane quarter fq holds bytes
 // [16 fq, +16) and [64 + 16 fq, +16) of the row: the k order inside an MFMA is free as long as A and B agree), so the
 // LDS image, swizzle, DMA pattern and barrier structure are the f16 kernel's; the K loop has half as many steps.
-// NW: waves per block.  8 (512 threads) everywhere except the "lean4" variant <2,13,*,1,2,true,4,false,4>: FOUR waves
-// per block, each owning 64 couts x 6 pixel tiles + two cout tiles of the shared 13th pixel tile (26 accumulator tiles,
-// <= 256 VGPRs), still two blocks per CU.  Same LDS image and barrier structure, but a wave's register tile is twice as
-// large, so a K step reads 26 KB of fragments for 52 MFMAs instead of 18 KB for 26 (0.50 vs 0.69 KB of LDS traffic per
-// MFMA) and a barrier joins 4 waves instead of 8.
-template <int WN, int NPT, int XROWS, int NXBUF, int MINW, bool STAMPS, bool LEAN = false, int NA = 4, bool F8 = false, int NW = 8, int ABL = 0>
-__global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
+template <int WN, int NPT, int XROWS, bool LEAN = false, bool F8 = false>
+__global__ __launch_bounds__(512, 4) void conv_halo_kernel(HaloP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(!F8 || LEAN, "the fp8 variant exists for the lean schedule only");
+    constexpr int NA = 4;                              // 16-cout MFMA tiles per wave
+    constexpr int NW = 8;                              // waves per block
     constexpr int ES = F8 ? 1 : 2;                     // bytes per element
     constexpr int CH = 128 / ES;                       // channels per 128-B chunk
     constexpr int BN = 16 * NA * WN;
@@ -97,17 +79,15 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
     // SPLIT (lean 196-pixel tiles): 13 pixel tiles over 4 pixel groups used to be 4+4+4+(1 real + 3 padding) tiles,
     // i.e. 16 MFMA tiles per wave for 12.25 useful.  Now every wave owns 3 pixel tiles x 64 couts and the 13th pixel
     // tile is shared by cout: wave (wn, wp) computes its couts [wn*64 + wp*16, +16) -> 13 MFMA tiles per wave.
-    constexpr bool SPLIT = LEAN && (WN == 2 || WN == 4) && NPT == 13 && NA == 4;
+    constexpr bool SPLIT = LEAN && WN == 2 && NPT == 13;
     constexpr int PT = SPLIT ? 12 / WP : (NPT + WP - 1) / WP;
-    constexpr int XT = SPLIT ? NA / WP : 1;           // cout tiles of the shared 13th pixel tile per wave (1 or 2)
+    constexpr int XT = SPLIT ? NA / WP : 1;           // cout tiles of the shared 13th pixel tile per wave
     constexpr int NWI = BN / (8 * NW);                // weight LDS-DMA instructions per thread per step
     constexpr int NXI = XROWS / (8 * NW);             // halo LDS-DMA instructions per thread per chunk
     static_assert(BN % (8 * NW) == 0 && XROWS % (8 * NW) == 0 && NW % WN == 0, "tile / wave split");
-    unsigned long long tA = 0, tB = 0, tC = 0, tD = 0;
-    STAMP(tA);
     extern __shared__ __attribute__((aligned(16))) half_t lds[];
-    half_t* xs = lds;                                 // [NXBUF][XROWS][HK]
-    half_t* ws = lds + NXBUF * XROWS * HK;            // [2][BN][HK]
+    half_t* xs = lds;                                 // [XROWS][HK]
+    half_t* ws = lds + XROWS * HK;                    // [2][BN][HK]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // provably wave-uniform: LDS-DMA bases stay in SGPRs
@@ -153,10 +133,9 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
     for (int i = 0; i < NWI; ++i) woff[i] = (unsigned)((cout0 + (wave * NWI + i) * 8 + lrow) * K * ES + schunk * 16);
 
     auto issue_x = [&](int c) {
-        half_t* dst = xs + (c & (NXBUF - 1)) * XROWS * HK;
 #pragma unroll
         for (int i = 0; i < NXI; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(dst + (wave * NXI + i) * 8 * HK), 16, xoff[i],
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(xs + (wave * NXI + i) * 8 * HK), 16, xoff[i],
                                                      c * (HK * 2), 0, 0);
     };
     // W(q): K offset (tap*Cin + chunk*64) halves; tracked incrementally for q+2 (no divisions in the loop)
@@ -225,13 +204,13 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
             const int row = (wp * XT + t) * 16 + fr;
             ax[t] = *reinterpret_cast<const int4v*>(wl + row * HK + (((kk * 4 + fq) ^ (row & 7)) << 3));
         }
-        const char* xl = reinterpret_cast<const char*>(xs + (c & (NXBUF - 1)) * XROWS * HK) + toff * (HK * 2);
+        const char* xl = reinterpret_cast<const char*>(xs) + toff * (HK * 2);
         const int key = (kbx + toff - 2 * kh) & 7;
         bx = *reinterpret_cast<const int4v*>(xl + hoffx + (((kk * 4 + fq) ^ key) << 4));
     };
     auto read_frags = [&](int4v (&a)[NA], int4v (&b)[PT], int q, int c, int toff, int kh, int kk) {
         const half_t* wl = ws + (q & 1) * BN * HK + (wn * NA * 16) * HK;
-        const char* xl = reinterpret_cast<const char*>(xs + (c & (NXBUF - 1)) * XROWS * HK) + toff * (HK * 2);   // scalar part
+        const char* xl = reinterpret_cast<const char*>(xs) + toff * (HK * 2);   // scalar part
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int row = i * 16 + fr;
@@ -263,7 +242,6 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
 #pragma unroll
     for (int j = 0; j < PT; ++j) b0[j] = b1[j] = int4v{0, 0, 0, 0};
 
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0, s01 = 0, s12 = 0, s23 = 0, s34 = 0, s45 = 0;
     if constexpr (F8) {
         // fp8 schedule: chunk loop x 9-tap inner loop; the tap step is ONE basic block (the weight DMA of the next step
         // is issued unconditionally - the step after the last reads rows that are never consumed and is drained before
@@ -333,77 +311,39 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the surplus weight DMA must not land in the epilogue tile
     } else
     if constexpr (LEAN) {
-        static_assert(NXBUF == 1 || NXBUF == 2, "lean variant: one halo buffer, or two (the 16-wave variant) so that the next chunk's halo lands under this chunk's MFMAs");
-        STAMP(tB);
-        if (FR_DEBUG && (p.stagger & 0xffff)) {   // experiment: de-phase blocks that may share a CU
-            const int mode = (p.stagger >> 8) & 255, n = p.stagger & 255;
-            const bool late = mode == 0 ? (int)blockIdx.x >= (int)gridDim.x / 2 : mode == 1 ? (blockIdx.x & 1) : ((blockIdx.x >> 3) & 1);
-            if (late) for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(8);
-        }
         issue_x(0);
         issue_w(0);
-        constexpr int abl = ABL;      // debug build only: compile-time ablation bits (1 no MFMA, 2 no reads, 4 no W DMA, 8 no barrier)
         int tap = 0, c = 0, toff = 0, kw = 0, kh = 0;
         for (int q = 0; q < nq; ++q) {
-            STAMP(t0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // W(q) (and a halo issued at the last chunk end)
-            STAMP(t1);
-            if constexpr (!(abl & 8)) __builtin_amdgcn_s_barrier();
-            STAMP(t2);
-            if (q + 1 < nq && !(abl & 4)) issue_w(q + 1);
-            if constexpr (NXBUF == 2) { if (tap == 0 && c + 1 < nchunk) issue_x(c + 1); }   // lands during this chunk's 9 steps
-            STAMP(t3);
-            if constexpr (!(abl & 2)) {
-                read_frags(a0, b0, q, c, toff, kh, 0);
-                if constexpr (SPLIT) read_x(ax0, bx0, q, c, toff, kh, 0);
-            }
-            if constexpr ((abl & 1) != 0) {
-#pragma unroll
-                for (int i = 0; i < NA; ++i) asm volatile("" ::"v"(a0[i]));
-#pragma unroll
-                for (int j = 0; j < PT; ++j) asm volatile("" ::"v"(b0[j]));
-                asm volatile("" ::"v"(ax0[0]), "v"(bx0));
-            } else {
+            __builtin_amdgcn_s_barrier();
+            if (q + 1 < nq) issue_w(q + 1);
+            read_frags(a0, b0, q, c, toff, kh, 0);
+            if constexpr (SPLIT) read_x(ax0, bx0, q, c, toff, kh, 0);
             mfma_all(a0, b0);
             if constexpr (SPLIT) {
 #pragma unroll
                 for (int t = 0; t < XT; ++t)
                     accx[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ax0[t]), __builtin_bit_cast(half8, bx0), accx[t], 0, 0, 0);
             }
-            }
-            if constexpr (!(abl & 2)) {
-                read_frags(a1, b1, q, c, toff, kh, 1);
-                if constexpr (SPLIT) read_x(ax1, bx1, q, c, toff, kh, 1);
-            }
-            if constexpr ((abl & 1) != 0) {
-#pragma unroll
-                for (int i = 0; i < NA; ++i) asm volatile("" ::"v"(a1[i]));
-#pragma unroll
-                for (int j = 0; j < PT; ++j) asm volatile("" ::"v"(b1[j]));
-                asm volatile("" ::"v"(ax1[0]), "v"(bx1));
-            } else {
+            read_frags(a1, b1, q, c, toff, kh, 1);
+            if constexpr (SPLIT) read_x(ax1, bx1, q, c, toff, kh, 1);
             mfma_all(a1, b1);
             if constexpr (SPLIT) {
 #pragma unroll
                 for (int t = 0; t < XT; ++t)
                     accx[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, ax1[t]), __builtin_bit_cast(half8, bx1), accx[t], 0, 0, 0);
             }
-            }
-            STAMP(t4);
             ++tap; ++kw; ++toff;
             if (kw == 3) { kw = 0; toff += HW - 3; ++kh; }
             if (tap == 9) {
                 tap = 0; kw = 0; toff = 0; kh = 0; ++c;
-                if constexpr (NXBUF == 1) {
                 if (c < nchunk) {                                    // reload the single halo buffer
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();                    // every wave is done reading chunk c-1
                     issue_x(c);
                 }
-                }
             }
-            STAMP(t5);
-            if (STAMPS) { s01 += t1 - t0; s12 += t2 - t1; s23 += t3 - t2; s34 += t4 - t3; s45 += t5 - t4; }
         }
     } else {
     issue_x(0);
@@ -421,7 +361,6 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
     // the lgkmcnt(0) before the barrier does not expose the last read's latency.
     auto step = [&](int q, auto issue_tag) {
         constexpr bool ISSUE = decltype(issue_tag)::value;
-        STAMP(t0);
         read_frags(a1, b1, q, c, toff, kh, 1);
         mfma_all(a0, b0);
 #pragma unroll
@@ -432,17 +371,13 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
         }
         __builtin_amdgcn_sched_group_barrier(0x008, NA * PT - (NA + PT), 0);
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(t1);
         int ntap = tap + 1, nkw = kw + 1, ntoff = toff + 1, nkh = kh, nc = c;
         if (nkw == 3) { nkw = 0; ntoff += HW - 3; ++nkh; }
         if (ntap == 9) { ntap = 0; nkw = 0; ntoff = 0; nkh = 0; ++nc; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // this wave's reads of W(q)'s buffer are in registers
         if (x_inflight) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NXI) : "memory");   // W(q+1) landed, halo may fly
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        STAMP(t2);
         __builtin_amdgcn_s_barrier();
-        STAMP(t3);
-        STAMP(t4);
         __builtin_amdgcn_sched_barrier(0);
         if (ISSUE) issue_w(q + 2);
         read_frags(a0, b0, q + 1, nc, ntoff, nkh, 0);      // harmless on the last step (stays inside the LDS buffers)
@@ -469,15 +404,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
         // still means W(q+1)..W(q+2) landed; once per 9 steps
         x_inflight = false;
         if (tap == 0 && c + 1 < nchunk) { issue_x(c + 1); x_inflight = true; }
-        STAMP(t5);
-        if (STAMPS) { s01 += t1 - t0; s12 += t2 - t1; s23 += t3 - t2; s34 += t4 - t3; s45 += t5 - t4; }
         tap = ntap; kw = nkw; toff = ntoff; kh = nkh; c = nc;
     };
     int q = 0;
     for (; q + 2 < nq; ++q) step(q, std::true_type{});
     for (; q < nq; ++q) step(q, std::false_type{});
     }
-    STAMP(tC);
 
     // ---- epilogue through LDS: the tile's output is 196 consecutive pixels x BN couts, so it is staged
     // as [px][BN] f16 (row pitch + 16 B against bank conflicts) and moved with 16-byte fully coalesced
@@ -566,39 +498,23 @@ __global__ __launch_bounds__(NW * 64, MINW) void conv_halo_kernel(HaloP p) {
             }
         }
     }
-    if (STAMPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(tD);
-    if (STAMPS && p.stamps && lane == 0) {
-        unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-        o[0] = s01; o[1] = s12; o[2] = s23; o[3] = s34; o[4] = s45;
-        o[5] = tB - tA; o[6] = tC - tB; o[7] = tD - tC;
-    }
 #endif
 }
 
-template <int WN, int NPT, int XROWS, int NXBUF, int MINW, bool LEAN = false, int NA = 4, bool F8 = false, int NW = 8, int ABL = 0>
+template <int WN, int NPT, int XROWS, bool LEAN = false, bool F8 = false>
 static int launch_halo(const HaloP& p, hipStream_t s) {
-    constexpr int BN = 16 * NA * WN;
-    constexpr size_t opnd = (size_t)(NXBUF * XROWS * HK + 2 * BN * HK) * sizeof(half_t);
+    constexpr int BN = 64 * WN;
+    constexpr size_t opnd = (size_t)(XROWS * HK + 2 * BN * HK) * sizeof(half_t);
     constexpr size_t epi = (size_t)NPT * 16 * (BN + 8) * sizeof(half_t);          // output staging tile
     constexpr size_t lds = opnd > epi ? opnd : epi;
     const int blocks = ((p.B + p.G - 1) / p.G) * p.tiles_per_img * (p.Cout / BN);
-    if constexpr (FR_DEBUG) {                  // stamped twin: debug build only
-        if (p.stamps) {
-            static FrDevLatch dl;
-            auto dk = conv_halo_kernel<WN, NPT, XROWS, NXBUF, MINW, true, LEAN, NA, F8, NW, ABL>;
-            if (!fr_raise_lds(reinterpret_cast<const void*>(dk), lds, dl)) { fr_set_error("conv_halo: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-            dk<<<blocks, NW * 64, lds, s>>>(p);
-            return FR_OK;
-        }
-    }
     static FrDevLatch latch;
-    auto kern = conv_halo_kernel<WN, NPT, XROWS, NXBUF, MINW, false, LEAN, NA, F8, NW, ABL>;
+    auto kern = conv_halo_kernel<WN, NPT, XROWS, LEAN, F8>;
     if (!fr_raise_lds(reinterpret_cast<const void*>(kern), lds, latch)) {
         fr_set_error("conv_halo: cannot raise dynamic LDS to %zu bytes", lds);
         return FR_E_LAUNCH;
     }
-    kern<<<blocks, NW * 64, lds, s>>>(p);
+    kern<<<blocks, 512, lds, s>>>(p);
     return FR_OK;
 }
 
@@ -623,54 +539,12 @@ int fr_conv_halo_try(const fr_conv_args* a, hipStream_t s) {
     p.TH = TH; p.tiles_per_img = a->H / TH; p.G = G;
     p.xbytes = (unsigned)((int64_t)a->B * a->H * a->W * a->Cin * 2);
     p.wbytes = (unsigned)((int64_t)a->Cout * 9 * a->Cin * 2);
-    p.stamps = (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS");        // always NULL in the product build
-    p.stagger = fr_dbg_int("FR_HALO_STAGGER", 0);
     int rc;
-    if (a->H == 7) rc = launch_halo<2, 13, 384, 1, 4, true>(p, s);        // lean schedule; halo rows: 4 x 9 x 9 = 324
-    else if (FR_DEBUG && (a->H == 56 || a->H == 112) && fr_dbg_int("FR_HALO_LEAN64", 0)) {
-        if constexpr (FR_DEBUG) {
-            if (a->H == 112) rc = launch_halo<1, 14, 512, 1, 4, true>(p, s);
-            else switch (fr_dbg_int("FR_HALO_LEAN64", 0)) {     // 56x56: the lean schedule and its compile-time ablations
-                case 2: rc = launch_halo<1, 14, 384, 1, 4, true, 4, false, 8, 4>(p, s); break;    // no W DMA after the first
-                case 3: rc = launch_halo<1, 14, 384, 1, 4, true, 4, false, 8, 1>(p, s); break;    // no MFMA
-                case 4: rc = launch_halo<1, 14, 384, 1, 4, true, 4, false, 8, 2>(p, s); break;    // no fragment reads
-                case 5: rc = launch_halo<1, 14, 384, 1, 4, true, 4, false, 8, 7>(p, s); break;    // skeleton
-                case 6: rc = launch_halo<1, 14, 384, 1, 4, true, 4, false, 8, 8>(p, s); break;    // no barrier
-                default: rc = launch_halo<1, 14, 384, 1, 4, true>(p, s);
-            }
-        }
-        else rc = FR_E_INVALID;
-    }
-    else if (a->H == 56) rc = launch_halo<1, 14, 384, 1, 4>(p, s);
-    else if (a->H == 112) rc = launch_halo<1, 14, 512, 1, 4>(p, s);
-    else {
-        // 28x28 and 14x14 layers run as two lean blocks per CU.  Debug build: FR_HALO_LEAN bit 0 / bit 1 = 0 selects
-        // the pipelined one-block-per-CU schedule for 28x28 / 14x14 instead (kept as a measured alternative).
-        const int lean = fr_dbg_int("FR_HALO_LEAN", 3);
-        const int nw4 = fr_dbg_int("FR_HALO_NW4", HALO_NW4_DEFAULT);      // bit 0: 28x28, bit 1: 14x14 on the 4-wave lean variant
-        if ((lean & 1) && a->H == 28) rc = (nw4 & 1) ? launch_halo<2, 13, 320, 1, 2, true, 4, false, 4>(p, s) : launch_halo<2, 13, 320, 1, 4, true>(p, s);
-        else if (FR_DEBUG && a->H == 14 && (p.stagger >> 16)) {
-            if constexpr (FR_DEBUG) {
-                switch (p.stagger >> 16) {
-                    case 1: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 1>(p, s); break;
-                    case 2: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 2>(p, s); break;
-                    case 3: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 3>(p, s); break;
-                    case 4: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 4>(p, s); break;
-                    case 6: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 6>(p, s); break;
-                    case 7: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 7>(p, s); break;
-                    case 8: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 8>(p, s); break;
-                    default: rc = launch_halo<2, 13, 256, 1, 4, true, 4, false, 8, 15>(p, s); break;
-                }
-            } else rc = FR_E_INVALID;
-        }
-        else if (FR_DEBUG && a->H == 14 && a->Cout % 256 == 0 && fr_dbg_int("FR_HALO_W16", 0)) {
-            if constexpr (FR_DEBUG) rc = launch_halo<4, 13, 256, 2, 4, true, 4, false, 16>(p, s);   // one 16-wave block per CU, two halo buffers
-            else rc = FR_E_INVALID;
-        }
-        else if ((lean & 2) && a->H == 14) rc = (nw4 & 2) ? launch_halo<2, 13, 256, 1, 2, true, 4, false, 4>(p, s) : launch_halo<2, 13, 256, 1, 4, true>(p, s);
-        else if constexpr (FR_DEBUG) rc = (a->Cout % 256 == 0) ? launch_halo<4, 13, 320, 2, 2>(p, s) : launch_halo<2, 13, 320, 2, 2>(p, s);
-        else rc = FR_E_INVALID;
-    }
+    if (a->H == 7) rc = launch_halo<2, 13, 384, true>(p, s);             // lean schedule; halo rows: 4 x 9 x 9 = 324
+    else if (a->H == 14) rc = launch_halo<2, 13, 256, true>(p, s);
+    else if (a->H == 28) rc = launch_halo<2, 13, 320, true>(p, s);
+    else if (a->H == 56) rc = launch_halo<1, 14, 384>(p, s);             // single chunk: the pipelined schedule
+    else rc = launch_halo<1, 14, 512>(p, s);                             // 112x112
     return rc == FR_OK ? 1 : rc;
 }
 
@@ -690,10 +564,8 @@ extern "C" int fr_conv_nhwc_f8(const fr_conv_f8_args* a, fr_stream_t stream) {
     p.TH = a->H == 14 ? 14 : 7; p.tiles_per_img = a->H / p.TH; p.G = 1;
     p.xbytes = (unsigned)((int64_t)a->B * a->H * a->W * a->Cin);
     p.wbytes = (unsigned)((int64_t)a->Cout * 9 * a->Cin);
-    p.stamps = (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS");
-    p.stagger = 0;
     hipStream_t s = fr_stream(stream);
-    const int rc = a->H == 28 ? launch_halo<2, 13, 320, 1, 4, true, 4, true>(p, s) : launch_halo<2, 13, 256, 1, 4, true, 4, true>(p, s);
+    const int rc = a->H == 28 ? launch_halo<2, 13, 320, true, true>(p, s) : launch_halo<2, 13, 256, true, true>(p, s);
     if (rc != FR_OK) return rc;
     FR_CHECK_LAUNCH("conv_halo_f8");
     return FR_OK;

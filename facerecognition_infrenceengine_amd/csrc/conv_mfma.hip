@@ -9,8 +9,8 @@
 //   accumulator quad, i.e. 8 contiguous bytes of the NHWC output row.
 // Tiling: 256 threads = 4 waves, each wave 64 couts x 64 pixels (4x4 MFMA tiles, 64 acc VGPRs);
 //   block = (64*WN couts) x (64*(4/WN) pixels); K step 64 (always inside one filter tap when
-//   Cin >= 64); two LDS stages, register-prefetched (global->VGPR issued before the MFMAs of the
-//   current stage, VGPR->LDS after them), one barrier per K step.
+//   Cin >= 64); two LDS stages filled by LDS-DMA (the next stage's loads issued before the MFMAs of
+//   the current stage), one barrier per K step.
 // LDS image: rows of 64 halves (128 B), 16-B chunk index XOR (row & 7): conflict-free for the
 //   ds_read_b128 fragment reads of the 16x16x32 operand layout.
 // Zero padding / M tail: buffer loads with the offset forced out of range return 0.
@@ -26,10 +26,6 @@ struct ConvP {
     unsigned xbytes, wbytes;
     const half_t* x2; int C2, nk_main; unsigned x2bytes;      // second input through a 1x1 tap (fr_conv_args.x2): K steps nk_main .. nk-1
 };
-
-__device__ __forceinline__ int4v buf_load16(__amdgpu_buffer_rsrc_t rs, unsigned off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
-}
 
 template <int WN>
 __device__ __forceinline__ void conv_epilogue(const ConvP& p, float4v (&acc)[4][4], int cout0, int m0, int wc, int wp,
@@ -80,9 +76,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, float4v (&acc)[4][
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// GLDS: stage tiles with buffer_load ... lds (16 B per lane straight into LDS, no VGPR round trip and
+// Tiles are staged with buffer_load ... lds (16 B per lane straight into LDS, no VGPR round trip and
 // no ds_write): one wave-instruction fills 8 rows x 128 B; the XOR swizzle moves to the SOURCE chunk.
-template <int WN, bool SMALL_CIN, bool GLDS>
+template <int WN, bool SMALL_CIN>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 #if defined(__HIP_DEVICE_COMPILE__)      // device-only builtins / LDS address-space casts: keep the host pass to the stub
     constexpr int WP = 4 / WN;
@@ -96,13 +92,12 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
     const int wc = wave % WN, wp = wave / WN;
     const int cout0 = blockIdx.y * BN;
     const int m0 = blockIdx.x * BM;
-    // loader mapping: thread -> (row, 16-B chunk) of a 128-B LDS row.  Register staging: rows tid/8 + 32*i.
-    // GLDS: wave w fills row groups w*ROWS + i (8 rows each), lane -> row lane/8, LDS chunk lane%8, and
+    // loader mapping: wave w fills row groups w*ROWS + i (8 rows each), lane -> row lane/8, LDS chunk lane%8, and
     // reads the source chunk (lane%8) ^ (row & 7) so that the linear DMA image IS the swizzled image.
-    const int trow = GLDS ? (lane >> 3) : (tid >> 3);
-    const int tchunk = GLDS ? ((lane & 7) ^ ((lane >> 3) & 7)) : (tid & 7);
-    auto wrow = [&](int i) { return GLDS ? (wave * WROWS + i) * 8 + trow : trow + 32 * i; };
-    auto xrow = [&](int i) { return GLDS ? (wave * XROWS + i) * 8 + trow : trow + 32 * i; };
+    const int trow = lane >> 3;
+    const int tchunk = (lane & 7) ^ ((lane >> 3) & 7);
+    auto wrow = [&](int i) { return (wave * WROWS + i) * 8 + trow; };
+    auto xrow = [&](int i) { return (wave * XROWS + i) * 8 + trow; };
 
     __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
     __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
@@ -145,7 +140,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
         ke = min(p.nk, ks + per);
     }
 
-    int4v wreg[WROWS], xreg[XROWS];
     const int cin_steps = SMALL_CIN ? 1 : (p.Cin / BK);
 
     auto gload_lds = [&](int s, int buf) {
@@ -181,47 +175,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(xl + (wave * XROWS + i) * 8 * BK), 16, off, 0, 0, 0);
         }
     };
-    auto gload = [&](int s) {
-        int kh, kw, tapoff;
-        if (SMALL_CIN) {
-            int tap = s * 8 + tchunk;              // one 16-B chunk (8 padded channels) per tap
-            kh = tap / p.KW; kw = tap - kh * p.KW;
-            if (tap >= p.KH * p.KW) kh = 1 << 14;  // beyond the filter: force out of range
-            tapoff = (kh * p.W + kw) * p.Cin * 2;
-        } else {
-            int tap = s / cin_steps, c0 = (s - tap * cin_steps) * BK;
-            kh = tap / p.KW; kw = tap - kh * p.KW;
-            tapoff = ((kh * p.W + kw) * p.Cin + c0) * 2;
-        }
-#pragma unroll
-        for (int i = 0; i < WROWS; ++i) wreg[i] = buf_load16(wrs, wbase[i] + (unsigned)s * (BK * 2));
-        if (!SMALL_CIN && s >= p.nk_main) {
-#pragma unroll
-            for (int i = 0; i < XROWS; ++i) xreg[i] = buf_load16(x2rs, x2off(i, (s - p.nk_main) * BK));
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < XROWS; ++i) {
-            int hi = (xhw[i] >> 16) + kh, wi = (int)(short)(xhw[i] & 0xffff) + kw;
-            bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            unsigned off = ok ? (unsigned)(xbase[i] + tapoff) : 0x80000000u;
-            xreg[i] = buf_load16(xrs, off);
-        }
-    };
-    auto lstore = [&](int buf) {
-        half_t* wl = lds + buf * (BN + BM) * BK;
-        half_t* xl = wl + BN * BK;
-#pragma unroll
-        for (int i = 0; i < WROWS; ++i) {
-            int row = trow + 32 * i;
-            *reinterpret_cast<int4v*>(wl + row * BK + ((tchunk ^ (row & 7)) << 3)) = wreg[i];
-        }
-#pragma unroll
-        for (int i = 0; i < XROWS; ++i) {
-            int row = trow + 32 * i;
-            *reinterpret_cast<int4v*>(xl + row * BK + ((tchunk ^ (row & 7)) << 3)) = xreg[i];
-        }
-    };
 
     float4v acc[4][4];
 #pragma unroll
@@ -231,20 +184,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 
     const int fr = lane & 15, fq = lane >> 4;
     if (ks < ke) {
-        if (GLDS) {
-            gload_lds(ks, 0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-            gload(ks);
-            lstore(0);
-        }
+        gload_lds(ks, 0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
     for (int s = ks; s < ke; ++s) {
         const int buf = (s - ks) & 1;
-        if (s + 1 < ke) {
-            if (GLDS) gload_lds(s + 1, buf ^ 1); else gload(s + 1);
-        }
+        if (s + 1 < ke) gload_lds(s + 1, buf ^ 1);
         const half_t* wl = lds + buf * (BN + BM) * BK + (wc * 64) * BK;
         const half_t* xl = lds + buf * (BN + BM) * BK + BN * BK + (wp * 64) * BK;
 #pragma unroll
@@ -263,8 +209,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
-        if (GLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (s + 1 < ke) lstore(buf ^ 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 
@@ -272,164 +217,15 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 #endif
 }
 
-// ---------------------------------------------------------------------------------------------
-// Four-stage ring variant (NOT on the product path: measured slower than the two-stage kernel above, compiled into
-// the debug build only, FR_CONV_KERNEL=2): K step 32, ring of 4 LDS stages (16 KB each, 64 KB/block,
-// 2 blocks/CU), tiles staged by LDS-DMA (buffer_load ... lds) that stay in flight ACROSS barriers:
-// per step  s_waitcnt vmcnt(8) [stage s landed; s+1, s+2 may still fly] -> raw s_barrier ->
-// issue stage s+3 into the buffer freed by step s-1 -> 8 ds_read_b128 + 16 MFMA on stage s.
-// LDS rows are 64 B (4 chunks of 16 B); chunk index XOR swz[(row>>2)&3], swz = {0,2,3,1}: the four
-// 16-lane groups of a ds_read_b128 each touch 16 distinct 16-B slots of the 256-B bank row.
-// One LDS-DMA wave-instruction fills 16 rows; the swizzle is applied to the SOURCE chunk.
-#define PK 32
-#define PNS 4
-template <int WN, bool SMALL_CIN>
-__global__ __launch_bounds__(256, 2) void conv_mfma_pipe(ConvP p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int WP = 4 / WN;
-    constexpr int BN = 64 * WN, BM = 64 * WP;
-    constexpr int WI = BN / 64, XI = BM / 64;            // LDS-DMA instructions per thread per stage (16 rows each)
-    constexpr int NLD = WI + XI;                          // = 4
-    constexpr int STAGE = (BN + BM) * PK;                 // halves per stage
-    __shared__ __attribute__((aligned(16))) half_t lds[PNS * STAGE];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wc = wave % WN, wp = wave / WN;
-    // XCD-aware tile order: blocks b and b+8 share an XCD (round-robin dispatch), so XCD x walks the
-    // contiguous tile range [x*per, ...) with the cout tile innermost: co-resident blocks of one XCD
-    // then share input rows / halos and weights in that XCD's L2 (speed only, any placement is correct).
-    int tile;
-    {
-        const int nwg = gridDim.x, b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    }
-    const int ntn = p.Cout / BN;
-    const int cout0 = (tile % ntn) * BN, m0 = (tile / ntn) * BM;
-    const int lrow = lane >> 2;                                              // row inside a 16-row group
-    const int swz_l = (0x1320 >> (4 * ((lane >> 4) & 3))) & 3;               // swz[(row>>2)&3] of the loader row
-    const int schunk = (lane & 3) ^ swz_l;                                   // source chunk of this lane
-
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
-
-    int xbase[XI], xhw[XI];
-    const int HoWo = p.Ho * p.Wo;
-#pragma unroll
-    for (int i = 0; i < XI; ++i) {
-        int m = m0 + (wave * XI + i) * 16 + lrow;
-        if (m < p.M) {
-            int n = m / HoWo, r = m - n * HoWo;
-            int ho = r / p.Wo, wo = r - ho * p.Wo;
-            int bh = ho * p.stride - p.pad, bw = wo * p.stride - p.pad;
-            xbase[i] = (((n * p.H + bh) * p.W + bw) * p.Cin + (SMALL_CIN ? 0 : schunk * 8)) * 2;
-            xhw[i] = (bh << 16) | (bw & 0xffff);
-        } else {
-            xbase[i] = 0;
-            xhw[i] = (int)0x80000000u;
-        }
-    }
-    unsigned wbase[WI];
-#pragma unroll
-    for (int i = 0; i < WI; ++i) wbase[i] = ((unsigned)(cout0 + (wave * WI + i) * 16 + lrow) * p.K + schunk * 8) * 2;
-
-    int ks = 0, ke = p.nk;                                 // nk counts 32-wide steps here
-    if (p.splitk > 1) {
-        int per = (p.nk + p.splitk - 1) / p.splitk;
-        ks = blockIdx.z * per;
-        ke = min(p.nk, ks + per);
-    }
-    const int cin_steps = SMALL_CIN ? 1 : (p.Cin / PK);
-
-    auto issue = [&](int s) {                              // LDS-DMA of K step s into ring slot (s - ks) % PNS
-        int kh, kw, tapoff;
-        if (SMALL_CIN) {
-            int tap = s * 4 + schunk;
-            kh = tap / p.KW; kw = tap - kh * p.KW;
-            if (tap >= p.KH * p.KW) kh = 1 << 14;
-            tapoff = (kh * p.W + kw) * p.Cin * 2;
-        } else {
-            int tap = s / cin_steps, c0 = (s - tap * cin_steps) * PK;
-            kh = tap / p.KW; kw = tap - kh * p.KW;
-            tapoff = ((kh * p.W + kw) * p.Cin + c0) * 2;
-        }
-        half_t* wl = lds + ((s - ks) % PNS) * STAGE;
-        half_t* xl = wl + BN * PK;
-#pragma unroll
-        for (int i = 0; i < WI; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (lds_ptr_t)(wl + (wave * WI + i) * 16 * PK), 16,
-                                                     wbase[i] + (unsigned)s * (PK * 2), 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < XI; ++i) {
-            int hi = (xhw[i] >> 16) + kh, wi = (int)(short)(xhw[i] & 0xffff) + kw;
-            bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            unsigned off = ok ? (unsigned)(xbase[i] + tapoff) : 0x80000000u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(xl + (wave * XI + i) * 16 * PK), 16, off, 0, 0, 0);
-        }
-    };
-
-    float4v acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = float4v{0.f, 0.f, 0.f, 0.f};
-
-    const int fr = lane & 15, fq = lane >> 4;
-    const int rdoff = fr * PK + ((fq ^ ((0x1320 >> (4 * ((fr >> 2) & 3))) & 3)) << 3);   // halves, within a 16-row tile
-#pragma unroll
-    for (int d = 0; d < PNS - 1; ++d)
-        if (ks + d < ke) issue(ks + d);
-    for (int s = ks; s < ke; ++s) {
-        const int rem = ke - 1 - s;                        // younger stages that exist
-        if (rem >= PNS - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD * (PNS - 2)) : "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLD) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (s + PNS - 1 < ke) issue(s + PNS - 1);
-        const half_t* wl = lds + ((s - ks) % PNS) * STAGE + (wc * 64) * PK;
-        const half_t* xl = lds + ((s - ks) % PNS) * STAGE + BN * PK + (wp * 64) * PK;
-        half8 a[4], b[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            a[i] = *reinterpret_cast<const half8*>(wl + i * 16 * PK + rdoff);
-            b[i] = *reinterpret_cast<const half8*>(xl + i * 16 * PK + rdoff);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-    conv_epilogue<WN>(p, acc, cout0, m0, wc, wp, fr, fq);
-#endif
-}
-
-// Generic-path variant (layers the halo kernel does not take): FR_CONV_KERNEL = 1 (default) two-stage
-// LDS-DMA loader, K step 64; 2 = four-stage LDS-DMA ring, K step 32 (slower: a barrier per 16 MFMAs and ~100
-// cycles of issue per LDS-DMA piece outweigh the deeper prefetch); 0 = two-stage register-staged loader.
-static int conv_kernel_choice() { return fr_dbg_int("FR_CONV_KERNEL", 1); }      // product build: always 1
-
 template <int WN, bool SMALL>
 static void launch_conv(const ConvP& p, hipStream_t s) {
     constexpr int BN = 64 * WN, BM = 64 * (4 / WN);
     dim3 grid((p.M + BM - 1) / BM, p.Cout / BN, p.splitk > 1 ? p.splitk : 1);
-    if constexpr (FR_DEBUG) {                  // measured alternatives, debug build only (none of them takes a second input)
-        const int which = p.x2 ? 1 : conv_kernel_choice();
-        if (which == 2) {
-            ConvP q = p;
-            q.nk = p.K / PK;
-            dim3 g1(grid.x * grid.y, 1, grid.z);
-            conv_mfma_pipe<WN, SMALL><<<g1, 256, 0, s>>>(q);
-            return;
-        }
-        if (which == 0) { conv_mfma_kernel<WN, SMALL, false><<<grid, 256, 0, s>>>(p); return; }
-    }
-    conv_mfma_kernel<WN, SMALL, true><<<grid, 256, 0, s>>>(p);
+    conv_mfma_kernel<WN, SMALL><<<grid, 256, 0, s>>>(p);
 }
 
 int fr_conv_halo_try(const fr_conv_args* a, hipStream_t s);     // conv_halo.hip
 int fr_conv_stem_try(const fr_conv_args* a, hipStream_t s);     // conv_stem.hip
-
-static bool conv_halo_enabled() { return fr_dbg_int("FR_CONV_HALO", 1) != 0; }   // debug build: FR_CONV_HALO=0 for A/B
 
 extern "C" int fr_conv_nhwc_f16(const fr_conv_args* a, fr_stream_t stream) {
     FR_REQUIRE(a, "fr_conv_nhwc_f16: null args");
@@ -468,13 +264,11 @@ extern "C" int fr_conv_nhwc_f16(const fr_conv_args* a, fr_stream_t stream) {
                "fr_conv_nhwc_f16: tensor too large for 32-bit buffer offsets (split the batch)");
     p.M = (int)M; p.nk = p.K / BK; p.xbytes = (unsigned)xbytes; p.wbytes = (unsigned)wbytes;
     hipStream_t s = fr_stream(stream);
-    if (conv_halo_enabled()) {
-        int h = fr_conv_halo_try(a, s);
-        if (h < 0) return h;
-        if (h == 1) {
-            FR_CHECK_LAUNCH("conv_halo_kernel");
-            return FR_OK;
-        }
+    const int h = fr_conv_halo_try(a, s);
+    if (h < 0) return h;
+    if (h == 1) {
+        FR_CHECK_LAUNCH("conv_halo_kernel");
+        return FR_OK;
     }
     if (small) {                                   // the packed stem has its own kernel (conv_stem.hip)
         if (fr_conv_stem_try(a, s) == 1) {

@@ -50,8 +50,6 @@ struct StageP {
     const float* prm;       // [nconv][10][256]
     int B, nconv;
     unsigned xbytes, wbytes;
-    unsigned long long* stamps;     // diagnostic build only (FR_DBG_STAMPS=<device ptr>): per-wave cycle sums
-    int dephase;                    // diagnostic build only (FR_S14_DEPHASE): start delay per XCD-local block index, in units of 64 s_sleep(127)
 };
 
 __device__ __forceinline__ float4v mfma16(const int4v& a, const int4v& b, float4v c) {
@@ -60,24 +58,8 @@ __device__ __forceinline__ float4v mfma16(const int4v& a, const int4v& b, float4
 
 }  // namespace
 
-#define S14_STAMP_L(var, level)                                                            \
-    do {                                                                                    \
-        if (STAMPS >= level) {                                                                       \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
-#define S14_STAMP(var) S14_STAMP_L(var, 1)
-
-// STAMPS (diagnostic build): 1 = per-conv phases only (3 stamps per conv), 2 = per-step segments too.
-// ABL (diagnostic build): compile-time ablation bits of the K loop - 1 no MFMA, 2 no fragment reads, 4 no weight DMA, 8 no barrier
-template <int STAMPS, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, tA = 0, tB = 0, tC = 0, sw = 0, sb = 0, sm = 0, se = 0, sp = 0, rA = 0, rB = 0, sl_ = 0, t0p = 0;
-    S14_STAMP(tA);
-    if (STAMPS) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rA)::"memory");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* img = lds;
     char* ring = lds + S14_IMG;
@@ -158,23 +140,14 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
         for (int j = 0; j < 7; ++j) set_tap_one(j, dy, dx);
     };
     auto rd_a = [&](int slot, int i) {
-        if constexpr (ABL & 2) { int4v v = {slot, i, 0, 0}; asm volatile("" : "+v"(v)); return v; }
-        else return *reinterpret_cast<const int4v*>(ring + slot * S14_SLOT + a_own + i * 1024);
+        return *reinterpret_cast<const int4v*>(ring + slot * S14_SLOT + a_own + i * 1024);
     };
     auto rd_b = [&](int g, int j) {
-        if constexpr (ABL & 2) { int4v v = {g, boff[j], 0, 0}; asm volatile("" : "+v"(v)); return v; }
-        else return *reinterpret_cast<const int4v*>(img + (g >> 1) * S14_PLANE + ((g & 1) ? (boff[j] ^ 64) : boff[j]));
+        return *reinterpret_cast<const int4v*>(img + (g >> 1) * S14_PLANE + ((g & 1) ? (boff[j] ^ 64) : boff[j]));
     };
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // image, W(0), W(1)
     __builtin_amdgcn_s_barrier();
-    if (STAMPS && p.dephase) {                                       // experiment: de-phase the workgroups that share an XCD (and its L2)
-        const int nd = (blockIdx.x >> 3) * p.dephase;
-        for (int i = 0; i < nd; ++i)
-            for (int q_ = 0; q_ < 64; ++q_) __builtin_amdgcn_s_sleep(127);
-        __builtin_amdgcn_s_barrier();
-        S14_STAMP(tA);
-    }
 
 #define S14_PIN() __builtin_amdgcn_sched_barrier(0)
     // One K step (local index k of a 24-step group: slot k % 3, channel group g = k & 7) on the fragments (ac, axc, b,
@@ -186,10 +159,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     // for the other, so that the partner's MFMAs cover it.  No branches besides that: the last step of a conv
     // prefetches too - its weight fragments are the next conv's first (that slot has landed), its pixel fragments
     // are dead (the prologue re-reads them).
-    auto mm = [&](const int4v& a, const int4v& b_, float4v c) {
-        if constexpr (ABL & 1) { asm volatile("" ::"v"(a), "v"(b_)); return c; }
-        else return mfma16(a, b_, c);
-    };
     auto step = [&](int4v (&ac)[4], int4v (&an)[4], int k, int dyn, int dxn) {
         const int g = k & 7, ng = (k + 1) & 7, nslot = (k + 1) % 3;
         // read order: the four weight fragments first, the seven pixel fragments behind them, b[5]' last - LDS returns in
@@ -200,14 +169,14 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
         // the partner has the matrix pipe to itself; the partner issues its pieces behind its 18th MFMA (about when the
         // first wave's pieces are out), while the first wave has the pipe (stamps: DMA in the middle of both streams
         // 1 470 cycles per step, first / last 1 180, first / 18th: see DESIGN.md).
-        if constexpr (WP == 0 && !(ABL & 4)) { issue_w(k % 3); S14_PIN(); }
+        if constexpr (WP == 0) { issue_w(k % 3); S14_PIN(); }
         // the shared 13th pixel tile: this wave's cout tiles 2 WP, 2 WP + 1 of its own four - the same weight fragments
-        accx[0] = mm(ac[2 * WP], bx, accx[0]); accx[1] = mm(ac[2 * WP + 1], bx, accx[1]);
+        accx[0] = mfma16(ac[2 * WP], bx, accx[0]); accx[1] = mfma16(ac[2 * WP + 1], bx, accx[1]);
         S14_PIN();
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = mm(ac[i], b[j], acc[j][i]);
+            for (int i = 0; i < 4; ++i) acc[j][i] = mfma16(ac[i], b[j], acc[j][i]);
             if (j == 0) { an[0] = rd_a(nslot, 0); an[1] = rd_a(nslot, 1); }
             if (j == 1) { an[2] = rd_a(nslot, 2); an[3] = rd_a(nslot, 3); }
             if (j == 2) {
@@ -227,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
                 b[5] = rd_b(ng, 5);
             }
             S14_PIN();
-            if constexpr (WP == 1 && !(ABL & 4)) { if (j == 3) { issue_w(k % 3); S14_PIN(); } }
+            if constexpr (WP == 1) { if (j == 3) { issue_w(k % 3); S14_PIN(); } }
         }
     };
 
@@ -238,8 +207,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     accx[0] = accx[1] = float4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int conv = 0; conv < p.nconv; ++conv) {
-        S14_STAMP(tC);
-        if (STAMPS && conv) se += tC - tB;                           // the previous conv's epilogue
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         fre = lane_e & 15; fqe = lane_e >> 4; px0e = WP * 96 + fre;
@@ -251,8 +218,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) b[j] = rd_b(0, j);
         bx = rd_b(0, 6);
-        S14_STAMP(t0p);
-        if (STAMPS) sp += t0p - tC;                                  // prologue
 #pragma unroll 1
         for (int it = 0; it < 3; ++it) {                             // kernel row dy = it - 1: taps 3 it .. 3 it + 2
 #pragma unroll
@@ -261,30 +226,21 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
                 // and its weight-fragment reads of slot k % 3 have returned (all but its youngest LDS read, a pixel
                 // fragment); after the barrier that holds for every wave:
                 // slot (k + 1) % 3 may be read, slot k % 3 may be overwritten
-                S14_STAMP_L(t0, 2);
                 asm volatile("s_waitcnt vmcnt(2) lgkmcnt(1)" ::: "memory");
-                S14_STAMP_L(t1, 2);
-                if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();
-                S14_STAMP_L(t2, 2);
+                __builtin_amdgcn_s_barrier();
                 S14_PIN();
                 const int tt = k >> 3;                               // next tap: (it, tt + 1), or (it + 1, 0) after the row's last
                 const int dyn = tt < 2 ? it - 1 : it, dxn = tt < 2 ? tt : -1;
                 if ((k & 1) == 0) step(a0, a1, k, dyn, dxn);
                 else step(a1, a0, k, dyn, dxn);
-                S14_STAMP_L(t3, 2);
-                if (STAMPS >= 2) { sw += t1 - t0; sb += t2 - t1; sm += t3 - t2; }
             }
         }
-        S14_STAMP(tB);
-        if (STAMPS) sl_ += tB - t0p;
         // ---- epilogue of the conv: parameters from LDS, residual (second conv of a block), then the image in place
         const bool second = conv & 1;
         half_t* ybase = p.y + (size_t)n * img_elems;
         asm volatile("" : "+v"(px0e), "+v"(fre), "+v"(fqe));
         asm volatile("s_waitcnt vmcnt(2)" ::: "memory");             // the parameters: older than the 2 weight pieces in flight
         __builtin_amdgcn_s_barrier();                                // every wave has consumed its last fragments of the old image
-        S14_STAMP(t1);
-        if (STAMPS == 1) sw += t1 - tB;                              // level-1 stamps: epilogue segments in the per-step slots
         // First conv of a block: the NEXT conv's accumulators start as the block's input (the residual), so that its
         // epilogue needs no second operand.  That input is the OLD image - still in LDS, and the element a lane is about
         // to overwrite with its output is exactly the residual element it needs: read, then write.  The residual
@@ -337,12 +293,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
             }
         };
         if (second) tiles(std::false_type{}); else tiles(std::true_type{});
-        S14_STAMP(t2);
-        if (STAMPS == 1) sb += t2 - t1;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                                // the new image is complete
-        S14_STAMP(t3);
-        if (STAMPS == 1) sm += t3 - t2;
         if (conv == p.nconv - 1) {                                   // the run's result -> HBM
             for (int e = tid; e < S14_PX * 32; e += 512) {           // 16-B chunks: pixel x 32 chunks
                 const int px = e >> 5, c = e & 31;                   // c = plane * 8 + chunk
@@ -354,12 +306,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     };
     if (wp == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    S14_STAMP(tC);
-    if (STAMPS) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rB)::"memory");
-    if (STAMPS && p.stamps && lane == 0) {
-        unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-        o[0] = sw; o[1] = sb; o[2] = sm; o[3] = se + (tC - tB); o[4] = sp; o[5] = tC - tA; o[6] = rB - rA; o[7] = sl_;
-    }
 #endif
 }
 
@@ -397,33 +343,12 @@ extern "C" int fr_conv_stage14_f16(const void* x, void* y, const void* wstream, 
     p.B = B; p.nconv = 2 * nblocks;
     p.xbytes = (unsigned)((int64_t)B * S14_PX * S14_C * 2);
     p.wbytes = (unsigned)((int64_t)p.nconv * S14_STEPS * S14_SLOT);
-    p.stamps = (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS");    // always NULL in the product build
-    p.dephase = fr_dbg_int("FR_S14_DEPHASE", 0);
-    if constexpr (FR_DEBUG) {                                       // stamped twin: debug build only
-        if (p.stamps) {
-            static FrDevLatch dl;
-            if (fr_dbg_int("FR_S14_STAMP_LEVEL", 2) == 1) {
-                const int abl = fr_dbg_int("FR_S14_ABL", 0);
-                auto k1 = abl == 1 ? conv_stage14_kernel<1, 1> : abl == 2 ? conv_stage14_kernel<1, 2> : abl == 3 ? conv_stage14_kernel<1, 3>
-                        : abl == 4 ? conv_stage14_kernel<1, 4> : abl == 8 ? conv_stage14_kernel<1, 8> : abl == 7 ? conv_stage14_kernel<1, 7>
-                        : conv_stage14_kernel<1, 0>;
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(k1), hipFuncAttributeMaxDynamicSharedMemorySize, S14_LDS) != hipSuccess) { fr_set_error("fr_conv_stage14_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-                k1<<<B, 512, S14_LDS, fr_stream(stream)>>>(p);
-                FR_CHECK_LAUNCH("conv_stage14_kernel<stamps 1>");
-                return FR_OK;
-            }
-            if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage14_kernel<2>), S14_LDS, dl)) { fr_set_error("fr_conv_stage14_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-            conv_stage14_kernel<2><<<B, 512, S14_LDS, fr_stream(stream)>>>(p);
-            FR_CHECK_LAUNCH("conv_stage14_kernel<stamps>");
-            return FR_OK;
-        }
-    }
     static FrDevLatch latch;
-    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage14_kernel<0>), S14_LDS, latch)) {
+    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage14_kernel), S14_LDS, latch)) {
         fr_set_error("fr_conv_stage14_f16: cannot raise dynamic LDS to %d bytes", S14_LDS);
         return FR_E_LAUNCH;
     }
-    conv_stage14_kernel<0><<<B, 512, S14_LDS, fr_stream(stream)>>>(p);
+    conv_stage14_kernel<<<B, 512, S14_LDS, fr_stream(stream)>>>(p);
     FR_CHECK_LAUNCH("conv_stage14_kernel");
     return FR_OK;
 }

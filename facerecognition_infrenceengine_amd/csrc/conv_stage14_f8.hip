@@ -48,7 +48,6 @@ struct StageF8P {
     const float* prm;           // [nconv][14][256]
     int B, nconv;
     unsigned xbytes8, xbytes16, wbytes;
-    unsigned long long* stamps; // diagnostic build only
 };
 
 __device__ __forceinline__ int pack_fp8x4_sat(float a, float b, float c, float d) {
@@ -71,22 +70,10 @@ __device__ __forceinline__ float4v mfma8(const Frag& a, const Frag& b, float4v c
 
 }  // namespace
 
-#define F14_STAMP(var)                                                                     \
-    do {                                                                                    \
-        if (STAMPS) {                                                                       \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
 #define F14_PIN() __builtin_amdgcn_sched_barrier(0)
 
-template <int STAMPS>
 __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long tA = 0, tB = 0, tC = 0, t0p = 0, t1 = 0, se = 0, sp = 0, sl_ = 0, rA = 0, rB = 0;
-    F14_STAMP(tA);
-    if (STAMPS) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rA)::"memory");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* img = lds;
     char* ring = lds + F14_IMG;
@@ -199,8 +186,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
 
 #pragma unroll 1
     for (int conv = 0; conv < p.nconv; ++conv) {
-        F14_STAMP(tC);
-        if (STAMPS && conv) se += tC - tB;
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
         fre = lane_e & 15; fqe = lane_e >> 4; px0e = WP * 96 + fre;
@@ -255,8 +240,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
 #pragma unroll
         for (int t = 0; t < 3; ++t) bt[t] = rd_b(0, t);
         bx = rd_b(0, 6);
-        F14_STAMP(t0p);
-        if (STAMPS) sp += t0p - tC;
 #pragma unroll 1
         for (int it = 0; it < 3; ++it) {                             // kernel row dy = it - 1
 #pragma unroll
@@ -272,8 +255,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
                 else step(a1, a0, k, dyn, dxn);
             }
         }
-        F14_STAMP(tB);
-        if (STAMPS) sl_ += tB - t0p;
         // ---- epilogue: dequantise, bias, PReLU (first conv), f16; second conv: f16 -> HBM; next conv's codes -> the image
         const bool second = conv & 1;
         asm volatile("" : "+v"(px0e), "+v"(fre), "+v"(fqe));
@@ -350,13 +331,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
     };
     if (wp == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    F14_STAMP(tC);
-    if (STAMPS) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rB)::"memory");
-    if (STAMPS && p.stamps && lane == 0) {
-        unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-        o[0] = 0; o[1] = 0; o[2] = 0; o[3] = se + (tC - tB); o[4] = sp; o[5] = tC - tA; o[6] = rB - rA; o[7] = sl_;
-    }
-    (void)t1;
 #endif
 }
 
@@ -395,21 +369,12 @@ extern "C" int fr_conv_stage14_f8(const void* x8, const void* x16, void* y16, co
     p.xbytes8 = (unsigned)((int64_t)B * F14_PX * F14_C);
     p.xbytes16 = 2 * p.xbytes8;
     p.wbytes = (unsigned)((int64_t)p.nconv * F14_STEPS * F14_SLOT);
-    p.stamps = (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS");
-    if constexpr (FR_DEBUG) {
-        if (p.stamps) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stage14_f8_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, F14_LDS) != hipSuccess) { fr_set_error("fr_conv_stage14_f8: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-            conv_stage14_f8_kernel<1><<<B, 512, F14_LDS, fr_stream(stream)>>>(p);
-            FR_CHECK_LAUNCH("conv_stage14_f8_kernel<stamps>");
-            return FR_OK;
-        }
-    }
     static FrDevLatch latch;
-    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage14_f8_kernel<0>), F14_LDS, latch)) {
+    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage14_f8_kernel), F14_LDS, latch)) {
         fr_set_error("fr_conv_stage14_f8: cannot raise dynamic LDS to %d bytes", F14_LDS);
         return FR_E_LAUNCH;
     }
-    conv_stage14_f8_kernel<0><<<B, 512, F14_LDS, fr_stream(stream)>>>(p);
+    conv_stage14_f8_kernel<<<B, 512, F14_LDS, fr_stream(stream)>>>(p);
     FR_CHECK_LAUNCH("conv_stage14_f8_kernel");
     return FR_OK;
 }

@@ -52,7 +52,6 @@ struct Stage28P {
     half_t* x; half_t* mid; const half_t* w; const float* prm;
     int B, nconv;
     unsigned xbytes, wbytes;
-    unsigned long long* stamps;     // diagnostic build only (FR_DBG_STAMPS=<device ptr>): per-wave cycle sums
 };
 
 __device__ __forceinline__ float4v mm16(const int4v& a, const int4v& b, float4v c) {
@@ -62,22 +61,9 @@ __device__ __forceinline__ float4v mm16(const int4v& a, const int4v& b, float4v 
 }  // namespace
 
 #define S28_PIN() __builtin_amdgcn_sched_barrier(0)
-#define S28_STAMP(var)                                                                      \
-    do {                                                                                    \
-        if (STAMPS) {                                                                       \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");      \
-            __builtin_amdgcn_sched_barrier(0);                                              \
-        }                                                                                   \
-    } while (0)
 
-// STAMPS (diagnostic build): s_memtime sums per wave - load wait at a pass start, K loop, epilogue issue, drain
-template <int STAMPS>
 __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    unsigned long long tA = 0, t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, rA = 0, rB = 0, s_wait = 0, s_k = 0, s_epi = 0, s_drain = 0, s_pro = 0;
-    S28_STAMP(tA);
-    if (STAMPS) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rA)::"memory");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     char* ring = lds + S28_RING;
     const float* lprm = reinterpret_cast<const float*>(lds + S28_PRMO);
@@ -182,7 +168,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
         auto rd_b = [&](int gg, int j) { return *reinterpret_cast<const int4v*>(lds + (gg ? (boff[j] ^ 64) : boff[j])); };
         auto co_of = [&](int i) { return wn * 64 + ((i + wp) & 3) * 16 + fq * 4; };
 
-        S28_STAMP(t0);
         // ---- accumulators start as their pixel's border-class bias (+ the residual: second conv of a block, this tile of x).
         // Here, not in the epilogue: 100 b128 LDS reads per wave are 6 k cycles of LDS time per pass, free while the halo is in flight.
         if (hf == 0) {       // the conv's parameters were issued BEFORE the halo pieces still in flight (kernel start: 16; else waves 4..7: 2)
@@ -234,7 +219,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // halo planes, W(0..2), parameters
         __builtin_amdgcn_s_barrier();
-        S28_STAMP(t1);
         // second half of a conv: the weights again; else on to the next conv
         wwrap = (unsigned)(conv + 1) * (S28_STEPS * S28_SLOT);
         wback = hf == 0 ? (unsigned)conv * (S28_STEPS * S28_SLOT) : wwrap;
@@ -246,7 +230,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) bt[j] = rd_b(0, j);
         bx = rd_b(0, 6);
-        S28_STAMP(t2);
 
         // one K step: 25 MFMAs on fragments read during the previous step; the next step's fragment reads between them
         auto step = [&](int4v (&ac)[4], int4v (&an)[4], int k, int dyn, int dxn, int pln, auto pf_tag) {
@@ -312,7 +295,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
 #pragma unroll 1
         for (int it = 1; it < 3; ++it) row(it, 1, std::false_type{});
 
-        S28_STAMP(t3);
         // ---- end of the pass.  Plane 1's buffer is dead once every wave is past its last fragment read.
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -346,8 +328,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
             }
         if (fre < 8)
             *reinterpret_cast<int2v*>(dst + (size_t)(tile0 + 384 + fre) * S28_C + coe(0)) = act(accx, 0);
-        S28_STAMP(t4);
-        if (STAMPS) { s_wait += t1 - t0; s_pro += t2 - t1; s_k += t3 - t2; s_epi += t4 - t3; }
         if (hf == 1) {
             // the conv is complete once every wave's stores are: then the next conv's input halo (what this workgroup just wrote)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -359,21 +339,11 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
                     issue_halo(nxr, 1, 7, 0, lt, true);
                 }
             }
-            if (STAMPS) { unsigned long long t5; S28_STAMP(t5); s_drain += t5 - t4; }
         }
     }
     };
     if ((wp >> 1) == 0) run(std::integral_constant<int, 0>{}); else run(std::integral_constant<int, 1>{});
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (STAMPS) {
-        unsigned long long tZ;
-        S28_STAMP(tZ);
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rB)::"memory");
-        if (p.stamps && (tid & 63) == 0) {
-            unsigned long long* o = p.stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-            o[0] = s_wait; o[1] = s_pro; o[2] = s_k; o[3] = s_epi; o[4] = s_drain; o[5] = tZ - tA; o[6] = rB - rA; o[7] = tA;
-        }
-    }
 #endif
 }
 
@@ -408,22 +378,12 @@ extern "C" int fr_conv_stage28_f16(void* x, void* mid, const void* wstream, cons
     p.B = B; p.nconv = 2 * nblocks;
     p.xbytes = (unsigned)((int64_t)B * S28_IMG);
     p.wbytes = (unsigned)((int64_t)p.nconv * S28_STEPS * S28_SLOT);
-    p.stamps = (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS");    // always NULL in the product build
-    if constexpr (FR_DEBUG) {                                       // stamped twin: debug build only
-        if (p.stamps) {
-            static FrDevLatch dl;
-            if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage28_kernel<1>), S28_LDS, dl)) { fr_set_error("fr_conv_stage28_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-            conv_stage28_kernel<1><<<B, 512, S28_LDS, fr_stream(stream)>>>(p);
-            FR_CHECK_LAUNCH("conv_stage28_kernel<stamps>");
-            return FR_OK;
-        }
-    }
     static FrDevLatch latch;
-    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage28_kernel<0>), S28_LDS, latch)) {
+    if (!fr_raise_lds(reinterpret_cast<const void*>(conv_stage28_kernel), S28_LDS, latch)) {
         fr_set_error("fr_conv_stage28_f16: cannot raise dynamic LDS to %d bytes", S28_LDS);
         return FR_E_LAUNCH;
     }
-    conv_stage28_kernel<0><<<B, 512, S28_LDS, fr_stream(stream)>>>(p);
+    conv_stage28_kernel<<<B, 512, S28_LDS, fr_stream(stream)>>>(p);
     FR_CHECK_LAUNCH("conv_stage28_kernel");
     return FR_OK;
 }

@@ -24,20 +24,10 @@ struct DcArgs {
     int Ho, Wo;           // conv output extent (H-KH+1, W-KW+1)
     int regions_x, regions_y;
     const uint8_t* frames; int FH, FW;   // SRC == 1: u8 BGR frames [B,FH,FW,3], resized on the fly
-    unsigned long long* stamps;          // diagnostic (FR_DBG_STAMPS): per-wave phase cycle sums, else NULL
     const int32_t* counts; int cap;      // optional: image b is a real crop iff b % cap < counts[b / cap] (R-/O-Net slots)
     unsigned char* y_split;              // optional (layer 0): second copy of the output as split f16, 64 B per pixel =
                                          // [hi ch0-7 | hi ch8-15 | lo ch0-7 | lo ch8-15] (x = hi + lo; channels 12-15 zero): pnet_fused.hip
 };
-
-#define DSTAMP(var)                                                                               \
-    do {                                                                                          \
-        if (FR_DEBUG && a.stamps) {                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");            \
-            __builtin_amdgcn_sched_barrier(0);                                                    \
-        }                                                                                         \
-    } while (0)
 
 // POOL: 0 none | 1 fused 2x2/s2 ceil max pool in registers (needs RW % 16 == 0) | 2 fused PKxPK/s2 ceil max
 // pool through an LDS conv-output tile (regions step by RSY x RSX conv pixels, RH x RW computed per region).
@@ -92,8 +82,6 @@ template <int CIN, int COUT, int KH, int KW, int RH, int RW, int G, int NTB, int
 __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
     using C = DcCfg<CIN, COUT, KH, KW, RH, RW, G, NTB, WN, TG, POOL, PK, RSY, RSX, NHEAD, RPB, SRC, NW>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    unsigned long long dk = 0;
-    DSTAMP(dk);
     float* xin = lds;
     float* wl = lds + C::W_OFF;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -295,18 +283,14 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
     }
     if (item0 < nitems) store_tile();
 
-    unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, q01 = 0, q12 = 0, q23 = 0, q34 = 0;
     for (int rr = 0; rr < RPB; ++rr) {
         const int item = item0 + rr;
         if (item >= nitems) break;
-        DSTAMP(d0);
-        if (FR_DEBUG && a.stamps && rr == 0) q01 += d0 - dk;          // block prologue (first tile load, weights) counted once
         const int zz = item / per_img, rem = item - zz * per_img;
         const int ry = rem / a.regions_x, rx = rem - ry * a.regions_x;
         const int y0 = ry * RSY, x0 = rx * RSX, img0 = zz * G;
         const bool more = rr + 1 < RPB && item + 1 < nitems;
         if (more) load_tile(item + 1);                   // global loads fly under this item's MFMAs
-        DSTAMP(d1);
 
         float4v acc[C::NT][C::PT];
 #pragma unroll
@@ -357,7 +341,6 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
             }
         }
 
-        DSTAMP(d2);
         // ---- epilogue: bias + PReLU
 #pragma unroll
         for (int i = 0; i < C::NT; ++i) {
@@ -531,17 +514,10 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
                 }
             }
         }
-        DSTAMP(d3);
         if (more) {
             __syncthreads();                             // every wave is done with this item's tiles
             store_tile();
         }
-        DSTAMP(d4);
-        if (FR_DEBUG && a.stamps) { q01 += d1 - d0; q12 += d2 - d1; q23 += d3 - d2; q34 += d4 - d3; }
-    }
-    if (FR_DEBUG && a.stamps && lane == 0) {
-        unsigned long long* o = a.stamps + ((size_t)(blockIdx.x % 4096) * NW + wave) * 4;
-        o[0] = q01; o[1] = q12; o[2] = q23; o[3] = q34;
     }
 }
 
@@ -589,9 +565,7 @@ extern "C" int fr_dconv_mfma_f32(int layer, const float* x, const float* w, cons
     FR_REQUIRE(!counts || (cap > 0 && B % cap == 0 && layer >= 10), "fr_dconv_mfma_f32: counts need cap | B and an R-/O-Net layer");
     FR_REQUIRE(w && bias && y && B > 0 && H > 0 && W > 0, "fr_dconv_mfma_f32: bad argument");
     FR_REQUIRE((layer == 0 || layer == 3) ? (frames && FH > 0 && FW > 0) : (x != nullptr), "fr_dconv_mfma_f32: no input");
-    DcArgs a{x, w, bias, slope, y, head_w, head_b, B, H, W, 0, 0, 0, 0, frames, FH, FW,
-             (unsigned long long*)fr_dbg_ptr("FR_DBG_STAMPS"),           // NULL in the product build
-             counts, cap, (unsigned char*)y_split};
+    DcArgs a{x, w, bias, slope, y, head_w, head_b, B, H, W, 0, 0, 0, 0, frames, FH, FW, counts, cap, (unsigned char*)y_split};
     hipStream_t s = fr_stream(stream);
     int rc = FR_OK;
     switch (layer) {
@@ -600,12 +574,10 @@ extern "C" int fr_dconv_mfma_f32(int layer, const float* x, const float* w, cons
                  rc = fr_pnet_conv1_launch(frames, B, FH, FW, H, W, w, bias, slope, y, y_split, s);      // pnet_conv1.hip
                  break;
         case 3:  FR_REQUIRE(H >= 3 && W >= 3 && frames, "P1 needs frames and a level of at least 3x3");
-                 { const int v = fr_dbg_int("FR_P1_RPB", 8);
-                 const bool big = (int64_t)((H - 2 + 15) / 16) * ((W - 2 + 31) / 32) * B >= 8192;
-                 if (big && v == 2) rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 2, 1>(a, s);
-                 else if (big && v == 4) rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 4, 1>(a, s);
-                 else if (big && v == 8) rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 8, 1>(a, s);
-                 else rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 1, 1>(a, s); }
+                 if ((int64_t)((H - 2 + 15) / 16) * ((W - 2 + 31) / 32) * B < 8192)
+                     rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 1, 1>(a, s);
+                 else
+                     rc = launch_dc<3, 12, 3, 3, 16, 32, 1, 1, 1, 9, 1, 2, 16, 32, 0, 8, 1>(a, s);
                  break;                                                                                   // P-Net conv1 (+resize, PReLU, pool)
         case 1:  FR_REQUIRE(H >= 3 && W >= 3, "P2 input too small");
                  // small pyramid levels have too few tiles to fill 256 CUs: multi-tile blocks only add latency there
@@ -615,13 +587,10 @@ extern "C" int fr_dconv_mfma_f32(int layer, const float* x, const float* w, cons
                      rc = launch_dc<12, 16, 3, 3, 8, 32, 1, 1, 1, 9, 0, 2, 8, 32, 0, 8, 0>(a, s);
                  break;                                                                                   // P-Net conv2
         case 2:  FR_REQUIRE(H >= 3 && W >= 3 && head_w && head_b, "P3 needs head weights");
-                 { const int v = fr_dbg_int("FR_P3_RPB", 8);
-                 if (v == 1 || (int64_t)((H - 2 + 7) / 8) * ((W - 2 + 31) / 32) * B < 8192)
+                 if ((int64_t)((H - 2 + 7) / 8) * ((W - 2 + 31) / 32) * B < 8192)
                      rc = launch_dc<16, 32, 3, 3, 8, 32, 1, 2, 1, 9, 0, 2, 8, 32, 6, 1, 0>(a, s);
-                 else if (v == 2)
-                     rc = launch_dc<16, 32, 3, 3, 8, 32, 1, 2, 1, 9, 0, 2, 8, 32, 6, 2, 0>(a, s);
                  else
-                     rc = launch_dc<16, 32, 3, 3, 8, 32, 1, 2, 1, 9, 0, 2, 8, 32, 6, 8, 0>(a, s); }
+                     rc = launch_dc<16, 32, 3, 3, 8, 32, 1, 2, 1, 9, 0, 2, 8, 32, 6, 8, 0>(a, s);
                  break;                                                                                   // P-Net conv3+heads
         case 10: FR_REQUIRE(H == 24 && W == 24, "R1 expects 24x24");                        // conv1 + 3x3/s2 pool -> 11x11
                  rc = launch_dc<4, 28, 3, 3, 22, 22, 1, 2, 1, 9, 2, 3, 22, 22, 0, 4, 0>(a, s); break;

@@ -62,15 +62,11 @@ __device__ __forceinline__ float bilerp(float p00, float p01, float p10, float p
 
 typedef int int2v __attribute__((ext_vector_type(2)));
 constexpr int P1_TW = 64, P1_IW = P1_TW + 2;
-#ifndef P1_OCC
-#define P1_OCC 3
-#endif
-#ifndef P1_CTU
-#define P1_CTU 4
-#endif
-#ifndef P1_ABL
-#define P1_ABL 0
-#endif
+// F16 form, measured on levels 0 / 1 of a 64 x 1080p batch (profiles/r04_pnet_conv1_f16_ablation.txt): four waves per SIMD
+// (<= 128 VGPRs) spills 43 - 54 VGPRs and runs 1.3 - 1.5x slower than three; the cout-tile loop not unrolled runs 533 / 276 us
+// against 577 / 266 us unrolled - no clear gain, so the loop stays unrolled.
+constexpr int P1_OCC = 3;
+constexpr int P1_CTU = 4;
 
 __device__ __forceinline__ float dpp_xor1(float v) {        // value of lane ^ 1 (quad_perm [1,0,3,2])
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
@@ -205,11 +201,8 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
                 c0 = min(o0, lim); c1 = min(o1, lim);
                 fl |= ((o0 - c0) << 11) | ((o1 - c1) << 19);              // (bytes * 8) << 8 and << 16
             }
-            if (P1_ABL & 1) { rq0[u] = c0; rq1[u] = c1; (void)fbase; }
-            else {
             rq0[u] = *reinterpret_cast<const u64_unaligned*>(fbase + c0);
             rq1[u] = *reinterpret_cast<const u64_unaligned*>(fbase + c1);
-            }
             rfl[u] = valid ? fl : -1;
             special = special || !valid || !(fl & 1);
         }
@@ -227,13 +220,6 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
         for (int u = 0; u < NPF; ++u) {
             const int e = tid + u * 256;
             float v[3];
-            if ((P1_ABL & 16) && F16) {                                                                        // (ablation: no conversion / blend)
-                unsigned char* xz = reinterpret_cast<unsigned char*>(xin);
-                half4 hh; hh[0] = hh[1] = hh[2] = hh[3] = (half_t)__int_as_float((int)(rq0[u] ^ rq1[u]) & 0x3fffffff);
-                *reinterpret_cast<half4*>(xz + e * 8) = hh;
-                *reinterpret_cast<half4*>(xz + (XPX + e) * 8) = hh;
-                continue;
-            }
             const unsigned long long q0 = E ? rq0[u] >> ((rfl[u] >> 8) & 0xff) : rq0[u];
             const unsigned long long q1 = E ? rq1[u] >> ((rfl[u] >> 16) & 0xff) : rq1[u];
             const unsigned l0 = (unsigned)q0, h0 = (unsigned)(q0 >> 32), l1 = (unsigned)q1, h1 = (unsigned)(q1 >> 32);
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
                 const float sv = bilerp(a00[c], two ? a01[c] : a00[c], a10[c], two ? a11[c] : a10[c], wx[u], wy[u]);
                 // (sv - 127.5) * 2^-7 as ONE fma: scaling by a power of two commutes with the rounding of the difference (no
                 // subnormals here: |sv - 127.5| >= 2^-17 or 0), so the bits are those of the two-operation form
-                v[c] = (!E || rfl[u] >= 0) && !(P1_ABL & 4) ? __builtin_fmaf(sv, 0.0078125f, -0.99609375f) : 0.f;
+                v[c] = (!E || rfl[u] >= 0) ? __builtin_fmaf(sv, 0.0078125f, -0.99609375f) : 0.f;
             }
             if constexpr (F16) {
                 half4 hi, lo;
@@ -317,14 +303,9 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
             const int64_t fbase = (int64_t)n * a.Hp;
             auto conv16 = [&](int row, int ct) __attribute__((always_inline)) {          // 16 pixels x 16 couts: raw sums
                 const unsigned char* pb = xz + ((row + (kq >> 1)) * P1_IW + ct * 16 + li + 2 * (kq & 1)) * 8;
-                half8 h0, l0, h1, l1;
-                if (P1_ABL & 8) { h0 = l0 = h1 = l1 = wfh[0]; asm volatile("" :: "v"(pb)); }                 // (ablation: no fragment reads)
-                else {
-                h0 = *reinterpret_cast<const half8_a8*>(pb); l0 = *reinterpret_cast<const half8_a8*>(pb + XPX * 8);
-                h1 = *reinterpret_cast<const half8_a8*>(pb + 2 * P1_IW * 8); l1 = *reinterpret_cast<const half8_a8*>(pb + (XPX + 2 * P1_IW) * 8);
-                }
+                const half8 h0 = *reinterpret_cast<const half8_a8*>(pb), l0 = *reinterpret_cast<const half8_a8*>(pb + XPX * 8);
+                const half8 h1 = *reinterpret_cast<const half8_a8*>(pb + 2 * P1_IW * 8), l1 = *reinterpret_cast<const half8_a8*>(pb + (XPX + 2 * P1_IW) * 8);
                 float4v q = {0.f, 0.f, 0.f, 0.f};
-                if (P1_ABL & 2) { asm volatile("" :: "v"(h0), "v"(l0), "v"(h1), "v"(l1)); return q; }      // (ablation: no MFMAs)
                 q = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfl[0], h0, q, 0, 0, 0);
                 q = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfh[0], l0, q, 0, 0, 0);
                 q = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfl[1], h1, q, 0, 0, 0);
@@ -335,7 +316,6 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
             };
             auto put16 = [&](const float4v& m, int py, int px) __attribute__((always_inline)) {   // a pooled pixel's four couts
                 const int64_t pix = (fbase + py) * a.Wp + px;
-                if (P1_ABL & 32) { asm volatile("" :: "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(pix)); return; }   // (ablation: no split / stores)
                 half4 hi, lo;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -444,8 +424,6 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
                         static_for<3>([&](auto G) {
                             constexpr int g = decltype(G)::value;
                             constexpr int c = (kh * 9 + q) * 3 + g;          // 3k + g, k = (kh*3 + kw)*3 + channel = kh*9 + q
-                            if (P1_ABL & 2) { if (g == 0) asm volatile("" :: "v"(xv[q])); }
-                            else
                             acc[r][g] = __builtin_amdgcn_mfma_f32_4x4x1f32(wreg[c / 16], xv[q], acc[r][g], 4, c % 16, 0);
                         });
                     }

@@ -18,12 +18,11 @@
 #include "common.h"
 #include <type_traits>
 
-#ifndef RC1_PB_R           // developer A/B (tools/abl_rc1.py): pooled rows per band / slots per block of the batch path's F16 form
-#define RC1_PB_R 3         // measured (64 x 512 random boxes, us): PB x RPB 4x8 495, 3x8 417, 2x8 434, 4x16 429, 3x16 397, 3x32 see tools/abl_rc1.py
-#define RC1_RPB_R 16
-#define RC1_PB_O 2         // O-Net (64 x 64 boxes): 2x4 281, 2x8 279, 1x4 317, 3x4 446, 2x2 288
-#define RC1_RPB_O 4
-#endif
+// Pooled rows per band / slots per block of the batch path's F16 form, measured in us (profiles/r04_crop_conv1_shapes.txt):
+constexpr int RC1_PB_R = 3;        // R-Net (64 x 512 random boxes): PB x RPB 4x8 495, 3x8 417, 2x8 434, 4x16 429, 3x16 397, 3x32 414
+constexpr int RC1_RPB_R = 16;
+constexpr int RC1_PB_O = 2;        // O-Net (64 x 64 boxes): 2x4 281, 2x8 279, 1x4 317, 3x4 446, 2x2 288
+constexpr int RC1_RPB_O = 4;
 
 namespace {
 

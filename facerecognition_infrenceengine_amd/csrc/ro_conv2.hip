@@ -16,12 +16,12 @@
 // score and regression (the same distance from the oracle as a different f32 summation order).
 //
 // Geometry.  GEMM view D[cout][pixel] = sum_{tap, ch} W[cout][tap][ch] X[pixel + tap][ch]; A = weights (a wave owns ONE
-// 16-cout tile and keeps its nine taps' hi and lo fragments in registers: 72 VGPRs), B = pixels (LDS).  One workgroup per CU,
-// wave = (cout tile, pixel-tile group), persistent over consecutive items, the NEXT item's image arriving by LDS-DMA in a
-// second buffer under the current item's K loop:
-//   R-Net: item = three crops (3 x 9 x 9 = 243 conv pixels = 16 MFMA pixel tiles), 3 cout tiles x 4 pixel groups = 12 waves;
+// 16-cout tile and keeps its nine taps' hi and lo fragments in registers: 72 VGPRs), B = pixels (LDS).  Wave = (cout tile,
+// pixel-tile group); workgroups are persistent over consecutive items:
+//   R-Net: item = three crops (3 x 9 x 9 = 243 conv pixels = 16 MFMA pixel tiles), 3 cout tiles x 4 pixel groups = 12 waves,
+//          one workgroup per CU, the NEXT item's image arriving by LDS-DMA in a second buffer under the current item's K loop;
 //   O-Net: item = one band of a crop (11 conv rows x 21 = 231 pixels = 15 tiles; two bands per crop share conv row 10),
-//          4 cout tiles x 2 pixel groups = 8 waves.
+//          4 cout tiles = 4 waves, two workgroups per CU, one buffer each (an item's image is fetched behind the previous pool).
 // (First version: 3 / 4 waves per workgroup, two workgroups per CU, one buffer: the two workgroups ran in lockstep - load, K
 // loop and pool ADDED up, 148 + 167 + 83 us for the R-Net batch by compile-time ablation - and hipcc sank every fragment
 // read to its first use behind an lgkmcnt(0).)
@@ -38,15 +38,6 @@
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-#ifndef RC2_CFG
-#define RC2_CFG 0          // developer A/B of the workgroup shapes
-#endif
-#ifndef RC2_STAGGER
-#define RC2_STAGGER 0      // start delay of the second workgroup of a CU, in units of 1 024 cycles (measured 0 / 3 / 6: no difference)
-#endif
-#ifndef RC2_ABL
-#define RC2_ABL 0          // developer ablations (tools/abl_rc2.py builds its own objects): 1 no MFMAs, 2 no fragment reads, 4 no input DMA, 8 no pool
-#endif
 
 namespace {
 
@@ -66,16 +57,7 @@ struct Rc2Args {
     const int32_t* counts; int cap;        // slot s holds a crop iff s % cap < counts[s / cap]
     int nslots, per_block;                 // items per block (consecutive)
     int32_t* zero;                         // optional: a device word block 0 clears (the exact pass's list counter, used next)
-    unsigned long long* stamps;            // developer builds (RC2_ABL & 16): per-wave phase cycle sums, else unused
 };
-#define RC2_STAMP(var)                                                                   \
-    do {                                                                                 \
-        if (RC2_ABL & 16) {                                                              \
-            __builtin_amdgcn_sched_barrier(0);                                           \
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");  \
-            __builtin_amdgcn_sched_barrier(0);                                           \
-        }                                                                                \
-    } while (0)
 
 // NPH: pixel-tile groups per cout tile (waves = NCT * NPH: wave = (cout tile, pixel group)); PROUNDS: the conv map goes through
 // the LDS pool tile in PROUNDS rounds of NCT / PROUNDS cout tiles (the tile aliases ONE input buffer)
@@ -197,7 +179,7 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
     };
     auto piece = [&](__amdgpu_buffer_rsrc_t rs, int buf, int i) {
         const int j = wave + C::NW * i;
-        if (j < C::NPIECE && !(RC2_ABL & 4))
+        if (j < C::NPIECE)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(lds2 + buf * C::BUF + j * 1024), 16, voff[i], 0, 0, 0);
     };
     // ---- per-tile LDS addresses (buffer 0) of this lane's output pixel; lanes / tiles past the item's pixels: the last pixel
@@ -211,17 +193,6 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
         rt[k] = lbase + ((g * HB + y) * C::P + x) * 64;
     }
 
-    // Workgroups that share a CU start together and, left alone, stay in lockstep: they load together, share the matrix pipe
-    // together (each at half speed) and pool together - the phases ADD up (measured).  The workgroup whose waves sit in the
-    // odd wave slots of their SIMDs (the second to arrive on the CU) starts half an item late; from then on one computes
-    // while the other loads / pools.
-    if (RC2_STAGGER) {
-        const unsigned hwid = __builtin_amdgcn_s_getreg((4 /*HW_REG_HW_ID*/) | (0 << 6) | ((4 - 1) << 11));     // wave slot in its SIMD
-        if (__builtin_amdgcn_readfirstlane(hwid) & 1) {
-#pragma unroll 1
-            for (int i = 0; i < RC2_STAGGER; ++i) __builtin_amdgcn_s_sleep(16);      // 16 x 64 cycles each
-        }
-    }
     // pool: bias / slope of every cout in LDS (a thread reads its quad's there: no global latency behind the barrier)
     float* prm = reinterpret_cast<float*>(lds2 + C::PRM_OFF);
     for (int c = tid; c < C::COUT; c += C::NTHR) { prm[c] = a.bias[c]; prm[C::COUT + c] = a.slope[c]; }
@@ -230,10 +201,8 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
 #pragma unroll
         for (int i = 0; i < C::NPW; ++i) piece(rs0, 0, i);
     }
-    unsigned long long st[6] = {0, 0, 0, 0, 0, 0}, ph_sum[6] = {0, 0, 0, 0, 0, 0};
     int nxt = next_valid(cur + 1);
     for (int b = 0; cur >= 0; b ^= (NBUFS - 1)) {
-        RC2_STAMP(st[0]);
         const int sg = cur / NBAND, band = cur - sg * NBAND;
         const int s0 = sg * G;
         // which of the item's slots hold a crop (scalar; the pool stores only those)
@@ -254,12 +223,10 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's pieces of the item have landed ...
         __syncthreads();                                    // ... everybody's have, and the other buffer's pool tile has been read
-        RC2_STAMP(st[1]);
         // the next item's image arrives under this item's K loop: its LDS-DMA pieces are issued from INSIDE the MFMA stream, a
         // piece every DMA_EVERY steps (all of a wave's pieces in front of the loop held it for ~1 000 cycles: stamps)
         const __amdgpu_buffer_rsrc_t rsn = item_rsrc(nxt >= 0 ? nxt : cur);
         const int nn = nxt >= 0 ? next_valid(nxt + 1) : -1;  // (scalar loads: their latency hides under the K loop)
-        RC2_STAMP(st[2]);
 
         // ---- K loop: 9 taps x NTW pixel tiles.  The fragment reads run DEPTH (tap, tile) steps ahead of the MFMAs that use them,
         // by hand: ds_read_b128 as inline asm, released by counted lgkmcnt waits that carry the fragments as operands (hipcc
@@ -276,12 +243,13 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
             constexpr int s = decltype(S)::value;
             constexpr int tap = s / C::NTW, k = s - tap * C::NTW, kh = tap / 3, kw = tap - kh * 3;
             constexpr int imm = (kh * C::P + kw) * 64;
-            if (RC2_ABL & 2) { fh[s % (C::DEPTH + 1)] = wh[tap]; fl[s % (C::DEPTH + 1)] = wl[tap]; return; }
             // (the address add sits inside the asm: left to hipcc, the 9 x NTW sums are hoisted in front of the loop and spill)
             unsigned ad;
             const unsigned r0 = rt[k], x0 = xd[(kw + C::KC * kh) & 7];
+            half8& h = fh[s % (C::DEPTH + 1)];
+            half8& l = fl[s % (C::DEPTH + 1)];
             asm volatile("v_add_u32 %2, %3, %4\n\tds_read_b128 %0, %2 offset:%5\n\tds_read_b128 %1, %2 offset:%6"
-                         : "=&v"(fh[s % (C::DEPTH + 1)]), "=&v"(fl[s % (C::DEPTH + 1)]), "=&v"(ad)
+                         : "=&v"(h), "=&v"(l), "=&v"(ad)
                          : "v"(r0), "v"(x0), "n"(imm), "n"(imm + C::PLANE));
         };
         static_for<C::DEPTH>([&](auto S) { rd(S); });
@@ -295,24 +263,12 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
             constexpr int later = (C::NSTEP - 1 - s) < C::DEPTH ? (C::NSTEP - 1 - s) : C::DEPTH;      // reads issued behind this step's
             half8& bh = fh[s % (C::DEPTH + 1)];
             half8& bl = fl[s % (C::DEPTH + 1)];
-            if (!(RC2_ABL & 2)) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(bh), "+v"(bl) : "n"(2 * later));
-            if (RC2_ABL & 1) { asm volatile("" :: "v"(bh), "v"(bl)); }
-            else {
-                acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[tap], bh, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[tap], bh, acc[k], 0, 0, 0);
-                acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[tap], bl, acc[k], 0, 0, 0);
-            }
+            asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(bh), "+v"(bl) : "n"(2 * later));
+            acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[tap], bh, acc[k], 0, 0, 0);
+            acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[tap], bh, acc[k], 0, 0, 0);
+            acc[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[tap], bl, acc[k], 0, 0, 0);
         });
 
-        RC2_STAMP(st[3]);
-        if (RC2_ABL & 8) {
-            float4v sum = acc[0];
-#pragma unroll
-            for (int k = 1; k < C::NTW; ++k) sum += acc[k];
-            if (sum[0] + sum[1] + sum[2] + sum[3] == 12345.678f) a.y[tid] = sum[0];
-            cur = nxt; nxt = nn;
-            continue;
-        }
         // ---- conv map -> LDS tile [pixel][CS] (over this item's input buffer) in PROUNDS rounds of cout tiles, each followed
         // by the 3x3 / s2 pool of its couts
         float* pt = reinterpret_cast<float*>(lds2 + b * C::BUF);
@@ -335,7 +291,6 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
                 }
             }
             __syncthreads();
-            if (round == 0) RC2_STAMP(st[4]);
             constexpr int Q4 = C::Q4;
             for (int e = tid; e < G * PR * PO * Q4; e += C::NTHR) {
                 const int qd = e % Q4, pp = e / Q4;
@@ -364,18 +319,7 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
                 *reinterpret_cast<float4v*>(a.y + (((size_t)slot * PO + band * PR + pr) * PO + pc) * C::COUT + co) = m;
             }
         }
-        RC2_STAMP(st[5]);
-        if (RC2_ABL & 16) {
-#pragma unroll
-            for (int i = 0; i < 5; ++i) ph_sum[i] += st[i + 1] - st[i];
-            ph_sum[5] += 1;
-        }
         cur = nxt; nxt = nn;
-    }
-    if ((RC2_ABL & 16) && a.stamps && lane == 0) {
-        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * C::NW + wave) * 8;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) o[i] = ph_sum[i];
     }
 #endif
 }
@@ -428,21 +372,16 @@ extern "C" int fr_ro_conv2_split(int net, const void* x_split, const float* w, c
                                  int nslots, const int32_t* counts, int cap, int32_t* zero_word, fr_stream_t stream) {
     FR_REQUIRE(x_split && w && bias && slope && y && counts, "fr_ro_conv2_split: null pointer");
     FR_REQUIRE(nslots > 0 && cap > 0 && nslots % cap == 0, "fr_ro_conv2_split: nslots must be frames x cap");
-    Rc2Args a{(const unsigned char*)x_split, w, bias, slope, y, counts, cap, nslots, 1, zero_word,
-              (RC2_ABL & 16) ? reinterpret_cast<unsigned long long*>(zero_word) : nullptr};
-    if (RC2_ABL & 16) a.zero = nullptr;      // developer build: the pointer argument carries the stamp buffer
+    Rc2Args a{(const unsigned char*)x_split, w, bias, slope, y, counts, cap, nslots, 1, zero_word};
     hipStream_t s = fr_stream(stream);
     int rc;
-    //                       WIN HB WOUT HC G NCT NPH NBAND BROWS PR PO PROUNDS MINW
-    const int cfg = RC2_CFG;
     //                                    WIN HB WOUT HC G NCT NPH NBAND BROWS PR PO PROUNDS NBUFS DEPTH MINW
-    // Measured (64 x 1080p worth of slots, tools/abl_rc2.py; us): R-Net 6 waves x 2 workgroups per CU 340 - 380, 12 waves x 1: 277 - 302
+    // Measured (64 x 1080p worth of slots; us): R-Net 6 waves x 2 workgroups per CU 340 - 380, 12 waves x 1: 277 - 302
     // (first version, 3 waves x 2, one buffer, compiler-scheduled reads: 391); O-Net 4 waves x 2 (one buffer) 212 - 215, 8 waves x 1
-    // (two buffers) 232 - 283 (first version 237)
-    if (net == 0 && cfg == 1) rc = launch_rc2<11, 11, 9, 9, 2, 3, 2, 1, 0, 4, 4, 1, 2, 2, 3>(a, s);        // two crops, 3 cout tiles x 2 pixel groups = 6 waves, two workgroups per CU
-    else if (net == 0) rc = launch_rc2<11, 11, 9, 9, 3, 3, 4, 1, 0, 4, 4, 1, 2, 2, 3>(a, s);                 // three crops, 3 x 4 = 12 waves, one per CU
-    else if (net == 1 && cfg == 0) rc = launch_rc2<23, 13, 21, 11, 1, 4, 1, 2, 10, 5, 10, 1, 1, 3, 2>(a, s);   // one band, 4 waves (cout tiles), one buffer, two workgroups per CU
-    else if (net == 1) rc = launch_rc2<23, 13, 21, 11, 1, 4, 2, 2, 10, 5, 10, 1, 2, 3, 2>(a, s);            // one band, 4 x 2 = 8 waves, two buffers, one per CU
+    // (two buffers) 232 - 283 (first version 237).  A start delay of the second workgroup of a CU (0 / 3 / 6 x 1 024 cycles) made
+    // no difference.
+    if (net == 0) rc = launch_rc2<11, 11, 9, 9, 3, 3, 4, 1, 0, 4, 4, 1, 2, 2, 3>(a, s);             // three crops, 3 x 4 = 12 waves, one per CU
+    else if (net == 1) rc = launch_rc2<23, 13, 21, 11, 1, 4, 1, 2, 10, 5, 10, 1, 1, 3, 2>(a, s);   // one band, 4 waves (cout tiles), one buffer, two workgroups per CU
     else { FR_REQUIRE(false, "fr_ro_conv2_split: net must be 0 (R-Net) or 1 (O-Net)"); }
     if (rc != FR_OK) return rc;
     FR_CHECK_LAUNCH("ro_conv2_split_kernel");

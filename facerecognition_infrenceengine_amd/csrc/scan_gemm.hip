@@ -63,7 +63,6 @@ struct ScanP {
     float* ws_score; int* ws_idx;                       // [F][nranges*4][K]
     const int32_t* seg_counts; int seg_len;
     float qscale;                                       // fp8: queries are multiplied by this before conversion
-    int abl;                                            // debug build only (FR_SCAN_ABL): 1 no epilogue, 2 one DMA only, 4 no MFMA
 };
 
 __device__ __forceinline__ int4v sg_pack_f16(const float* q) {
@@ -182,7 +181,7 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
     for (int t = 0; t < ntiles; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of tile t have landed
         __builtin_amdgcn_s_barrier();                               // everyone's have; buffer (t+1)&1 is free again
-        if (t + 1 < ntiles && !(FR_DEBUG && (p.abl & 2))) issue_tile(t + 1);
+        if (t + 1 < ntiles) issue_tile(t + 1);
         const char* buf = lds + (t & 1) * TILE_B;
         float4v acc[4][2];
 #pragma unroll
@@ -197,11 +196,6 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
                 const char* rowp = buf + (kc * SG_ROWS + m * 16) * 128;
                 alo[m] = *reinterpret_cast<const int4v*>(rowp + a_lo);
                 ahi[m] = *reinterpret_cast<const int4v*>(rowp + a_hi);
-            }
-            if (FR_DEBUG && (p.abl & 4)) {
-#pragma unroll
-                for (int m = 0; m < 4; ++m) { acc[m][0][0] += __int_as_float(alo[m][0]); acc[m][1][0] += __int_as_float(ahi[m][0]); }
-                continue;
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -221,13 +215,6 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
                 }
         }
         // acc[m][n] = coarse scores of the 4-row group (t*64 + m*16 + 4*fq)/4 for query q0w + n*16 + fr; groups ascend in m
-        if (FR_DEBUG && (p.abl & 1)) {
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) top[n].s[0] = fmaxf(top[n].s[0], acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3]);
-            continue;
-        }
         const int rbase = t * SG_ROWS + 4 * fq;
         if (t == ntiles - 1) {                                       // rows past the range end read as zeros: not candidates
 #pragma unroll
@@ -402,7 +389,6 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
         ScanP p;
         p.Q = Q; p.G = Gc; p.F = F; p.N = N; p.nqt = pl.nqt; p.nranges = pl.nranges; p.rows_per_range = pl.rows_per_range;
         p.ws_score = ws_score; p.ws_idx = ws_idx; p.seg_counts = seg_counts; p.seg_len = seg_len; p.qscale = qscale;
-        p.abl = fr_dbg_int("FR_SCAN_ABL", 0);
         constexpr int lds = 2 * SG_ROWS * (FP8 ? 512 : 1024);
         static FrDevLatch latch;
         if (!fr_raise_lds(reinterpret_cast<const void*>(gallery_gemm_scan<FP8, TK>), lds, latch)) {

@@ -12,9 +12,7 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *     launches are asynchronous, nothing synchronises;
  *   - no global mutable state and no environment variables: the only process-wide state is an atomic
- *     per-device bit per kernel remembering that its dynamic-LDS limit has been raised there (idempotent);
- *     diagnostic switches and in-kernel cycle stamps exist only in the separate debug build
- *     (`make debug` -> libfrhip_debug.so), never in libfrhip.so.
+ *     per-device bit per kernel remembering that its dynamic-LDS limit has been raised there (idempotent).
  * Each declaration cites the reference behaviour it replaces.
  */
 #ifndef FRHIP_H
