@@ -8,7 +8,6 @@
 __constant__ double ARC_DST[5][2] = {{38.2946, 51.6963}, {73.5318, 51.5014}, {56.0252, 71.7366},
                                      {41.5493, 92.3655}, {70.7299, 92.2041}};
 
-typedef unsigned long long u64_unaligned_w __attribute__((aligned(1)));
 #define WARP_NB 7
 __global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict__ frames, int nframes, int H, int W,
                                                        const float* __restrict__ kps,
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict
                 if (pair && row_in) {
                     const long long off = (yy * W + x0) * 3;
                     const long long c8 = off < lim ? off : lim;
-                    const unsigned long long q = *reinterpret_cast<const u64_unaligned_w*>(fr + c8) >> ((off - c8) * 8);
+                    const unsigned long long q = *reinterpret_cast<const u64_unaligned*>(fr + c8) >> ((off - c8) * 8);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         pb[a][0][c] = (double)(unsigned)((q >> (8 * c)) & 0xff);

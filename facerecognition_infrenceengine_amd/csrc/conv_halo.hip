@@ -28,19 +28,6 @@ struct HaloP {
     unsigned xbytes, wbytes;
 };
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int8v __attribute__((ext_vector_type(8)));
-
-// 4 floats -> 4 fp8 e4m3 (OCP) bytes, saturating at +-448 (the conversion itself would produce NaN past the range)
-__device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
-    a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-    c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return v;
-}
-
 #define HK 64          // channels per chunk
 
 // scheduling pattern for one half step: 4+PT ds_read_b128 (+ ~3 address VALU each) spread over 4*PT MFMAs
@@ -107,8 +94,8 @@ __global__ __launch_bounds__(512, 4) void conv_halo_kernel(HaloP p) {
     const int nhalo = p.G * IH;
     const int IPX = p.TH * p.W;                        // output pixels of one image's part
 
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
 
     // LDS image: row = halo pixel, 16-B chunk' = chunk ^ key(row).  Weights: key = row & 7.  Halo: key =
     // (row - 2*hy) & 7 = the pixel's index in a W-pitch raster: 16 consecutive output pixels (any tap) then

@@ -40,8 +40,8 @@ __global__ __launch_bounds__(IB_WAVES * 64) void conv_inblock_kernel(InblockP p)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fq = lane >> 4;
     const int m0 = blockIdx.x * IB_TM, n0 = blockIdx.y * IB_TN;
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
 
     // the epilogue threads fetch their residual first: it is the longest-latency operand of the tail
     const int epx = tid % IB_TM, ecq = tid / IB_TM;                // tid < 8 IB_TM: pixel epx, couts 4 ecq .. + 3 of the tile

@@ -74,8 +74,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, float4v (&acc)[4][
     }
 }
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 // Tiles are staged with buffer_load ... lds (16 B per lane straight into LDS, no VGPR round trip and
 // no ds_write): one wave-instruction fills 8 rows x 128 B; the XOR swizzle moves to the SOURCE chunk.
 template <int WN, bool SMALL_CIN>
@@ -99,8 +97,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
     auto wrow = [&](int i) { return (wave * WROWS + i) * 8 + trow; };
     auto xrow = [&](int i) { return (wave * XROWS + i) * 8 + trow; };
 
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
 
     // ---- per-thread gather state for its XROWS pixels
     int xbase[XROWS];   // byte offset of (n, ho*s-pad, wo*s-pad, chunk*8)
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(ConvP p) {
 #pragma unroll
     for (int i = 0; i < WROWS; ++i) wbase[i] = ((unsigned)(cout0 + wrow(i)) * p.K + tchunk * 8) * 2;
     // second input (1x1 tap at the output pixel's stride position): same pixel raster, its own channel count
-    __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.x2 ? p.x2 : p.x), 0, p.x2 ? p.x2bytes : 0u, 0x00020000);
+    __amdgpu_buffer_rsrc_t x2rs = buffer_rsrc(p.x2 ? p.x2 : p.x, p.x2 ? p.x2bytes : 0u);
     auto x2off = [&](int i, int c0) -> unsigned {
         if (xhw[i] == (int)0x80000000u) return 0x80000000u;
         const int bh = (xhw[i] >> 16) + p.pad, bw = (int)(short)(xhw[i] & 0xffff) + p.pad;      // = ho * stride, wo * stride

@@ -30,9 +30,6 @@
 #include "common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int2v __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int S14_PX = 196, S14_C = 256, S14_ROWS = 200;            // rows per plane (196 pixels + zero rows)
@@ -52,10 +49,6 @@ struct StageP {
     unsigned xbytes, wbytes;
 };
 
-__device__ __forceinline__ float4v mfma16(const int4v& a, const int4v& b, float4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
@@ -71,8 +64,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     const int n = blockIdx.x;                                        // the image
     const size_t img_elems = (size_t)S14_PX * S14_C;
 
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
 
     // ---- weight stream: W(s) = 16 KB at s * 16 KB; this wave moves pieces 2 * wave and 2 * wave + 1 (1 KB each).
     // Unconditional: past the end of the stream the buffer resource returns zeros (into a slot nobody reads).
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     issue_w(1);
     issue_w(2);
     // a conv's parameters (10 KB) -> LDS, by LDS-DMA too: pieces 0..7 by the 8 waves, 8..9 by waves 0 and 1
-    __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)p.prm, 0, (unsigned)p.nconv * S14_PRM, 0x00020000);
+    __amdgpu_buffer_rsrc_t prs = buffer_rsrc(p.prm, (unsigned)p.nconv * S14_PRM);
     auto issue_prm = [&](int conv, int ln) {
         char* dst = lds + S14_IMG + 3 * S14_SLOT;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (lds_ptr_t)(dst + wave * 1024), 16, (unsigned)(wave * 1024 + ln * 16), conv * S14_PRM, 0, 0);
@@ -149,7 +142,6 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // image, W(0), W(1)
     __builtin_amdgcn_s_barrier();
 
-#define S14_PIN() __builtin_amdgcn_sched_barrier(0)
     // One K step (local index k of a 24-step group: slot k % 3, channel group g = k & 7) on the fragments (ac, axc, b,
     // bx); meanwhile the NEXT step's fragments are read: weights into (an, axn) from slot (k + 1) % 3, pixel tile j
     // into b[j] right behind the MFMAs that used it.  Before a step with g == 7 reads its successor's pixels, boff
@@ -169,10 +161,10 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
         // the partner has the matrix pipe to itself; the partner issues its pieces behind its 18th MFMA (about when the
         // first wave's pieces are out), while the first wave has the pipe (stamps: DMA in the middle of both streams
         // 1 470 cycles per step, first / last 1 180, first / 18th: see DESIGN.md).
-        if constexpr (WP == 0) { issue_w(k % 3); S14_PIN(); }
+        if constexpr (WP == 0) { issue_w(k % 3); FR_PIN(); }
         // the shared 13th pixel tile: this wave's cout tiles 2 WP, 2 WP + 1 of its own four - the same weight fragments
         accx[0] = mfma16(ac[2 * WP], bx, accx[0]); accx[1] = mfma16(ac[2 * WP + 1], bx, accx[1]);
-        S14_PIN();
+        FR_PIN();
 #pragma unroll
         for (int j = 0; j < 6; ++j) {
 #pragma unroll
@@ -195,8 +187,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
                 if (g == 7) set_tap_one(5, dyn, dxn);
                 b[5] = rd_b(ng, 5);
             }
-            S14_PIN();
-            if constexpr (WP == 1) { if (j == 3) { issue_w(k % 3); S14_PIN(); } }
+            FR_PIN();
+            if constexpr (WP == 1) { if (j == 3) { issue_w(k % 3); FR_PIN(); } }
         }
     };
 
@@ -228,7 +220,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
                 // slot (k + 1) % 3 may be read, slot k % 3 may be overwritten
                 asm volatile("s_waitcnt vmcnt(2) lgkmcnt(1)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-                S14_PIN();
+                FR_PIN();
                 const int tt = k >> 3;                               // next tap: (it, tt + 1), or (it + 1, 0) after the row's last
                 const int dyn = tt < 2 ? it - 1 : it, dxn = tt < 2 ? tt : -1;
                 if ((k & 1) == 0) step(a0, a1, k, dyn, dxn);
@@ -289,7 +281,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_kernel(StageP p) {
                 const half4 h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
                 if (t < 24) *dst = h;
                 else if (192 + fre < S14_PX) *dst = h;
-                if ((t & 3) == 3) S14_PIN();
+                if ((t & 3) == 3) FR_PIN();
             }
         };
         if (second) tiles(std::false_type{}); else tiles(std::true_type{});

@@ -24,10 +24,6 @@
 #include "common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef int int8v __attribute__((ext_vector_type(8)));
-
 namespace {
 
 constexpr int F14_PX = 196, F14_C = 256, F14_ROWS = 200;
@@ -50,15 +46,6 @@ struct StageF8P {
     unsigned xbytes8, xbytes16, wbytes;
 };
 
-__device__ __forceinline__ int pack_fp8x4_sat(float a, float b, float c, float d) {
-    a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-    c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return v;
-}
-
 // an MFMA operand: 8 consecutive VGPRs, built from its two 16-B halves at load time (one 256-bit value from the start:
 // joining the halves at the MFMA instead made hipcc copy them into fresh 8-register tuples and spill 500 VGPRs)
 typedef int8v Frag;
@@ -69,8 +56,6 @@ __device__ __forceinline__ float4v mfma8(const Frag& a, const Frag& b, float4v c
 }
 
 }  // namespace
-
-#define F14_PIN() __builtin_amdgcn_sched_barrier(0)
 
 __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -84,9 +69,9 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
     const int fr = lane & 15, fq = lane >> 4;
     const int n = blockIdx.x;
 
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x8, 0, p.xbytes8, 0x00020000);
-    __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)p.prm, 0, (unsigned)p.nconv * F14_PRM, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x8, p.xbytes8);
+    __amdgpu_buffer_rsrc_t prs = buffer_rsrc(p.prm, (unsigned)p.nconv * F14_PRM);
 
     // ---- weight stream: W(s) = 32 KB at s * 32 KB; this wave moves pieces 4 * wave .. 4 * wave + 3 (1 KB each)
     const unsigned wlane = (unsigned)(wave * 4096 + lane * 16);
@@ -158,9 +143,9 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
     // One K step (local index k of a 6-step group: slot k % 3, plane g = k & 1); see conv_stage14.hip for the protocol.
     auto step = [&](Frag (&ac)[4], Frag (&an)[4], int k, int dyn, int dxn) {
         const int g = k & 1, ng = (k + 1) & 1, nslot = (k + 1) % 3;
-        if constexpr (WP == 0) { issue_w(k % 3); F14_PIN(); }
+        if constexpr (WP == 0) { issue_w(k % 3); FR_PIN(); }
         accx[0] = mfma8(ac[2 * WP], bx, accx[0]); accx[1] = mfma8(ac[2 * WP + 1], bx, accx[1]);
-        F14_PIN();
+        FR_PIN();
 #pragma unroll
         for (int t = 0; t < 6; ++t) {
 #pragma unroll
@@ -178,8 +163,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
                 bt[t % 3] = rd_b(ng, t - 3);
             }
             if (t == 5) { if (g == 1) set_tap_one(6, dyn, dxn); bx = rd_b(ng, 6); }
-            F14_PIN();
-            if constexpr (WP == 1) { if (t == 3) { issue_w(k % 3); F14_PIN(); } }
+            FR_PIN();
+            if constexpr (WP == 1) { if (t == 3) { issue_w(k % 3); FR_PIN(); } }
         }
         if (g == 1) { set_tap_one(3, dyn, dxn); set_tap_one(4, dyn, dxn); set_tap_one(5, dyn, dxn); }      // read inside the next step
     };
@@ -195,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
             // second conv of a block: accumulators start as residual / oscale (the epilogue's dequantising multiply restores
             // the residual).  The block's input: x16 for the first block, else what this workgroup wrote to y16 one block
             // ago - L1-bypassing loads (sc1): a CU's vector L1 is never refreshed by stores.
-            __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void*)(conv == 1 ? p.x16 : (const half_t*)p.y16), 0, p.xbytes16, 0x00020000);
+            __amdgpu_buffer_rsrc_t rrs = buffer_rsrc(conv == 1 ? p.x16 : (const half_t*)p.y16, p.xbytes16);
             const unsigned rb = (unsigned)n * (unsigned)(F14_PX * F14_C * 2);
             // 16 B per lane = 8 consecutive couts: lanes fq = 0, 2 / 1, 3 fetch couts 0..7 / 8..15 of cout tiles (2 ip, 2 ip + 1) and
             // v_permlane16_swap puts them back into the accumulator layout (a vector-memory instruction costs the same whatever
@@ -248,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
                 // (all but the 6 youngest LDS reads: pixel fragments)
                 asm volatile("s_waitcnt vmcnt(4) lgkmcnt(6)" ::: "memory");          // the last weight read is followed by bx and tiles 2..5: >= 6 pixel reads
                 __builtin_amdgcn_s_barrier();
-                F14_PIN();
+                FR_PIN();
                 const int tt = k >> 1;
                 const int dyn = tt < 2 ? it - 1 : it, dxn = tt < 2 ? tt : -1;
                 if ((k & 1) == 0) step(a0, a1, k, dyn, dxn);
@@ -311,8 +296,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
                         }
                         const half4 h = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
                         hp[u] = __builtin_bit_cast(int2v, h);
-                        const int code = pack_fp8x4_sat(((float)h[0] - mu2[u][0]) * inv_sx, ((float)h[1] - mu2[u][1]) * inv_sx,
-                                                        ((float)h[2] - mu2[u][2]) * inv_sx, ((float)h[3] - mu2[u][3]) * inv_sx);
+                        const int code = pack_fp8x4(((float)h[0] - mu2[u][0]) * inv_sx, ((float)h[1] - mu2[u][1]) * inv_sx,
+                                                    ((float)h[2] - mu2[u][2]) * inv_sx, ((float)h[3] - mu2[u][3]) * inv_sx);
                         if (live) *reinterpret_cast<int*>(img + rowoff[j] + ((ch ^ key[j]) << 4)) = code;
                     }
                     if constexpr (!FIRST) {                          // the residual stream / the result
@@ -320,7 +305,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage14_f8_kernel(StageF8P p) {
                         const auto s1 = __builtin_amdgcn_permlane16_swap((unsigned)hp[0][1], (unsigned)hp[1][1], false, false);
                         if (live) *reinterpret_cast<int4v*>(ybase + gpix[j] + co8e + (ip < 2 ? ip * 32 : WP * 32)) = int4v{(int)s0[0], (int)s1[0], (int)s0[1], (int)s1[1]};
                     }
-                    F14_PIN();
+                    FR_PIN();
                 }
             }
         };

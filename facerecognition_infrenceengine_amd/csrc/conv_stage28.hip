@@ -32,9 +32,6 @@
 #include "common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int2v __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int S28_W = 28, S28_TH = 14, S28_C = 128;
@@ -54,13 +51,7 @@ struct Stage28P {
     unsigned xbytes, wbytes;
 };
 
-__device__ __forceinline__ float4v mm16(const int4v& a, const int4v& b, float4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-}
-
 }  // namespace
-
-#define S28_PIN() __builtin_amdgcn_sched_barrier(0)
 
 __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -72,10 +63,10 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
     const int wn = wave & 1, wp = wave >> 1;                          // SIMD partners: waves w and w + 4 = (wn, wp) and (wn, wp + 2)
     const int n = blockIdx.x;
 
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t mrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.mid, 0, p.xbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)p.prm, 0, (unsigned)p.nconv * S28_PRM, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
+    __amdgpu_buffer_rsrc_t mrs = buffer_rsrc(p.mid, p.xbytes);
+    __amdgpu_buffer_rsrc_t prs = buffer_rsrc(p.prm, (unsigned)p.nconv * S28_PRM);
 
     // ---- weight stream: conv c's 36 slots at c * 36 * 8 KB, read once per half; this wave moves piece `wave` (1 KB) of a slot
     unsigned wsrc = 0, wwrap = S28_STEPS * S28_SLOT, wback = 0;       // at wsrc == wwrap continue at wback (second half: the conv again)
@@ -247,13 +238,13 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
                 }
                 issue_w(k % 3, lane);
             };
-            if constexpr (ROLE == 0) { dma(); S28_PIN(); }
-            accx = mm16(ac[0], bx, accx);
-            S28_PIN();
+            if constexpr (ROLE == 0) { dma(); FR_PIN(); }
+            accx = mfma16(ac[0], bx, accx);
+            FR_PIN();
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) acc[j][i] = mm16(ac[i], bt[j % 3], acc[j][i]);
+                for (int i = 0; i < 4; ++i) acc[j][i] = mfma16(ac[i], bt[j % 3], acc[j][i]);
                 // pixel fragments live in a ring of three: tile j's register takes tile j + 3 (this step's, then the next step's)
                 if (j == 0) { an[0] = rd_a(nslot, 0); an[1] = rd_a(nslot, 1); }
                 if (j == 1) { an[2] = rd_a(nslot, 2); an[3] = rd_a(nslot, 3); }
@@ -267,8 +258,8 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
                         bx = rd_b(ngg, 6);
                     }
                 }
-                S28_PIN();
-                if constexpr (ROLE == 1) { if (j == 3) { dma(); S28_PIN(); } }
+                FR_PIN();
+                if constexpr (ROLE == 1) { if (j == 3) { dma(); FR_PIN(); } }
             }
         };
         // six steps = one kernel row (3 taps x 2 channel groups) of one plane; 6 % 3 == 0: ring slots are compile-time
@@ -280,7 +271,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
                 if (PF && k >= 1 && k <= 4) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(1)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(1) lgkmcnt(1)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
-                S28_PIN();
+                FR_PIN();
                 const int tt = k >> 1;
                 const bool last = tt == 2 && it == 2;                // behind the plane's last tap: the next plane's first
                 const int dyn = last ? -1 : (tt < 2 ? it - 1 : it), dxn = tt < 2 ? tt : -1;
@@ -302,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void conv_stage28_kernel(Stage28P p) {
         asm volatile("" : "+v"(le));
         const unsigned lt = halo_lane(le);
         for (int i = 0; i < 8; ++i) issue_halo(nxr, 1, i, nxy0, lt, nx_ok(i));
-        S28_PIN();
+        FR_PIN();
         const int fre = le & 15, fqe = le >> 4;
         auto coe = [&](int i) { return wn * 64 + ((i + wp) & 3) * 16 + fqe * 4; };
         float4v sv[4];                                               // read unconditionally: a conditional definition is carried through

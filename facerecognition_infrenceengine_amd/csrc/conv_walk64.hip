@@ -23,9 +23,6 @@
 #include "common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int2v __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int K64_RW = 28, K64_RH = 14, K64_C = 64;                  // region width / height, input channels
@@ -44,13 +41,7 @@ struct Walk64P {
     unsigned xbytes, ybytes, wbytes;
 };
 
-__device__ __forceinline__ float4v mmk(const int4v& a, const int4v& b, float4v c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
-}
-
 }  // namespace
-
-#define K64_PIN() __builtin_amdgcn_sched_barrier(0)
 
 __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -64,8 +55,8 @@ __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
     const int HW = p.HW, nbx = HW / K64_RW;
     const int reg0 = part * (nbx * (HW / K64_RH) / p.nsplit), nreg = reg0 + nbx * (HW / K64_RH) / p.nsplit;       // this workgroup's regions: [reg0, nreg)
 
-    __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.wbytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.xbytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t wrs = buffer_rsrc(p.w, p.wbytes);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(p.x, p.xbytes);
 
     // ---- weight stream of this cout group: 9 slots (taps) of 8 KB, streamed once per region; this wave moves piece `wave`
     const unsigned wbase = (unsigned)cg * (9 * K64_SLOT);
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
         }
         accx = *reinterpret_cast<const float4v*>(lprm + cls_off(fr < 8 ? 384 + fr : 0) + (wave & 3) * 16 + fq * 4);
         if (p.res) {
-            __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc((void*)p.res, 0, p.ybytes, 0x00020000);
+            __amdgpu_buffer_rsrc_t rrs = buffer_rsrc(p.res, p.ybytes);
             int4v r[3][2];
 #pragma unroll
             for (int t = 0; t < 3; ++t)
@@ -218,15 +209,15 @@ __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
                 if (s < 8) issue_halo(cur ^ 1, s, reg + 1, lane);    // the next region's halo into the other buffer
                 issue_w(s % 3, lane);                                // last: the next step but one waits for it with two pieces behind it
             };
-            if constexpr (ROLE == 0) { dma(); K64_PIN(); }
+            if constexpr (ROLE == 0) { dma(); FR_PIN(); }
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
-                accx = mmk(ac[kh][0], bx[kh], accx);
-                K64_PIN();
+                accx = mfma16(ac[kh][0], bx[kh], accx);
+                FR_PIN();
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[t][i] = mmk(ac[kh][i], b[t][kh], acc[t][i]);
+                    for (int i = 0; i < 4; ++i) acc[t][i] = mfma16(ac[kh][i], b[t][kh], acc[t][i]);
                     // weights of the next step: two fragments behind each of the first four tile groups
                     if (kh == 0) { an[0][t] = rd_a(nslot, 0, t); if (t == 2) an[0][3] = rd_a(nslot, 0, 3); }
                     else { an[1][t] = rd_a(nslot, 1, t); if (t == 2) an[1][3] = rd_a(nslot, 1, 3); }
@@ -236,9 +227,9 @@ __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
                         if (kh == 0) set_tap_one(3, dyn, dxn);
                         bx[kh] = rd_b(kh, 3);
                     }
-                    K64_PIN();
+                    FR_PIN();
                 }
-                if constexpr (ROLE == 1) { if (kh == 0) { dma(); K64_PIN(); } }
+                if constexpr (ROLE == 1) { if (kh == 0) { dma(); FR_PIN(); } }
             }
         };
 #pragma unroll
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(512, 2) void conv_walk64_kernel(Walk64P p) {
             // W(s+1) was the LAST DMA of step s-2; behind it step s-1's two (a halo piece of the next region, its weight piece)
             asm volatile("s_waitcnt vmcnt(2) lgkmcnt(1)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            K64_PIN();
+            FR_PIN();
             if ((s & 1) == 0) step(a0, a1, s); else step(a1, a0, s);
         }
 

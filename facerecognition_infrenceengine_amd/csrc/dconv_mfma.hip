@@ -15,7 +15,7 @@
 // channels padded to a multiple of 4 with zeros.  Weights are staged per group of TG taps.
 // Optional fused epilogues: PReLU, 2x2/s2 ceil-mode max pool (P-Net conv1), 1x1 head (P-Net
 // conv3 -> 2 logits + 4 regressions).
-#include "common.h"
+#include "detect_math.h"
 
 struct DcArgs {
     const float* x; const float* w; const float* bias; const float* slope; float* y;
@@ -58,24 +58,6 @@ struct DcCfg {
     static_assert(CIN % 4 == 0 || SRC == 1, "f32 inputs are read as float4: pad channels to a multiple of 4");
     static_assert(SRC == 0 || CIN == 3, "fused resize feeds a 3-channel layer");
 };
-
-typedef unsigned long long u64_unaligned __attribute__((aligned(1)));
-struct DLerp { int i0, i1; float w; };
-__device__ __forceinline__ DLerp dlerp_coord(int d, float ratio, int n) {      // == detect_ops.hip lerp_coord
-    float f = ((float)d + 0.5f) * ratio - 0.5f;
-    float fl = floorf(f);
-    DLerp r;
-    r.w = f - fl;
-    int i = (int)fl;
-    r.i0 = min(max(i, 0), n - 1);
-    r.i1 = min(max(i + 1, 0), n - 1);
-    return r;
-}
-__device__ __forceinline__ float dbilerp(float p00, float p01, float p10, float p11, float wx, float wy) {
-    float top = (1.0f - wx) * p00 + wx * p01;
-    float bot = (1.0f - wx) * p10 + wx * p11;
-    return (1.0f - wy) * top + wy * bot;
-}
 
 template <int CIN, int COUT, int KH, int KW, int RH, int RW, int G, int NTB, int WN, int TG, int POOL, int PK,
           int RSY, int RSX, int NHEAD, int RPB, int SRC, int NW = 4>
@@ -185,7 +167,7 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
             if constexpr (SRC == 1) {
                 rsh[u] = -1; rq0[u] = rq1[u] = 0; rwx[u] = rwy[u] = 0.f; rpb[u] = 0;
                 if (l >= 0 && n < a.B && yy < a.H && xx < a.W) {
-                    const DLerp ly = dlerp_coord(yy, ryr, a.FH), lx = dlerp_coord(xx, rxr, a.FW);
+                    const Lerp ly = lerp_coord(yy, ryr, a.FH), lx = lerp_coord(xx, rxr, a.FW);
                     // both corners of a row are 6 adjacent bytes (BGR BGR): ONE unaligned 8-byte load per source row.
                     // 32-bit offsets inside the (block-uniform) frame; in the LAST frame the load is pulled back so
                     // that it never runs past the end of the buffer.  x1 == x0 (clamped right border) re-uses the
@@ -228,7 +210,7 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
                         const float a11[3] = {(float)((h1 >> 8) & 0xff), (float)(h1 & 0xff), (float)(l1 >> 24)};
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
-                            const float sv = dbilerp(a00[c], two ? a01[c] : a00[c], a10[c], two ? a11[c] : a10[c], rwx[u], rwy[u]);
+                            const float sv = bilerp(a00[c], two ? a01[c] : a00[c], a10[c], two ? a11[c] : a10[c], rwx[u], rwy[u]);
                             v[c] = (sv - 127.5f) * 0.0078125f;
                         }
                     }
@@ -395,9 +377,7 @@ __global__ __launch_bounds__(NW * 64) void dconv_mfma(DcArgs a) {
                                         half4 hi, lo;
 #pragma unroll
                                         for (int e = 0; e < 4; ++e) {
-                                            const float x = ch0 + e < COUT ? v[e] : 0.f;
-                                            const half_t h = (half_t)x;
-                                            hi[e] = h; lo[e] = (half_t)(x - (float)h);
+                                            split_f16(ch0 + e < COUT ? v[e] : 0.f, hi, lo, e);
                                         }
                                         unsigned char* o2 = a.y_split + (((int64_t)n * Hp + py) * Wp + px) * 64 + (ch0 >> 3) * 16 + ((ch0 >> 2) & 1) * 8;
                                         *reinterpret_cast<half4*>(o2) = hi;

@@ -3,27 +3,7 @@
 // not MFMA-shaped), max pool, candidate generation, box refinement, crop+resize, stage select.
 // Arithmetic order mirrors oracle/detect.py op for op (built with -ffp-contract=off; fused
 // multiply-adds are written explicitly where the spec allows them).
-#include "common.h"
-
-// ------------------------------------------------------------------ resize helpers
-struct Lerp { int i0, i1; float w; };
-
-__device__ __forceinline__ Lerp lerp_coord(int d, float ratio, int n) {
-    float f = ((float)d + 0.5f) * ratio - 0.5f;
-    float fl = floorf(f);
-    Lerp r;
-    r.w = f - fl;
-    int i = (int)fl;
-    r.i0 = min(max(i, 0), n - 1);
-    r.i1 = min(max(i + 1, 0), n - 1);
-    return r;
-}
-
-__device__ __forceinline__ float bilerp(float p00, float p01, float p10, float p11, float wx, float wy) {
-    float top = (1.0f - wx) * p00 + wx * p01;
-    float bot = (1.0f - wx) * p10 + wx * p11;
-    return (1.0f - wy) * top + wy * bot;
-}
+#include "detect_math.h"
 
 // frames u8 [N,H,W,3] BGR -> out f32 [N,hs,ws,3] RGB, (v - 127.5) * 0.0078125
 __global__ void pyramid_resize_norm(const uint8_t* __restrict__ frames, int N, int H, int W, int hs, int ws,
@@ -429,7 +409,6 @@ extern "C" int fr_box_refine(float* boxes, const float* aux, int naux, const int
 // Zero-padded crop of the (1-based inclusive) box trunc(b), bilinear to size x size, RGB normalised,
 // written as 4-channel pixels (RGB0) so that the first R/O-Net conv reads 16-byte pixels.
 // One block per candidate slot; invalid slots (>= count, or empty boxes) are zero-filled.
-typedef unsigned long long u64_unaligned_t __attribute__((aligned(1)));
 __global__ __launch_bounds__(256) void crop_resize_norm(const uint8_t* __restrict__ frames, int H, int W,
                                                         const float* __restrict__ boxes,
                                                         const int32_t* __restrict__ counts, int cap, int size,
@@ -462,7 +441,7 @@ __global__ __launch_bounds__(256) void crop_resize_norm(const uint8_t* __restric
                 if (pair && row_in) {
                     const int off = (ys[a] * W + xs[0]) * 3;
                     const int c = min(off, lim);
-                    const unsigned long long q = *reinterpret_cast<const u64_unaligned_t*>(fr + c) >> ((off - c) * 8);
+                    const unsigned long long q = *reinterpret_cast<const u64_unaligned*>(fr + c) >> ((off - c) * 8);
                     const unsigned lo = (unsigned)q, hi = (unsigned)(q >> 32);
                     p[a][0][0] = (float)((lo >> 16) & 0xff); p[a][0][1] = (float)((lo >> 8) & 0xff); p[a][0][2] = (float)(lo & 0xff);
                     p[a][1][0] = (float)((hi >> 8) & 0xff); p[a][1][1] = (float)(hi & 0xff); p[a][1][2] = (float)(lo >> 24);

@@ -17,11 +17,6 @@
 
 struct BestPair { float s; int64_t i; };
 
-// query slot q belongs to segment q / seg_len and is real iff its position in the segment < seg_counts[segment]
-__device__ __forceinline__ bool slot_valid(const int32_t* seg_counts, int seg_len, int q) {
-    const int seg = q / seg_len;
-    return q - seg * seg_len < seg_counts[seg];
-}
 __device__ __forceinline__ bool group_has_valid(const int32_t* seg_counts, int seg_len, int qa, int qb) {
     // [qa, qb) spans at most a few segments; a segment contributes iff its first slot inside the range is real
     for (int q = qa; q < qb;) {

@@ -18,18 +18,9 @@
 // an input row's 9 values (kw, channel) are read once and feed the up to 3 output rows that use it.
 // Blocks are persistent over RPB tiles; the next tile's SOURCE BYTES are fetched under the current tile's MFMAs and
 // blended afterwards (same scheme and same arithmetic as the form this replaces).
-#include "common.h"
-#include <type_traits>
+#include "detect_math.h"
 
 namespace {
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
 
 struct P1Args {
     const uint8_t* frames; int B, FH, FW;      // u8 BGR frames [B,FH,FW,3]
@@ -42,25 +33,6 @@ struct P1Args {
     const int32_t* list; const int32_t* list_count; int list_cap;     // LIST: the tiles to compute (numbers in the full launch's tile order)
 };
 
-typedef unsigned long long u64_unaligned __attribute__((aligned(1)));
-struct Lerp { int i0, i1; float w; };
-__device__ __forceinline__ Lerp lerp_coord(int d, float ratio, int n) {        // == detect_ops.hip lerp_coord
-    float f = ((float)d + 0.5f) * ratio - 0.5f;
-    float fl = floorf(f);
-    Lerp r;
-    r.w = f - fl;
-    int i = (int)fl;
-    r.i0 = min(max(i, 0), n - 1);
-    r.i1 = min(max(i + 1, 0), n - 1);
-    return r;
-}
-__device__ __forceinline__ float bilerp(float p00, float p01, float p10, float p11, float wx, float wy) {
-    float top = (1.0f - wx) * p00 + wx * p01;
-    float bot = (1.0f - wx) * p10 + wx * p11;
-    return (1.0f - wy) * top + wy * bot;
-}
-
-typedef int int2v __attribute__((ext_vector_type(2)));
 constexpr int P1_TW = 64, P1_IW = P1_TW + 2;
 // F16 form, measured on levels 0 / 1 of a 64 x 1080p batch (profiles/r04_pnet_conv1_f16_ablation.txt): four waves per SIMD
 // (<= 128 VGPRs) spills 43 - 54 VGPRs and runs 1.3 - 1.5x slower than three; the cout-tile loop not unrolled runs 533 / 276 us
@@ -124,8 +96,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
             for (int j = 0; j < 8; ++j) {
                 const int kq_ = lane >> 4, kh = 2 * st + (kq_ >> 1), kw = (kq_ & 1) * 2 + (j >> 2), c = j & 3;
                 const float w = (kh < 3 && kw < 3 && c < 3) ? a.w[((kh * 3 + kw) * 4 + c) * 16 + (lane & 15)] : 0.f;
-                const half_t h = (half_t)w;
-                wfh[st][j] = h; wfl[st][j] = (half_t)(w - (float)h);
+                split_f16(w, wfh[st], wfl[st], j);
             }
     } else {
 #pragma unroll
@@ -239,10 +210,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
             if constexpr (F16) {
                 half4 hi, lo;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const half_t h = (half_t)v[c];
-                    hi[c] = h; lo[c] = (half_t)(v[c] - (float)h);
-                }
+                for (int c = 0; c < 3; ++c) split_f16(v[c], hi, lo, c);
                 hi[3] = lo[3] = (half_t)0.f;
                 unsigned char* xz = reinterpret_cast<unsigned char*>(xin);
                 *reinterpret_cast<half4*>(xz + e * 8) = hi;
@@ -318,10 +286,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
                 const int64_t pix = (fbase + py) * a.Wp + px;
                 half4 hi, lo;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const half_t hh = (half_t)m[e];
-                    hi[e] = hh; lo[e] = (half_t)(m[e] - (float)hh);
-                }
+                for (int e = 0; e < 4; ++e) split_f16(m[e], hi, lo, e);
                 // 16 B per lane: v_permlane16_swap trades the odd kq rows' hi halves with the even rows' lo halves - an even-kq lane then
                 // holds hi of couts 4 kq .. 4 kq + 7, the odd one beside it their lo (partners share the pixel, hence the branch);
                 // the four lanes of a pixel write its whole 64-B entry in ONE instruction (two 8-B stores per lane before)
@@ -444,12 +409,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
                 // channels 10..15 zero
                 half8 hi[2], lo[2];
 #pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const float x = c < 10 ? pv[c >> 2][c & 3] : 0.f;
-                    const half_t h = (half_t)x;
-                    hi[c >> 3][c & 7] = h;
-                    lo[c >> 3][c & 7] = (half_t)(x - (float)h);
-                }
+                for (int c = 0; c < 16; ++c) split_f16(c < 10 ? pv[c >> 2][c & 3] : 0.f, hi[c >> 3], lo[c >> 3], c & 7);
                 unsigned char* o2 = a.y_split + pix * 64;
                 *reinterpret_cast<half8*>(o2) = hi[0];
                 *reinterpret_cast<half8*>(o2 + 16) = hi[1];

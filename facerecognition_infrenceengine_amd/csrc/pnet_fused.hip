@@ -21,9 +21,7 @@
 // a lane owns one pixel and 4 consecutive couts.  In LDS a pixel is 32 B (16 channels f16) in a hi plane and 32 B in a
 // lo plane: conflict-free ds_read_b128 fragments (2-way on 38 % of conv2's reads, where a 16-pixel tile wraps an image
 // row) with LINEAR addresses.  Weights sit in LDS pre-split in fragment order (a lane's 16 B contiguous).
-#include "common.h"
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
+#include "detect_math.h"
 
 #define P23_RH 8
 #define P23_RW 32
@@ -54,15 +52,6 @@ struct P23Args {
     int B, H1, W1, H3, W3, tiles_x, tiles_y, ntiles;
 };
 
-__device__ __forceinline__ void p23_split4(const float4v v, half4& hi, half4& lo) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const half_t h = (half_t)v[e];
-        hi[e] = h;
-        lo[e] = (half_t)(v[e] - (float)h);
-    }
-}
-
 __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -83,11 +72,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
         const float* w = (c3 ? a.w3 : a.w2) + ((size_t)(ct * 16 + r) * 10 + 2 * ks + (q >> 1)) * 16 + 8 * (q & 1);
         half8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float v = w[j];
-            const half_t h = (half_t)v;
-            o[j] = plane ? (half_t)(v - (float)h) : h;
-        }
+        for (int j = 0; j < 8; ++j) o[j] = split_f16_plane(w[j], plane);
         *reinterpret_cast<half8*>(wf + (size_t)e * 16) = o;
     }
     for (int e = tid; e < 16; e += P23_NT) { cst[e] = a.b2[e]; cst[16 + e] = a.s2[e] - 1.f; }      // slopes as s - 1: PReLU = x + (s - 1) min(x, 0), two operations
@@ -114,7 +99,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
     // conv1 map window (12 x 36 pixels) -> LDS by LDS-DMA: per plane 14 pieces of 32 pixels x 32 B (1 KB per wave-
     // instruction), piece j by wave j % 8; a lane moves 16-B chunk (lane & 1) of pixel 32 (j % 14) + (lane >> 1) from
     // the 64-B global row [hi 32 B | lo 32 B]; pixels outside the map (and the 16 padding pixels of piece 13) read zeros.
-    __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.x1s, 0, a.x1s_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(a.x1s, a.x1s_bytes);
     int wy[4], wx[4], wc[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -144,8 +129,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
     for (int j = 0; j < 8; ++j) {
         const int co = j < 4 ? 4 * fq + j : 16 + 4 * fq + (j - 4);
         const float w = fr < 6 ? a.hw[co * 6 + fr] : 0.f;
-        const half_t h = (half_t)w;
-        hwh[j] = h; hwl[j] = (half_t)(w - (float)h);
+        split_f16(w, hwh, hwl, j);
     }
     issue_window(blockIdx.x);
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
@@ -192,7 +176,8 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(fminf(v[e], 0.f), ss[e], v[e]);
                     half4 hi, lo;
-                    p23_split4(v, hi, lo);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) split_f16(v[e], hi, lo, e);
                     char* o = x2t + q * 32 + fq * 8;
                     *reinterpret_cast<half4*>(o) = hi;
                     *reinterpret_cast<half4*>(o + P23_X2PL) = lo;
@@ -244,6 +229,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float x0 = __builtin_fmaf(fminf(v0[e], 0.f), s30[e], v0[e]), x1 = __builtin_fmaf(fminf(v1[e], 0.f), s31[e], v1[e]);
+                    // split by hand: two split_f16 calls here change the schedule of the MFMA loop around them
                     const half_t h0 = (half_t)x0, h1 = (half_t)x1;
                     bh[e] = h0; bl[e] = (half_t)(x0 - (float)h0);
                     bh[4 + e] = h1; bl[4 + e] = (half_t)(x1 - (float)h1);

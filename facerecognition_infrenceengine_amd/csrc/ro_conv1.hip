@@ -15,8 +15,7 @@
 // registers) under the current slot's conv.  When every PReLU slope is >= 0 the raw sums are pooled first and
 // activated after (the same bits, a ninth of the bias / PReLU work); otherwise every pixel is activated before the pool.
 // Count-aware like the other R-/O-Net layers: a slot >= counts[frame] does no work and leaves its output unwritten.
-#include "common.h"
-#include <type_traits>
+#include "detect_math.h"
 
 // Pooled rows per band / slots per block of the batch path's F16 form, measured in us (profiles/r04_crop_conv1_shapes.txt):
 constexpr int RC1_PB_R = 3;        // R-Net (64 x 512 random boxes): PB x RPB 4x8 495, 3x8 417, 2x8 434, 4x16 429, 3x16 397, 3x32 414
@@ -25,14 +24,6 @@ constexpr int RC1_PB_O = 2;        // O-Net (64 x 64 boxes): 2x4 281, 2x8 279, 1
 constexpr int RC1_RPB_O = 4;
 
 namespace {
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
 
 struct RoArgs {
     const uint8_t* frames; int nframes, H, W;
@@ -48,23 +39,6 @@ struct RoArgs {
     const int32_t* list; const int32_t* list_count; int list_cap;
 };
 
-typedef unsigned long long u64_unaligned_r __attribute__((aligned(1)));
-struct LerpR { int i0, i1; float w; };
-__device__ __forceinline__ LerpR lerp_coord_r(int d, float ratio, int n) {        // == detect_ops.hip lerp_coord
-    float f = ((float)d + 0.5f) * ratio - 0.5f;
-    float fl = floorf(f);
-    LerpR r;
-    r.w = f - fl;
-    int i = (int)fl;
-    r.i0 = min(max(i, 0), n - 1);
-    r.i1 = min(max(i + 1, 0), n - 1);
-    return r;
-}
-__device__ __forceinline__ float bilerp_r(float p00, float p01, float p10, float p11, float wx, float wy) {
-    float top = (1.0f - wx) * p00 + wx * p01;
-    float bot = (1.0f - wx) * p10 + wx * p11;
-    return (1.0f - wy) * top + wy * bot;
-}
 __device__ __forceinline__ float vmax_r(float x, float y) {        // no canonicalising self-max (operands are never sNaN)
     float r;
     asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
@@ -137,8 +111,7 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
                 for (int j = 0; j < 8; ++j) {
                     const int kh = 2 * st + (kq_ >> 1), kw = (kq_ & 1) * 2 + (j >> 2), c = j & 3, co = ct * 16 + li_;
                     const float w = (kh < 3 && kw < 3 && c < 3 && co < NG * 4) ? a.w[((kh * 3 + kw) * 3 + c) * (NG * 4) + co] : 0.f;
-                    const half_t h = (half_t)w;
-                    wfh[st][ct][j] = h; wfl[st][ct][j] = (half_t)(w - (float)h);
+                    split_f16(w, wfh[st][ct], wfl[st][ct], j);
                 }
     } else {
 #pragma unroll
@@ -166,10 +139,10 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
             int4v e = {0, 0, 0, 0};                              // e[3] = 1: the box is not empty
             if (tw > 0 && th > 0) {
                 if (tid < S) {
-                    const LerpR l = lerp_coord_r(tid, (float)th / (float)S, th);
+                    const Lerp l = lerp_coord(tid, (float)th / (float)S, th);
                     e = int4v{y1 - 1 + l.i0, y1 - 1 + l.i1, __float_as_int(l.w), 1};
                 } else {
-                    const LerpR l = lerp_coord_r(tid - S, (float)tw / (float)S, tw);
+                    const Lerp l = lerp_coord(tid - S, (float)tw / (float)S, tw);
                     e = int4v{x1 - 1 + l.i0, x1 - 1 + l.i1, __float_as_int(l.w), 1};
                 }
             }
@@ -201,7 +174,7 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
                         if (ys >= 0 && ys < a.H) {
                             const int off = (ys * a.W + basecol) * 3;
                             const int c8 = min(off, lim);
-                            const unsigned long long q = *reinterpret_cast<const u64_unaligned_r*>(fr + c8);
+                            const unsigned long long q = *reinterpret_cast<const u64_unaligned*>(fr + c8);
                             if (r) rq1[u] = q; else rq0[u] = q;
                             fl |= ((off - c8) * 8) << (8 + 8 * r);
                         }
@@ -237,16 +210,13 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
                     const float p00 = E ? (src0 ? f0[ch] : 0.f) : f0[ch], p10 = E ? (src0 ? f1[ch] : 0.f) : f1[ch];
                     const float p01 = E ? (src1 == 2 ? s0[ch] : (src1 == 1 ? f0[ch] : 0.f)) : s0[ch];
                     const float p11 = E ? (src1 == 2 ? s1[ch] : (src1 == 1 ? f1[ch] : 0.f)) : s1[ch];
-                    v[ch] = __builtin_fmaf(bilerp_r(p00, p01, p10, p11, wx, wy), 0.0078125f, -0.99609375f);      // == (s - 127.5) * 2^-7 bit for bit (pnet_conv1.hip)
+                    v[ch] = __builtin_fmaf(bilerp(p00, p01, p10, p11, wx, wy), 0.0078125f, -0.99609375f);      // == (s - 127.5) * 2^-7 bit for bit (pnet_conv1.hip)
                 }
             }
             if constexpr (F16) {
                 half4 hi, lo;
 #pragma unroll
-                for (int ch = 0; ch < 3; ++ch) {
-                    const half_t h = (half_t)v[ch];
-                    hi[ch] = h; lo[ch] = (half_t)(v[ch] - (float)h);
-                }
+                for (int ch = 0; ch < 3; ++ch) split_f16(v[ch], hi, lo, ch);
                 hi[3] = lo[3] = (half_t)0.f;
                 unsigned char* xz = reinterpret_cast<unsigned char*>(xin);
                 *reinterpret_cast<half4*>(xz + t * 8) = hi;
@@ -379,10 +349,7 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
             if constexpr (SPLIT) {
                 half4 hi, lo;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const half_t h = (half_t)m[k];
-                    hi[k] = h; lo[k] = (half_t)(m[k] - (float)h);
-                }
+                for (int k = 0; k < 4; ++k) split_f16(m[k], hi, lo, k);
                 unsigned char* o2 = a.ys + ((int64_t)slot * P * P + (p0 + pyl) * P + px) * 128 + qd * 8;
                 *reinterpret_cast<half4*>(o2) = hi;
                 *reinterpret_cast<half4*>(o2 + 64) = lo;

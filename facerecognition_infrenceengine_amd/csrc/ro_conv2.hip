@@ -34,20 +34,9 @@
 // The conv map goes through an LDS tile (aliasing the item's own input buffer; O-Net: 32 couts at a time) to the pool;
 // pool-before-activation when every PReLU slope is >= 0 (the same bits, a ninth of the bias / PReLU work), as in the other
 // detector kernels.
-#include "common.h"
-#include <type_traits>
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
+#include "detect_math.h"
 
 namespace {
-
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
 
 struct Rc2Args {
     const unsigned char* xs;               // split map [slots][WIN * WIN][128 B] (fr_crop_conv1_split)
@@ -137,10 +126,7 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
             const float4v v1 = *reinterpret_cast<const float4v*>(wrow + tap * 32 + 4);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float v = j < 4 ? v0[j] : v1[j - 4];
-                const half_t h = (half_t)v;
-                wh[tap][j] = h;
-                wl[tap][j] = (half_t)(v - (float)h);
+                split_f16(j < 4 ? v0[j] : v1[j - 4], wh[tap], wl[tap], j);
             }
         }
     }
@@ -175,7 +161,7 @@ __global__ __launch_bounds__(NCT * NPH * 64, MINW) void ro_conv2_split_kernel(Rc
         const unsigned char* base = a.xs + (size_t)s0 * C::SLOT_BYTES + (size_t)band * BROWS * WIN * 128;
         const int nsl = min(G, a.nslots - s0);
         const unsigned bytes = NBAND == 1 ? (unsigned)nsl * C::SLOT_BYTES : (unsigned)(HB * WIN * 128);
-        return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
+        return buffer_rsrc(base, bytes);
     };
     auto piece = [&](__amdgpu_buffer_rsrc_t rs, int buf, int i) {
         const int j = wave + C::NW * i;

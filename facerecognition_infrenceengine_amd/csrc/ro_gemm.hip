@@ -17,7 +17,7 @@
 //   W      pre-split by the host into MFMA fragment order [K step][cout tile][hi | lo][lane][16 B]: a wave's fragments come
 //          straight from global memory (L2-resident: every block reads the same few hundred KB), one step ahead
 // Count-aware like the other R-/O-Net layers: a block whose rows belong to empty slots only exits at once.
-#include "common.h"
+#include "detect_math.h"
 
 namespace {
 
@@ -79,10 +79,7 @@ __global__ __launch_bounds__(256, 2) void ro_gemm_split_kernel(RgArgs a) {
             const int r = xr + 32 * h;
             half4 hi, lo;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const half_t t = (half_t)v[h][e];
-                hi[e] = t; lo[e] = (half_t)(v[h][e] - (float)t);
-            }
+            for (int e = 0; e < 4; ++e) split_f16(v[h][e], hi, lo, e);
             const int off = r * 64 + (((c4 >> 1) ^ ((r >> 1) & 3)) << 4) + (c4 & 1) * 8;
             *reinterpret_cast<half4*>(xs[buf][0] + off) = hi;
             *reinterpret_cast<half4*>(xs[buf][1] + off) = lo;
@@ -185,11 +182,7 @@ __global__ void ro_gemm_pack_kernel(const float* __restrict__ w, unsigned char* 
     const float* src = w + (size_t)(ct * 16 + (lane & 15)) * K + ks * 32 + 8 * (lane >> 4);
     half8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const float v = src[j];
-        const half_t h = (half_t)v;
-        o[j] = plane ? (half_t)(v - (float)h) : h;
-    }
+    for (int j = 0; j < 8; ++j) o[j] = split_f16_plane(src[j], plane);
     *reinterpret_cast<half8*>(out + (size_t)e * 16) = o;
 }
 

@@ -31,15 +31,6 @@
 #define SG_QW 32              // queries per wave (2 MFMA n-tiles)
 #define SG_QB 256             // queries per block (8 waves)
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef int int8v __attribute__((ext_vector_type(8)));
-
-// query slot q belongs to segment q / seg_len and is real iff its position in the segment < seg_counts[segment]
-__device__ __forceinline__ bool sg_slot_valid(const int32_t* seg_counts, int seg_len, int q) {
-    const int seg = q / seg_len;
-    return q - seg * seg_len < seg_counts[seg];
-}
-
 template <int K>
 struct TopK { float s[K]; int i[K]; };
 
@@ -71,24 +62,15 @@ __device__ __forceinline__ int4v sg_pack_f16(const float* q) {
     return __builtin_bit_cast(int4v, h);
 }
 
-// saturating at +-448: past the range the OCP e4m3 conversion produces NaN, and a NaN code fails every '>' of the
-// coarse scan - a non-unit row or query (set_rows(normalise=False), match_device(renormalise=False)) with an element
+// pack_fp8x4 saturates at +-448: past the range the OCP e4m3 conversion produces NaN, and a NaN code fails every '>' of
+// the coarse scan - a non-unit row or query (set_rows(normalise=False), match_device(renormalise=False)) with an element
 // beyond 1.75 (x 256) would silently never reach the exact re-rank
-__device__ __forceinline__ int sg_pack_fp8x4(float a, float b, float c, float d) {
-    a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-    c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, v, true);
-    return v;
-}
-
 __device__ __forceinline__ int4v sg_pack_fp8(const float* q, float sc) {
     int4v o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float4 a = *reinterpret_cast<const float4*>(q + e * 4);
-        o[e] = sg_pack_fp8x4(a.x * sc, a.y * sc, a.z * sc, a.w * sc);
+        o[e] = pack_fp8x4(a.x * sc, a.y * sc, a.z * sc, a.w * sc);
     }
     return o;
 }
@@ -119,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
     bool any = false;                                    // block-uniform: does this query tile hold a real query?
     if (p.seg_counts) {
         for (int q = q0b; q < min(q0b + SG_QB, p.F);) {
-            if (sg_slot_valid(p.seg_counts, p.seg_len, q)) { any = true; break; }
+            if (slot_valid(p.seg_counts, p.seg_len, q)) { any = true; break; }
             q = (q / p.seg_len + 1) * p.seg_len;
         }
         if (!any) return;
@@ -150,8 +132,7 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
     }
 
     // ---- gallery stream: wave w fills pieces w*NPIECE + i of a tile; piece = (kc, 8-row group)
-    __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(reinterpret_cast<const char*>(p.G) + r0 * RB), 0, (unsigned)((int64_t)nrows * RB), 0x00020000);
+    __amdgpu_buffer_rsrc_t grs = buffer_rsrc(reinterpret_cast<const char*>(p.G) + r0 * RB, (unsigned)((int64_t)nrows * RB));
     unsigned voff[NPIECE];
     unsigned ldst[NPIECE];
 #pragma unroll
@@ -259,7 +240,7 @@ __global__ __launch_bounds__(64) void gallery_rerank(const float* __restrict__ Q
                                                      int64_t* __restrict__ out_idx, float* __restrict__ out_score,
                                                      const int32_t* __restrict__ seg_counts, int seg_len) {
     const int q = blockIdx.x, lane = threadIdx.x;
-    if (seg_counts && !sg_slot_valid(seg_counts, seg_len, q)) {
+    if (seg_counts && !slot_valid(seg_counts, seg_len, q)) {
         if (lane == 0) { out_idx[q] = -1; out_score[q] = -1.0f; }
         return;
     }
@@ -430,7 +411,7 @@ __global__ void f32_to_f8_k(const float* __restrict__ x, int* __restrict__ out, 
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     for (; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const float4 v = *reinterpret_cast<const float4*>(x + i * 4);
-        out[i] = sg_pack_fp8x4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
+        out[i] = pack_fp8x4(v.x * sc, v.y * sc, v.z * sc, v.w * sc);
     }
 }
 
