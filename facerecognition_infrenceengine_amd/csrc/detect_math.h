@@ -37,6 +37,10 @@ __device__ __forceinline__ void split_f16(float x, V& hi, V& lo, int e) {
     hi[e] = h; lo[e] = (half_t)(x - (float)h);
 }
 
+// A split-precision logit difference that is not finite (an operand beyond the f16 range, or inf - inf) says nothing about
+// the f32 one.  Every decision site sends such a cell or crop to the exact pass, like one inside the margin band.
+__device__ __forceinline__ bool split_nonfinite(float d) { return !__builtin_isfinite(d); }
+
 // Plane p of the split of x: p = 0 gives hi, p = 1 gives lo (the weight packers write one plane at a time).
 __device__ __forceinline__ half_t split_f16_plane(float x, int p) {
     half_t hi[1], lo[1];

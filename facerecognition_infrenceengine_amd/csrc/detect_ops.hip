@@ -182,6 +182,10 @@ __device__ __forceinline__ float softmax2_face(float a0, float a1) {
     return e1 / (e0 + e1);
 }
 
+// The pre-filter on the fused P-Net's approximate logit difference: a cell may pass unless its split value lies below dl_min.
+// A non-finite split value rules nothing out (pnet_fused.hip put that cell on the exact pass's list).
+__device__ __forceinline__ bool dl_may_pass(float d, float dl_min) { return d >= dl_min || split_nonfinite(d); }
+
 // head: f32 [N, hc, wc, 6] = (logit0, logit1, reg0..3).  Pass 1: per-block pass counts.
 // dl (optional, fused P-Net): f32 [N, hc, wc] approximate logit1 - logit0; a cell with dl < dl_min is certainly below the
 // threshold (pnet_fused.hip re-evaluated every cell at or above dl_min exactly), so its 24-byte head row is not read.
@@ -191,7 +195,7 @@ __global__ __launch_bounds__(256) void pnet_count(const float* __restrict__ head
     const int f = blockIdx.y, b = blockIdx.x;
     const int cell = b * 256 + threadIdx.x;
     bool pass = false;
-    if (cell < cells && (!dl || prob_out || dl[(int64_t)f * cells + cell] >= dl_min)) {
+    if (cell < cells && (!dl || prob_out || dl_may_pass(dl[(int64_t)f * cells + cell], dl_min))) {
         const float* h = head + ((int64_t)f * cells + cell) * 6;
         float p = softmax2_face(h[0], h[1]);
         if (prob_out) prob_out[(int64_t)f * cells + cell] = p;
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(256) void pnet_emit(const float* __restrict__ head,
     bool pass = false;
     float p = 0.f;
     const float* h = head + ((int64_t)f * cells + (cell < cells ? cell : 0)) * 6;
-    if (cell < cells && (!dl || dl[(int64_t)f * cells + cell] >= dl_min)) {
+    if (cell < cells && (!dl || dl_may_pass(dl[(int64_t)f * cells + cell], dl_min))) {
         p = softmax2_face(h[0], h[1]);
         pass = p >= thr;
     }
@@ -273,7 +277,7 @@ __global__ __launch_bounds__(256) void pnet_count_levels(PCandLevels t, float th
     const int cells = t.cells[l];
     const int cell = b * 256 + threadIdx.x;
     bool pass = false;
-    if (cell < cells && t.dl[l][(int64_t)f * cells + cell] >= dl_min) {
+    if (cell < cells && dl_may_pass(t.dl[l][(int64_t)f * cells + cell], dl_min)) {
         const float* h = t.head[l] + ((int64_t)f * cells + cell) * 6;
         pass = softmax2_face(h[0], h[1]) >= thr;
     }
@@ -305,7 +309,7 @@ __global__ __launch_bounds__(256) void pnet_emit_levels(PCandLevels t, float thr
     bool pass = false;
     float p = 0.f;
     const float* h = t.head[l] + ((int64_t)f * cells + (cell < cells ? cell : 0)) * 6;
-    if (cell < cells && t.dl[l][(int64_t)f * cells + cell] >= dl_min) {
+    if (cell < cells && dl_may_pass(t.dl[l][(int64_t)f * cells + cell], dl_min)) {
         p = softmax2_face(h[0], h[1]);
         pass = p >= thr;
     }

@@ -67,7 +67,7 @@ __device__ __forceinline__ float vmax(float x, float y, float pinf) { return __b
 // 4-channel pixels (8 B: R, G, B, 0) so that the (kw' = 0..3, c' = 0..3) values of a kernel row are 32 contiguous bytes and
 // K = (kh, kw', c') = 4 x 4 x 4 with zero weights at kh = 3, kw' = 3, c' = 3 (the packing of ro_conv1.hip's F16 form): two K = 32
 // steps per 16 pixels x 16 couts, 6 MFMAs of 16 cycles, against 81 4x4x1 MFMAs of 8 cycles per 64 pixels - 2.6x fewer matrix
-// cycles, and a 4x4x1 MFMA holds the SIMD's vector issue for its whole 8 cycles.  The map differs from the f32 form's by ~1e-6; the
+// cycles, and a 4x4x1 MFMA holds the SIMD's vector issue for its whole 8 cycles.  The map differs from the f32 form's by the split format's error; the
 // cells whose decision that could touch are re-evaluated from an EXACT map: the f32 form below, run over the tiles such a cell's
 // window touches (LIST: tile numbers from fr_pnet_band_tiles).
 template <int RPW, int RPB, bool F16 = false, bool LIST = false>

@@ -5,12 +5,12 @@
 // Why: the f32 MFMA (v_mfma_f32_16x16x4_f32) runs at 1/16 of the f16 rate and the two layers already sit at 53-59 % of
 // that roof.  Every f32 operand is split x = hi + lo with hi = f16(x), lo = f16(x - hi) (22 mantissa
 // bits between them) and a product is evaluated as hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 with f32
-// accumulation: three MFMAs at 16x the rate; the dropped lo*lo term is 2^-22 relative.  conv2's output tile stays in
+// accumulation: three MFMAs at 16x the rate; the dropped lo*lo term is 2^-22 relative while hi and lo are normal f16 (the measured error by operand scale).  conv2's output tile stays in
 // LDS (no 16-channel f32 map in HBM, the judge's "conv2+conv3 in one kernel").
-// Parity: the result is NOT the f32 fma chain bit for bit (logit error ~1e-5).  The detector thresholds the face
+// Parity: the result is NOT the f32 fma chain bit for bit (logit error 5.4e-6 at the canonical weight scale).  The detector thresholds the face
 // probability and TRUNCATES boxes refined with the regression outputs, so every cell that can be kept must carry exact
 // f32 values: pnet_refine_mfma recomputes, on the f32 matrix instruction with the all-f32 layers' own K-step composition,
-// the heads of every cell whose approximate logit difference is within `margin` (2e-3, ~200x the approximation error) of the
+// the heads of every cell whose approximate logit difference is within `margin` (2e-3, >= 20x the format error inside the envelope of DESIGN.md 4.3a; a non-finite value always) of the
 // threshold or above it - about 1 % of the cells, which this kernel appends to per-block work lists as it goes.  Cells the
 // exact pass does not touch are below the threshold by more than the error bound, i.e. certainly rejected, whatever the
 // rounding.  Kept-box sets and all downstream values therefore equal those of an all-f32 evaluation.
@@ -247,8 +247,9 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
                 const float o0 = d[0] + hb4[0], o1 = d[1] + hb4[1];
                 const float dlv = __shfl(o1 - o0, fr, 64);                  // the pixel's logit difference, on its fq = 1 lane too
                 const bool band = a.band_hi > a.logit_thr;
-                // the exact pass's work list: one LDS atomic per wave and pixel tile that holds a flagged cell
-                const bool flag = inb && fq == 0 && dlv >= a.logit_thr && (!band || dlv <= a.band_hi);
+                // the exact pass's work list: one LDS atomic per wave and pixel tile that holds a flagged cell (a non-finite
+                // split value is flagged whatever the mode: only the f32 arithmetic can decide that cell)
+                const bool flag = inb && fq == 0 && (split_nonfinite(dlv) || (dlv >= a.logit_thr && (!band || dlv <= a.band_hi)));
                 const unsigned long long fm = __ballot(flag);
                 if (fm) {
                     int base = 0;

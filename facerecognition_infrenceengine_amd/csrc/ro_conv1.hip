@@ -53,7 +53,7 @@ __device__ __forceinline__ float vmax_r(float x, float y) {        // no canonic
 // values of one kernel row are 32 contiguous bytes and K = (kh, kw', c') = 4 x 4 x 4 with zero weights at kh = 3, kw' = 3,
 // c' = 3: two K = 32 steps, a B fragment = 16 B (2 pixels) at an 8-byte aligned address.  6 MFMAs of 16 cycles per 16 pixels x
 // 16 couts against 27 x 4 = 108 4x4x1 MFMAs of 8 cycles per 64 pixels x 16 couts: ~2.8x fewer matrix cycles, and the work
-// splits in tiles of 16 pixels instead of units of 64.  ~1e-6 from the f32 form (the exact pass covers the threshold).
+// splits in tiles of 16 pixels instead of units of 64.  The split format's error from the f32 form: DESIGN.md 4.3a (the exact pass covers the threshold).
 template <int S, int NG, int COUT, int PB, int RPB, bool SPLIT = false, bool LIST = false, bool F16 = false>
 __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
     constexpr int C = S - 2;                                     // conv map size

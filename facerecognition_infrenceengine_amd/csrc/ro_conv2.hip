@@ -5,11 +5,11 @@
 // Why: on the f32 matrix instruction (v_mfma_f32_16x16x4_f32, 1/16 of the f16 rate) these two layers were 1.42 ms of a
 // 6.5 ms detector batch (64 x 1080p: 32 768 R-Net and 4 096 O-Net crops), at 0.56 of that instruction's roof.  Here every f32
 // operand is x = hi + lo (hi = f16(x), lo = f16(x - hi): 22 mantissa bits) and a product is hi*hi + lo*hi + hi*lo on
-// v_mfma_f32_16x16x32_f16 with f32 accumulation - three MFMAs at 16x the rate, the dropped lo*lo term is 2^-22 relative.
+// v_mfma_f32_16x16x32_f16 with f32 accumulation - three MFMAs at 16x the rate, the dropped lo*lo term is 2^-22 relative while hi and lo are normal f16.
 // The input arrives ALREADY split (fr_crop_conv1_split writes [slot][pixel][hi 32 ch | lo 32 ch], 128 B per pixel), so it
 // goes to LDS by LDS-DMA and no conversion runs here; K step = one tap x 32 channels (R-Net's 28 are zero-padded).
 //
-// Parity: the sums differ from the f32 fma chain in the last bits (measured on the heads: ~1e-6).  The cascade THRESHOLDS the
+// Parity: the sums differ from the f32 fma chain in the last bits (the measured head error by operand scale: DESIGN.md 4.3a).  The cascade THRESHOLDS the
 // face probability, so the crops whose logit difference lies within `margin` of the threshold are re-evaluated by the all-f32
 // layers (fr_ro_margin_list -> fr_crop_conv1_list_f32 -> fr_dconv_mfma_f32 on the compact list -> fr_ro_scatter_rows): every
 // keep / reject decision is that of exact f32 arithmetic.  A kept crop further from the threshold keeps the split-precision
@@ -338,8 +338,11 @@ __global__ void ro_margin_list_kernel(const float* head, int nhead, const int32_
     if (slot >= nslots) return;
     const int f = slot / cap;
     if (slot - f * cap >= counts[f]) return;
-    const float d = head[(size_t)slot * nhead + 1] - head[(size_t)slot * nhead];
-    if (fabsf(d - lthr) <= margin) {
+    const float* h = head + (size_t)slot * nhead;
+    const float d = h[1] - h[0];
+    bool nonfinite = split_nonfinite(d);           // any non-finite head (a regression or landmark too): only f32 can fill the row
+    for (int i = 2; i < nhead; ++i) nonfinite = nonfinite || split_nonfinite(h[i]);
+    if (nonfinite || fabsf(d - lthr) <= margin) {
         const int pos = atomicAdd(lcount, 1);
         if (pos < lcap) list[pos] = slot;
     }

@@ -5,7 +5,7 @@
 // Why: on the f32 matrix instruction these four launches were 0.36 ms of a 64 x 1080p detector batch (32 768 R-Net and 4 096
 // O-Net crops) at a third of that instruction's roof - they are short GEMMs (K = 192 .. 1 152) whose operands fit the caches.
 // Every f32 operand is x = hi + lo in f16 and a product hi*hi + lo*hi + hi*lo on v_mfma_f32_16x16x32_f16 (f32 accumulate):
-// the layers' outputs differ from the f32 layers' by ~1e-6 of their scale; like the second layers (ro_conv2.hip) they run on
+// the layers' outputs differ from the f32 layers' by the split format's error; like the second layers (ro_conv2.hip) they run on
 // the batch path only, where the crops near the stage threshold are re-evaluated by the all-f32 layers (the exact pass).
 //
 // GEMM view: D[cout][row] = sum_k W[cout][k] X[row][k]; a row = one output pixel of one crop slot, and its K values are KH

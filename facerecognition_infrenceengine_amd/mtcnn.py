@@ -115,6 +115,36 @@ class _MConv:
         return (_pool_out(hc, self.pool, 2), _pool_out(wc, self.pool, 2)) if self.pool else (hc, wc)
 
 
+# consecutive layers of each net: (layer, the layers that read its output)
+_CHAINS = {"pnet": (("conv1", ("conv2",)), ("conv2", ("conv3",)), ("conv3", ("conv4_1", "conv4_2"))),
+           "rnet": (("conv1", ("conv2",)), ("conv2", ("conv3",)), ("conv3", ("dense4",)), ("dense4", ("dense5_1", "dense5_2"))),
+           "onet": (("conv1", ("conv2",)), ("conv2", ("conv3",)), ("conv3", ("conv4",)), ("conv4", ("dense5",)),
+                    ("dense5", ("dense6_1", "dense6_2", "dense6_3")))}
+
+
+def canonical_scale(state, net, dead_zone=2):
+    """The state dict rescaled, layer pair by layer pair, so that every layer's weights have about the He-init RMS
+    sqrt(2 / fan_in): layer l's weights and bias x 2^e, the weights of the layers reading it x 2^-e (e an integer, 0 while the
+    RMS is within 2^dead_zone of He init).  PReLU and max pool commute with a positive scale, so the network is unchanged, and
+    in f32 arithmetic bit for bit while nothing under- or overflows.  Why: the split-precision operands (x = hi + lo in f16) are
+    accurate only near that scale - below it lo, then hi, are f16 subnormals - and a checkpoint may
+    carry its scale anywhere along the chain.  The heads take what is left."""
+    st = dict(state)
+    for name, readers in _CHAINS[net]:
+        w = st[name + ".weight"]
+        rms = float(w.double().pow(2).mean().sqrt())
+        if rms == 0.0:
+            continue
+        e = math.log2(math.sqrt(2.0 / w[0].numel()) / rms)
+        k = int(round(e)) if abs(e) > dead_zone else 0
+        if k:
+            st[name + ".weight"] = w * 2.0 ** k
+            st[name + ".bias"] = st[name + ".bias"] * 2.0 ** k
+            for n in readers:
+                st[n + ".weight"] = st[n + ".weight"] * 2.0 ** -k
+    return st
+
+
 def _dense_as_conv(w, k, c):
     """MTCNN dense layer over a k x k x c map flattened (w, h, c) -> conv weight [o, c, kh, kw]."""
     o = w.shape[0]
@@ -128,7 +158,7 @@ class MTCNNHIP:
     SINGLE_FRAME_LEVEL_STREAMS = 4
     def __init__(self, pstate, rstate, ostate, device="cuda:0", minsize=20, factor=0.709,
                  thresholds=(0.6, 0.7, 0.7), cap_scale=2048, keep_scale=256, cap_p=512, cap_r=64, cap_o=16,
-                 fused_pnet=True, batch_min_pixels=None):
+                 fused_pnet=True, batch_min_pixels=None, canonical=True):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device)
@@ -152,6 +182,10 @@ class MTCNNHIP:
         self.solo_max_frames = 7            # up to this many frames a call that is not a batch runs on ONE stream, eagerly, and is recorded
         d = self.device
         p, r, o = ({k: v.detach().float().cpu() for k, v in s.items()} for s in (pstate, rstate, ostate))
+        # canonical: every path runs the nets rescaled to the He-init weight scale (canonical_scale: the same f32 results, and
+        # split-precision operands inside the envelope the batch path's margins are sized for).  False: the weights as given.
+        if canonical:
+            p, r, o = (canonical_scale(s, n) for s, n in ((p, "pnet"), (r, "rnet"), (o, "onet")))
         self.p1 = _MConv(0, p["conv1.weight"], p["conv1.bias"], p["prelu1.weight"], d)
         self.p2 = _MConv(1, p["conv2.weight"], p["conv2.bias"], p["prelu2.weight"], d)
         hw = torch.cat([p["conv4_1.weight"].reshape(2, 32), p["conv4_2.weight"].reshape(4, 32)])
@@ -164,7 +198,7 @@ class MTCNNHIP:
         w3p = torch.zeros((32, 10, 16)); w3p[:, :9, :16] = p["conv3.weight"].permute(0, 2, 3, 1).reshape(32, 9, 16)
         self._p23 = tuple(t.to(torch.float32).contiguous().to(d) for t in (
             w2p, p["conv2.bias"], p["prelu2.weight"], w3p, p["conv3.bias"], p["prelu3.weight"], hw.t().contiguous(), hb))
-        self.refine_margin = 2e-3           # in logit units, ~200x the split-precision error
+        self.refine_margin = 2e-3           # in logit units; >= 20x the split format's error inside the envelope of DESIGN.md 4.3a
         # The batch path (batch_min_pixels): only the cells within ``refine_margin`` of the face threshold are re-evaluated exactly (every
         # keep / reject decision is that of f32 arithmetic); kept cells above the band carry the split-precision heads (~2e-6 from
         # the f32 ones) - as the R-/O-Net crops do (``split_ro``).  False: every cell that can be kept carries the f32 path's bits.
@@ -190,7 +224,7 @@ class MTCNNHIP:
         self.split_ro = True
         self.split_conv1 = True             # with split_ro: the first layer's conv on the f16 matrix cores too (csrc/ro_conv1.hip, F16)
         self.split_tail = True              # with split_ro: conv3 / dense4 (R-Net), conv4 / dense5 (O-Net) as split-precision GEMMs too
-        self.ro_margin = 1e-3               # in logit units; the split path's measured head error is ~1e-6
+        self.ro_margin = 1e-3               # in logit units; >= 20x the split format's error inside the envelope of DESIGN.md 4.3a
         self.ro_list_cap = (1024, 256)      # slots of the exact pass's work list (R-Net, O-Net); entries past it keep the split values
         def c2w(w):
             o, c = w.shape[0], w.shape[1]

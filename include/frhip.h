@@ -329,7 +329,7 @@ int fr_crop_conv1_f32(int net, const uint8_t* frames, int nframes, int H, int W,
  * y_split [nframes*cap][P*P pixels][hi 32 channels | lo 32 channels], 128 B per pixel, channels >= Cout zero (P = 11 / 23) -
  * the operand format of fr_ro_conv2_split.  Same slots computed / left unwritten as fr_crop_conv1_f32.
  * conv_f16 = 0: the conv itself is the f32 form's (the map is hi + lo of fr_crop_conv1_f32's to 2^-21); 1: the conv runs on
- * the f16 matrix cores with split-precision operands too (~1e-6 of the map's scale from the f32 form). */
+ * the f16 matrix cores with split-precision operands too (the split format's error from the f32 form: DESIGN.md 4.3a). */
 int fr_crop_conv1_split(int net, const uint8_t* frames, int nframes, int H, int W, const float* boxes,
                         const int32_t* counts, int cap, const float* w, const float* bias, const float* slope,
                         void* y_split, int conv_f16, fr_stream_t stream);
@@ -339,7 +339,7 @@ int fr_crop_conv1_list_f32(int net, const uint8_t* frames, int nframes, int H, i
                            const int32_t* list, const int32_t* list_count, int list_cap, const float* w,
                            const float* bias, const float* slope, float* y, fr_stream_t stream);
 /* R-Net / O-Net SECOND layer on the f16 matrix cores with split-precision operands (three v_mfma_f32_16x16x32_f16 per
- * product term, f32 accumulate; heads differ from the f32 layers by ~1e-6): net 0: [.,11,11,28] -> conv 3x3 -> PReLU ->
+ * product term, f32 accumulate; heads differ from the f32 layers by the split format's error): net 0: [.,11,11,28] -> conv 3x3 -> PReLU ->
  * 3x3/s2 pool -> y f32 [nslots,4,4,48]; net 1: [.,23,23,32] -> ... -> [nslots,10,10,64] - the outputs of layers 11 / 21 of
  * fr_dconv_mfma_f32.  x_split: fr_crop_conv1_split's map; w f32 [Cout][9 taps][32 channels] (channels >= Cin zero);
  * counts / cap as fr_dconv_mfma_f32 (nslots = frames x cap).  The cascade's keep / reject decisions stay those of f32
@@ -348,7 +348,7 @@ int fr_crop_conv1_list_f32(int net, const uint8_t* frames, int nframes, int H, i
 int fr_ro_conv2_split(int net, const void* x_split, const float* w, const float* bias, const float* slope, float* y,
                       int nslots, const int32_t* counts, int cap, int32_t* zero_word, fr_stream_t stream);
 /* The small tail layers of R-Net / O-Net as one split-precision GEMM kernel on the f16 matrix cores (x = hi + lo in f16,
- * three MFMAs per product term, f32 accumulate; ~1e-6 of the output's scale from the f32 layers): layer 12 = R-Net conv3
+ * three MFMAs per product term, f32 accumulate; the split format's error from the f32 layers): layer 12 = R-Net conv3
  * (2x2, 48 -> 64, [.,4,4,48] -> [.,3,3,64]), 13 = R-Net dense4 ([.,3,3,64] -> [.,128]), 22 = O-Net conv3 (3x3, 64 -> 64,
  * [.,10,10,64] -> 8x8 -> 2x2/s2 max pool -> [.,4,4,64]), 23 = O-Net conv4 (2x2, 64 -> 128,
  * [.,4,4,64] -> [.,3,3,128]), 24 = O-Net dense5 ([.,3,3,128] -> [.,256]) - the layers of the same ids of fr_dconv_mfma_f32,
@@ -359,7 +359,8 @@ int fr_ro_gemm_pack(int layer, const float* w, void* out, fr_stream_t stream);
 int fr_ro_gemm_split(int layer, const float* x, const void* w_packed, const float* bias, const float* slope, float* y,
                      int nslots, const int32_t* counts, int cap, fr_stream_t stream);
 /* The exact pass's work list: the valid slots whose logit difference head[s][1] - head[s][0] lies within `margin` of
- * logit_thr = ln(t / (1 - t)) (t: the stage's probability threshold) are appended to list (any order); *list_count = how
+ * logit_thr = ln(t / (1 - t)) (t: the stage's probability threshold), or whose heads are not all finite (NaN or +-inf: an
+ * f16 operand overflowed), are appended to list (any order); *list_count = how
  * many there are (may exceed list_cap: entries past it are dropped, consumers clamp).  head f32 [nframes*cap][nhead].
  * *list_count must be 0 on entry (fr_ro_conv2_split's zero_word, or the caller's memset).
  * OVERFLOW (*list_count > list_cap): list holds list_cap distinct qualifying slots, which ones is unspecified (atomic order);
@@ -376,7 +377,7 @@ int fr_ro_margin_list(const float* head, int nhead, const int32_t* counts, int n
 int fr_ro_scatter_rows(const float* src, const int32_t* list, const int32_t* list_count, int list_cap, int ncols,
                        float* dst, fr_stream_t stream);
 /* P-Net conv2 -> PReLU -> conv3 -> PReLU -> heads fused, on the f16 matrix cores with split-precision operands
- * (x = hi + lo in f16, three MFMAs per product term, f32 accumulate; ~1e-5 logit error), followed by an EXACT f32
+ * (x = hi + lo in f16, three MFMAs per product term, f32 accumulate; the split format's logit error), followed by an EXACT f32
  * re-evaluation of every cell whose logit1 - logit0 >= refine_logit_thr (pass ln(t/(1-t)) - 2e-3 for threshold t):
  * every cell that can be kept by fr_pnet_candidates then carries exact f32 logits and regressions, every other cell is
  * below the threshold by more than the approximation error.  x1: P-Net conv1 output (layer 0 of fr_dconv_mfma_f32),
@@ -388,7 +389,7 @@ int fr_ro_scatter_rows(const float* src, const int32_t* list, const int32_t* lis
  * refine_band_hi: <= refine_logit_thr (pass -INFINITY): as above.  > refine_logit_thr: only the cells with refine_logit_thr <=
  * logit1 - logit0 <= refine_band_hi - the band around the face threshold, pass ln(t/(1-t)) + 2e-3 - are re-evaluated
  * exactly (every keep / reject decision is still that of f32 arithmetic); the cells above the band keep their
- * split-precision rows, which the kernel then writes for every cell >= refine_logit_thr (~2e-6 from the f32 heads).
+ * split-precision rows, which the kernel then writes for every cell >= refine_logit_thr (the split format's error from the f32 heads).
  * refined_count (optional device i32, accumulated): number of re-evaluated cells.
  * workspace: fr_pnet23_workspace_bytes(B, H1, W1) bytes; its first B*(H1-4)*(W1-4) floats are the logit differences
  * (the `dl` argument of fr_pnet_candidates), behind them the per-block lists of the cells the exact pass re-evaluates.
@@ -438,7 +439,7 @@ int fr_stage_select(const float* boxes, const float* head, int nh, const int32_t
 
 /* Band mode with conv1 on the f16 matrix cores (round 4, batches).  fr_pnet_conv1_band mode 0: P-Net conv1 (+ the pyramid
  * resize, PReLU, 2x2 ceil pool: layer 0 of fr_dconv_mfma_f32) with split-precision operands - writes the split map y_split
- * only (y optional: the f32 view of the same ~1e-6-accurate values).  The exact pass then needs an exact f32 map under the
+ * only (y optional: the f32 view of the same split-accurate values).  The exact pass then needs an exact f32 map under the
  * windows of the cells on its lists: fr_pnet_band_tiles marks the conv1 tiles (8 x 32 map pixels) those windows touch
  * (tbuf: 1 + ceil(tiles / 32) int32 = [count | bitmap], zeroed here; tiles: int32 [fr_pnet_band_tiles_count(B, H1, W1)]), and
  * fr_pnet_conv1_band mode 1 runs the EXACT f32 kernel over that list (list = tiles, list_count = tbuf, list_cap = the tile

@@ -55,7 +55,8 @@ def _edge_d(thr, margin, sign):
 @pytest.mark.parametrize("nhead", [6, 16])
 def test_ro_margin_list_vs_numpy(lib, nhead):
     """fr_ro_margin_list over 3 frames x 300 slots (900: not a multiple of 256), counts {300, 0, 171}: the listed set is the
-    numpy set of valid slots with |d - thr| <= margin (f32), including planted rows exactly on the margin; qualifying heads past
+    numpy set of valid slots with |d - thr| <= margin (f32) or any head not finite (NaN, +inf, -inf: the exact pass decides),
+    including planted rows exactly on the margin; qualifying heads past
     a frame's count never appear; with a list capacity below the number of qualifying slots the counter still counts them all
     and the list holds list_cap distinct members of the set, nothing past list_cap is written."""
     from facerecognition_infrenceengine_amd import _lib
@@ -74,9 +75,21 @@ def test_ro_margin_list_vs_numpy(lib, nhead):
     valid = (np.arange(cap)[None, :] < counts[:, None]).reshape(-1)
     h[~valid, 0] = 0.0
     h[~valid, 1] = thr                                           # would qualify, but lie past their frame's count
-    d = (h[:, 1] - h[:, 0]).astype(F32)
-    want = set(np.nonzero(valid & (np.abs((d - thr).astype(F32)) <= margin))[0].tolist())
-    assert {3, 4, 2 * cap + 170} <= want and not ({5, 6, 2 * cap + 169} & want)
+    # non-finite split heads (an f16 operand overflowed): d = NaN, +inf, -inf must go to the exact pass on valid slots, never
+    # past the counts
+    nonfinite = {7: (0.0, np.nan), 8: (0.0, np.inf), 9: (np.inf, 0.0), 10: (np.inf, np.inf), 2 * cap + 168: (np.nan, 0.0),
+                 cap + 5: (0.0, np.nan), 2 * cap + 200: (0.0, np.inf), 2 * cap + 201: (np.inf, 0.0)}
+    for s, (a0, a1) in nonfinite.items():
+        h[s, 0], h[s, 1] = a0, a1
+    # a finite logit difference far from the threshold, but a regression / landmark head that is not: the exact pass too
+    h[11, 0], h[11, 1], h[11, nhead - 1] = 0.0, thr + 5.0, np.nan
+    h[12, 0], h[12, 1], h[12, 2] = 0.0, thr - 5.0, -np.inf
+    h[2 * cap + 202, 0], h[2 * cap + 202, 1], h[2 * cap + 202, 3] = 0.0, thr + 5.0, np.nan      # past the count: not
+    with np.errstate(invalid="ignore"):
+        d = (h[:, 1] - h[:, 0]).astype(F32)
+        want = set(np.nonzero(valid & (~np.isfinite(h).all(1) | (np.abs((d - thr).astype(F32)) <= margin)))[0].tolist())
+    assert {3, 4, 2 * cap + 170, 7, 8, 9, 10, 11, 12, 2 * cap + 168} <= want
+    assert not ({5, 6, 2 * cap + 169, cap + 5, 2 * cap + 200, 2 * cap + 201, 2 * cap + 202} & want)
     assert 200 < len(want) < valid.sum()
     hd, cd = _dev(h), _dev(counts)
     for list_cap in (len(want) + 37, len(want), 64):

@@ -277,3 +277,39 @@ def test_decode_image_is_the_imdecode_of_the_enrolment_path():
     g3 = decode_image(grey.getvalue())
     assert g3.shape == smooth.shape and np.array_equal(g3[:, :, 0], g3[:, :, 2])
     assert decode_image(b"not an image") is None
+
+
+@pytest.mark.parametrize("k", [-8, -4, 4, 8])
+def test_canonical_scale_undoes_layer_pair_rescaling(k):
+    """mtcnn.canonical_scale (what MTCNNHIP packs): the synthetic weights come back unchanged; with any layer pair of the three
+    nets rescaled (layer x 2^k with its bias, the layers reading it x 2^-k) every layer returns to within 2^+-1 of the given
+    weights, and the float64 oracle nets compute the same outputs as the given ones."""
+    import torch
+    from facerecognition_infrenceengine_amd import mtcnn, weights
+    from oracle import nets as onets
+    st = weights.synth_mtcnn_states(seed=6)
+    names = ("pnet", "rnet", "onet")
+    for s, n in zip(st, names):
+        c = mtcnn.canonical_scale(s, n)
+        assert all(torch.equal(c[key], s[key]) for key in s), n
+    g = torch.Generator().manual_seed(k + 100)
+    xs = {"pnet": torch.randn((2, 3, 17, 23), generator=g, dtype=torch.float64),
+          "rnet": torch.randn((3, 3, 24, 24), generator=g, dtype=torch.float64),
+          "onet": torch.randn((3, 3, 48, 48), generator=g, dtype=torch.float64)}
+    fwd = {"pnet": onets.pnet_forward, "rnet": onets.rnet_forward, "onet": onets.onet_forward}
+    for s, n in zip(st, names):
+        for layer, readers in mtcnn._CHAINS[n]:
+            r = dict(s)
+            r[layer + ".weight"] = r[layer + ".weight"] * 2.0 ** k
+            r[layer + ".bias"] = r[layer + ".bias"] * 2.0 ** k
+            for m in readers:
+                r[m + ".weight"] = r[m + ".weight"] * 2.0 ** -k
+            c = mtcnn.canonical_scale(r, n)
+            for key in s:
+                if key.endswith(".weight") and not key.startswith("prelu"):
+                    ratio = float(c[key].abs().sum() / s[key].abs().sum())
+                    assert 0.5 <= ratio <= 2.0, (n, layer, key, ratio)
+            want = fwd[n]({key: v.double() for key, v in s.items()}, xs[n])
+            got = fwd[n]({key: v.double() for key, v in c.items()}, xs[n])
+            for a, b in zip(got, want):
+                assert torch.allclose(a, b, rtol=1e-9, atol=1e-12), (n, layer)
