@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfrhip.so")
 
 _lock = threading.Lock()
 _lib = None
-ABI_VERSION = 102          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 103          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
 
 
 class FrError(RuntimeError):
@@ -71,6 +71,9 @@ SIGNATURES = {
     "fr_gallery_match_workspace": (_Z, [_I, _L]),
     "fr_gallery_match_f32": (_I, [_P, _P, _I, _L, _I, _L, _P, _P, _P, _Z, _P, _I, _P]),
     "fr_gallery_match_view_f32": (_I, [_P, _P, _P, _I, _L, _I, _P, _P, _P, _Z, _P]),
+    "fr_gallery_topk_workspace": (_Z, [_I, _L, _I]),
+    "fr_gallery_topk_f32": (_I, [_P, _P, _I, _L, _I, _I, _L, _P, _P, _P, _Z, _P, _I, _P]),
+    "fr_gallery_topk_view_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _Z, _P]),
     "fr_gallery_update_rows_f32": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "fr_gallery_match_f16_workspace": (_Z, [_I, _L]),
     "fr_gallery_match_f16": (_I, [_P, _P, _P, _I, _L, _I, _L, _P, _P, _P, _Z, _P, _I, _P]),
@@ -81,6 +84,7 @@ SIGNATURES = {
     "fr_match_decide": (_I, [_P, _P, _I, _F, _F, _P, _P]),
     "fr_match_pack_candidates": (_I, [_P, _P, _I, _P, _P]),
     "fr_match_reduce_shards": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "fr_match_reduce_shards_topk": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "fr_exchange_pack_queries": (_I, [_P, _I, _I, _I, _P, _P]),
     "fr_exchange_counts": (_I, [_P, _I, _I, _I, _P, _P]),
     "fr_gallery_first_above_f32": (_I, [_P, _P, _I, _L, _I, _F, _I, _L, _P, _P, _P, _Z, _P]),

@@ -6,30 +6,13 @@
 // A = 32 gallery rows, B = 32 queries, so a lane owns ONE query (column) and 16 gallery
 // rows (registers): the running (max, first-argmax) is lane-local, no cross-lane work
 // inside the scan.  HBM-bound: N*D*4 bytes per pass per 32-query group.
-#include "common.h"
+#include "match_scan.h"   // GD / QPAD / QG, group_has_valid, take_better, scan_blocks: shared with match_topk.hip
 
-#define GD 512          // embedding dim
-#define QPAD 516        // LDS row stride (floats) for the query tile: breaks the 2 KB bank stride
-#define QG 32           // queries per group (MFMA N)
 #ifndef FR_TOPK
 #define FR_TOPK 4
 #endif
 
 struct BestPair { float s; int64_t i; };
-
-__device__ __forceinline__ bool group_has_valid(const int32_t* seg_counts, int seg_len, int qa, int qb) {
-    // [qa, qb) spans at most a few segments; a segment contributes iff its first slot inside the range is real
-    for (int q = qa; q < qb;) {
-        if (slot_valid(seg_counts, seg_len, q)) return true;
-        q = (q / seg_len + 1) * seg_len;
-    }
-    return false;
-}
-
-__device__ __forceinline__ void take_better(float& bs, int64_t& bi, float s, int64_t i) {
-    // max score; lowest index on exact ties (== first maximum in row order)
-    if (s > bs || (s == bs && i < bi && i >= 0)) { bs = s; bi = i; }
-}
 
 // VIEW: row r of the scanned gallery is storage slot view[r] of G (a per-company view of one device-resident
 // slab, no copy of the rows); the winner index is the VIEW position, so the order/tie rule is the view's.
@@ -117,14 +100,6 @@ __global__ void gallery_reduce(const float* __restrict__ ws_score, const int64_t
     // reference: best_score starts at -1 and only a strictly larger score replaces it
     if (bi < 0 || !(bs > -1.0f)) { out_idx[f] = -1; out_score[f] = -1.0f; }
     else { out_idx[f] = bi + row_offset; out_score[f] = bs; }
-}
-
-static int scan_blocks(int64_t N) {
-    int64_t tiles = (N + 31) / 32;
-    int64_t b = (tiles + 3) / 4;
-    if (b < 1) b = 1;
-    if (b > 1024) b = 1024;
-    return (int)b;
 }
 
 extern "C" size_t fr_gallery_match_workspace(int F, int64_t N) {

@@ -1,0 +1,287 @@
+// Exact top-K gallery identification: the K best rows per query under the total order (score descending, row
+// ascending) among rows whose score is > -1 - the reference loop's rule (best starts at -1, strict '>', first
+// maximum) extended from 1 to K.  Scores are the same k-ordered f32 MFMA chains as gallery_scan_f32 (match.hip), so
+// column 0 is bit-identical to the top-1 match for every K.
+//
+// A candidate list is KP = 2 / 4 / 8 / 16 (score, row) pairs in REGISTERS, best first; an empty slot is
+// (-inf, -1) and loses to every row.  Every index into a list is a compile-time constant (fully unrolled loops): a
+// dynamically indexed list would live in scratch memory.  Two operations:
+//   insert:      the scan's step.  One compare drops a score that is not '>' the lane's K-th entry - rows ascend
+//                within a lane, so an equal score with a higher row loses, as it must; otherwise an unrolled
+//                compare-and-shift puts the pair behind every entry with score >= s.
+//   merge:       the K best of two sorted lists, as a bitonic merge: c[j] = better(a[j], b[KP-1-j]) holds the K best
+//                of both as a bitonic sequence, log2(KP) compare-exchange stages sort it.  Used by every merge level:
+//                half-waves (__shfl_xor 32), waves (LDS), blocks (workspace), shards.
+#include "match_scan.h"
+
+#define TOPK_EMPTY_S (-INFINITY)
+
+// a before b in the total order; rows are distinct among real candidates, all empty slots are equal
+__device__ __forceinline__ bool topk_before(float as, int64_t ai, float bs, int64_t bi) {
+    return ai >= 0 && (bi < 0 || as > bs || (as == bs && ai < bi));
+}
+
+template <int KP>
+struct TopK {
+    float s[KP];
+    int64_t i[KP];
+
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) { s[j] = TOPK_EMPTY_S; i[j] = -1; }
+    }
+
+    // scan step: row gi ascends from call to call, s is finite or NaN (a NaN is never '>': never listed)
+    __device__ __forceinline__ void insert(float v, int64_t gi) {
+        if (!(v > s[KP - 1])) return;
+#pragma unroll
+        for (int j = KP - 1; j > 0; --j) {
+            if (v > s[j - 1]) { s[j] = s[j - 1]; i[j] = i[j - 1]; }
+            else if (v > s[j]) { s[j] = v; i[j] = gi; }
+        }
+        if (v > s[0]) { s[0] = v; i[0] = gi; }
+    }
+
+    // this = the KP best of this and o (both sorted)
+    __device__ __forceinline__ void merge(const TopK& o) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j)
+            if (topk_before(o.s[KP - 1 - j], o.i[KP - 1 - j], s[j], i[j])) { s[j] = o.s[KP - 1 - j]; i[j] = o.i[KP - 1 - j]; }
+#pragma unroll
+        for (int d = KP / 2; d >= 1; d >>= 1) {
+#pragma unroll
+            for (int j = 0; j < KP; ++j) {
+                if ((j & d) == 0 && topk_before(s[j + d], i[j + d], s[j], i[j])) {
+                    const float ts = s[j]; const int64_t ti = i[j];
+                    s[j] = s[j + d]; i[j] = i[j + d];
+                    s[j + d] = ts; i[j + d] = ti;
+                }
+            }
+        }
+    }
+
+    __device__ __forceinline__ TopK shfl_xor(int mask) const {
+        TopK o;
+#pragma unroll
+        for (int j = 0; j < KP; ++j) { o.s[j] = __shfl_xor(s[j], mask, 64); o.i[j] = __shfl_xor(i[j], mask, 64); }
+        return o;
+    }
+
+    // entries [0, K) from ps / pi (stride 1), the rest empty
+    __device__ __forceinline__ void load(const float* ps, const int64_t* pi, int K) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const bool in = j < K;
+            s[j] = in ? ps[j] : TOPK_EMPTY_S;
+            i[j] = in ? pi[j] : -1;
+        }
+    }
+
+    __device__ __forceinline__ void store(float* ps, int64_t* pi, int K) const {
+#pragma unroll
+        for (int j = 0; j < KP; ++j)
+            if (j < K) { ps[j] = s[j]; pi[j] = i[j]; }
+    }
+};
+
+// Same orientation and arithmetic as gallery_scan_f32: a lane owns ONE query and 16 rows of a tile, its list is
+// lane-local inside the scan.  Partial lists go to ws_score / ws_idx [gridDim.x][F][K].
+template <bool VIEW, int KP>
+__global__ __launch_bounds__(256) void gallery_scan_topk_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                             const int64_t* __restrict__ view, int F, int64_t N, int K,
+                                                             float* __restrict__ ws_score, int64_t* __restrict__ ws_idx,
+                                                             const int32_t* __restrict__ seg_counts, int seg_len) {
+    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q0 = blockIdx.y * QG;
+    // a group made of padding only does no work (the reduce reports empty lists for every padding slot)
+    if (seg_counts && !group_has_valid(seg_counts, seg_len, q0, min(q0 + QG, F))) return;
+    stage_query_group(Q, F, q0, qs);
+    __syncthreads();
+    const int r = lane & 31, h = lane >> 5;
+    TopK<KP> top;
+    top.clear();
+    const int64_t ntiles = (N + 31) / 32;
+    for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < ntiles; t += (int64_t)gridDim.x * 4) {
+        const int64_t row = t * 32 + r;
+        const bool ok = row < N;
+        const int64_t slot = VIEW ? (ok ? view[row] : 0) : (ok ? row : 0);
+        const float16v acc = scan_tile_f32(G + slot * GD + 4 * h, &qs[r * QPAD + 4 * h], ok);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int64_t gi = t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;   // ascends with reg and t
+            if (gi < N) top.insert(acc[reg], gi);
+        }
+    }
+    // the two half-waves that hold the same query, then the 4 waves through LDS
+    top.merge(top.shfl_xor(32));
+    __syncthreads();
+    float* ls = qs;                                                          // reuse LDS: 4 x 32 lists
+    int64_t* li = reinterpret_cast<int64_t*>(qs + 4 * 32 * KP);
+    if (h == 0 && wave > 0) top.store(ls + (wave * 32 + r) * KP, li + (wave * 32 + r) * KP, KP);
+    __syncthreads();
+    if (tid < 32) {
+        for (int w = 1; w < 4; ++w) {
+            TopK<KP> o;
+            o.load(ls + (w * 32 + tid) * KP, li + (w * 32 + tid) * KP, KP);
+            top.merge(o);
+        }
+        if (q0 + tid < F) {
+            const int64_t at = ((int64_t)blockIdx.x * F + q0 + tid) * K;
+            top.store(ws_score + at, ws_idx + at, K);
+        }
+    }
+}
+
+// One wave per query: lane l merges the lists of blocks l, l + 64, ..., six __shfl_xor levels merge the lanes, lane 0
+// applies row_offset, the '> -1' rule and the padding rule.
+template <int KP>
+__global__ __launch_bounds__(256) void gallery_topk_reduce(const float* __restrict__ ws_score,
+                                                           const int64_t* __restrict__ ws_idx, int nblk, int F, int K,
+                                                           int64_t row_offset, int64_t* __restrict__ out_idx,
+                                                           float* __restrict__ out_score,
+                                                           const int32_t* __restrict__ seg_counts, int seg_len) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (f >= F) return;
+    TopK<KP> top;
+    top.clear();
+    if (!seg_counts || slot_valid(seg_counts, seg_len, f)) {
+        for (int b = lane; b < nblk; b += 64) {
+            TopK<KP> o;
+            const int64_t at = ((int64_t)b * F + f) * K;
+            o.load(ws_score + at, ws_idx + at, K);
+            top.merge(o);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) top.merge(top.shfl_xor(m));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            if (j < K) {
+                // reference: best_score starts at -1 and only a strictly larger score replaces it
+                const bool has = top.i[j] >= 0 && top.s[j] > -1.0f;
+                out_idx[(int64_t)f * K + j] = has ? top.i[j] + row_offset : -1;
+                out_score[(int64_t)f * K + j] = has ? top.s[j] : -1.0f;
+            }
+        }
+    }
+}
+
+// cand int32 [R][n][K][3] (score bits, row lo, row hi; row < 0: empty): the K best of the R lists of each query
+template <int KP>
+__global__ __launch_bounds__(64) void match_reduce_shards_topk(const int32_t* __restrict__ cand, int R, int n, int K, int q0, int F,
+                                         int64_t* __restrict__ out_idx, float* __restrict__ out_score) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    TopK<KP> top;
+    top.clear();
+    for (int r = 0; r < R; ++r) {
+        const int32_t* c = cand + ((int64_t)r * n + q0 + f) * K * 3;
+        TopK<KP> o;
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            int64_t i = -1;
+            float s = TOPK_EMPTY_S;
+            if (j < K) {
+                i = (int64_t)(((uint64_t)(uint32_t)c[j * 3 + 2] << 32) | (uint32_t)c[j * 3 + 1]);
+                s = __int_as_float(c[j * 3]);
+            }
+            o.i[j] = i < 0 ? -1 : i;
+            o.s[j] = i < 0 ? TOPK_EMPTY_S : s;
+        }
+        top.merge(o);
+    }
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+        if (j < K) {
+            const bool has = top.i[j] >= 0;
+            out_idx[(int64_t)f * K + j] = has ? top.i[j] : -1;
+            out_score[(int64_t)f * K + j] = has ? top.s[j] : -1.0f;
+        }
+    }
+}
+
+static int topk_kp(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : 16; }
+
+static size_t topk_score_bytes(int F, int64_t N, int K) {
+    const size_t lists = (size_t)scan_blocks(N) * (size_t)(F > 0 ? F : 1) * (size_t)(K > 0 ? K : 1);
+    return (lists * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" size_t fr_gallery_topk_workspace(int F, int64_t N, int K) {
+    const size_t lists = (size_t)scan_blocks(N) * (size_t)(F > 0 ? F : 1) * (size_t)(K > 0 ? K : 1);
+    return topk_score_bytes(F, N, K) + lists * sizeof(int64_t) + 256;
+}
+
+template <int KP>
+static int gallery_topk_launch_kp(const float* Q, const float* G, const int64_t* view, int F, int64_t N, int K,
+                                  int64_t row_offset, int64_t* out_idx, float* out_score, float* ws_score,
+                                  int64_t* ws_idx, const int32_t* seg_counts, int seg_len, hipStream_t s) {
+    const int nblk = scan_blocks(N);
+    dim3 grid(nblk, (F + QG - 1) / QG);
+    if (view) gallery_scan_topk_f32<true, KP><<<grid, 256, 0, s>>>(Q, G, view, F, N, K, ws_score, ws_idx, seg_counts, seg_len);
+    else gallery_scan_topk_f32<false, KP><<<grid, 256, 0, s>>>(Q, G, nullptr, F, N, K, ws_score, ws_idx, seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_scan_topk_f32");
+    gallery_topk_reduce<KP><<<fr_cdiv(F, 4), 256, 0, s>>>(ws_score, ws_idx, nblk, F, K, row_offset, out_idx, out_score,
+                                                         seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_topk_reduce");
+    return FR_OK;
+}
+
+static int gallery_topk_launch(const char* who, const float* Q, const float* G, const int64_t* view, int F, int64_t N,
+                               int D, int K, int64_t row_offset, int64_t* out_idx, float* out_score, void* workspace,
+                               size_t workspace_bytes, const int32_t* seg_counts, int seg_len, fr_stream_t stream) {
+    FR_REQUIRE(K >= 1 && K <= FR_TOPK_MAX, "%s: K must be 1..%d (got %d)", who, FR_TOPK_MAX, K);
+    FR_REQUIRE(!seg_counts || (seg_len > 0 && F % seg_len == 0), "%s: seg_len must divide F", who);
+    FR_REQUIRE(D == GD, "%s: D must be %d (got %d)", who, GD, D);
+    FR_REQUIRE(F >= 0 && N >= 0, "%s: negative size", who);
+    if (F == 0) return FR_OK;
+    FR_REQUIRE(Q && out_idx && out_score && (G || N == 0), "%s: null pointer", who);
+    FR_REQUIRE(workspace && workspace_bytes >= fr_gallery_topk_workspace(F, N, K),
+               "%s: workspace too small (%zu < %zu)", who, workspace_bytes, fr_gallery_topk_workspace(F, N, K));
+    float* ws_score = reinterpret_cast<float*>(workspace);
+    int64_t* ws_idx = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + topk_score_bytes(F, N, K));
+    hipStream_t s = fr_stream(stream);
+    switch (topk_kp(K)) {
+        case 2: return gallery_topk_launch_kp<2>(Q, G, view, F, N, K, row_offset, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        case 4: return gallery_topk_launch_kp<4>(Q, G, view, F, N, K, row_offset, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        case 8: return gallery_topk_launch_kp<8>(Q, G, view, F, N, K, row_offset, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        default: return gallery_topk_launch_kp<16>(Q, G, view, F, N, K, row_offset, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+    }
+}
+
+extern "C" int fr_gallery_topk_f32(const float* Q, const float* G, int F, int64_t N, int D, int K, int64_t row_offset,
+                                   int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
+                                   const int32_t* seg_counts, int seg_len, fr_stream_t stream) {
+    return gallery_topk_launch("fr_gallery_topk_f32", Q, G, nullptr, F, N, D, K, row_offset, out_idx, out_score,
+                               workspace, workspace_bytes, seg_counts, seg_len, stream);
+}
+
+extern "C" int fr_gallery_topk_view_f32(const float* Q, const float* G, const int64_t* view, int F, int64_t Nview,
+                                        int D, int K, int64_t* out_idx, float* out_score, void* workspace,
+                                        size_t workspace_bytes, fr_stream_t stream) {
+    FR_REQUIRE(view || Nview == 0, "fr_gallery_topk_view_f32: null view");
+    // Nview == 0: the scan kernel sees no tiles and the reduce writes (-1, -1.0) everywhere
+    return gallery_topk_launch("fr_gallery_topk_view_f32", Q, G, Nview ? view : nullptr, F, Nview, D, K, 0, out_idx,
+                               out_score, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+extern "C" int fr_match_reduce_shards_topk(const int32_t* cand, int R, int n, int K, int q0, int F, int64_t* out_idx,
+                                           float* out_score, fr_stream_t stream) {
+    FR_REQUIRE(K >= 1 && K <= FR_TOPK_MAX, "fr_match_reduce_shards_topk: K must be 1..%d (got %d)", FR_TOPK_MAX, K);
+    FR_REQUIRE(R >= 1 && n >= 0 && q0 >= 0 && F >= 0 && q0 + F <= n,
+               "fr_match_reduce_shards_topk: bad range (R %d n %d q0 %d F %d)", R, n, q0, F);
+    if (F == 0) return FR_OK;
+    FR_REQUIRE(cand && out_idx && out_score, "fr_match_reduce_shards_topk: null pointer");
+    hipStream_t s = fr_stream(stream);
+    const int blocks = fr_cdiv(F, 64);
+    switch (topk_kp(K)) {
+        case 2: match_reduce_shards_topk<2><<<blocks, 64, 0, s>>>(cand, R, n, K, q0, F, out_idx, out_score); break;
+        case 4: match_reduce_shards_topk<4><<<blocks, 64, 0, s>>>(cand, R, n, K, q0, F, out_idx, out_score); break;
+        case 8: match_reduce_shards_topk<8><<<blocks, 64, 0, s>>>(cand, R, n, K, q0, F, out_idx, out_score); break;
+        default: match_reduce_shards_topk<16><<<blocks, 64, 0, s>>>(cand, R, n, K, q0, F, out_idx, out_score); break;
+    }
+    FR_CHECK_LAUNCH("match_reduce_shards_topk");
+    return FR_OK;
+}

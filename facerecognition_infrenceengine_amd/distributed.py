@@ -13,6 +13,7 @@ The reference's only parallelism is one OS process per camera, each scanning the
   3. ONE all-gather of the per-shard candidates, packed as int32 (score bits, row lo, row hi); each rank
      reduces the candidates of its own queries: maximum score, lowest global row on exact ties - the same
      rule as the single-GPU scan (strict '>' in /root/reference/infrenceServer.py:538-542).
+     ``match_topk`` is the same exchange with K candidates per slot and shard in step 3 (12 * K bytes per slot).
 
 The arithmetic is injected as an ``ops`` object: ``HipOps`` (the product: libfrhip.so kernels through
 ``GalleryMatcher``; fails without a HIP device) or, in the CPU ``gloo`` tests, an oracle-backed stand-in with
@@ -82,6 +83,33 @@ def reduce_packed(allp, world, n, q0, F):
     return reduce_candidates(sc, ix)
 
 
+def reduce_candidates_topk(scores, idx, k):
+    """scores f32 [R,F,K], idx i64 [R,F,K] (global rows, -1 = empty slot) -> the k best per query (idx[F,k],
+    score[F,k]) under the scan's total order: score descending, lowest global row first on exact ties; slots with no
+    candidate hold (-1, -1.0).  Torch form of fr_match_reduce_shards_topk (CPU gloo tests, cross-check of the kernel)."""
+    R, F, K = scores.shape
+    s = scores.permute(1, 0, 2).reshape(F, R * K)
+    i = idx.permute(1, 0, 2).reshape(F, R * K)
+    valid = i >= 0
+    s = torch.where(valid, s, torch.full_like(s, float("-inf")))
+    i = torch.where(valid, i, torch.full_like(i, torch.iinfo(torch.int64).max))
+    by_row = torch.sort(i, dim=1, stable=True).indices                    # rows ascending, empty slots last ...
+    s, i = s.gather(1, by_row), i.gather(1, by_row)
+    by_score = torch.sort(s, dim=1, descending=True, stable=True).indices  # ... then scores descending, stable
+    s, i = s.gather(1, by_score)[:, :k], i.gather(1, by_score)[:, :k]
+    none = i == torch.iinfo(torch.int64).max
+    return (torch.where(none, torch.full_like(i, -1), i).contiguous(),
+            torch.where(none, torch.full_like(s, -1.0), s).contiguous())
+
+
+def reduce_packed_topk(allp, world, n, k, q0, F):
+    """Torch reduce of gathered packed top-k candidates int32 [world*n*k,3] for queries [q0, q0+F)."""
+    mine = allp.view(world, n, k, 3)[:, q0:q0 + F]
+    sc = torch.empty((world, F, k), dtype=torch.int32, device=allp.device).copy_(mine[..., 0]).view(torch.float32)
+    ix = torch.empty((world, F, k, 2), dtype=torch.int32, device=allp.device).copy_(mine[..., 1:]).view(torch.int64)
+    return reduce_candidates_topk(sc, ix.reshape(world, F, k), k)
+
+
 class HipOps:
     """The product's arithmetic for the exchange: libfrhip.so kernels on this rank's GPU."""
 
@@ -101,6 +129,19 @@ class HipOps:
     def scan(self, Q, counts=None, seg_len=0):
         """Q: unit query rows f32 [n,512]; returns global rows (shard row + row_lo) or -1."""
         return self.matcher.match_device(Q, renormalise=False, row_offset=self.row_lo, counts=counts, seg_len=seg_len)
+
+    def scan_topk(self, Q, k, counts=None, seg_len=0):
+        """Q: unit query rows f32 [n,512]; the k best rows of this shard per slot, as global rows (or -1): [n,k]."""
+        return self.matcher.match_topk_device(Q, k, renormalise=False, row_offset=self.row_lo, counts=counts,
+                                              seg_len=seg_len)
+
+    def reduce_topk(self, allp, world, n, k, q0, F):
+        idx = torch.empty((F, k), dtype=torch.int64, device=self.device)
+        score = torch.empty((F, k), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            self.lib.fr_match_reduce_shards_topk(self._lib.ptr(allp), world, n, k, q0, F, self._lib.ptr(idx),
+                                                 self._lib.ptr(score), self._lib.stream_ptr())
+        return idx, score
 
     def pack_queries(self, Qn, q_max):
         send = torch.empty((q_max + 1, Qn.shape[1]), dtype=torch.float32, device=self.device)
@@ -135,7 +176,8 @@ class HipOps:
 
 class ShardedGalleryMatcher:
     def __init__(self, ops, q_max, dim=512, group=None, force_exchange=False):
-        """``ops``: renormalise / pack_queries / gathered_counts / scan / pack / reduce (``HipOps`` in the product).
+        """``ops``: renormalise / pack_queries / gathered_counts / scan / pack / reduce, and scan_topk / reduce_topk for
+        ``match_topk`` (``HipOps`` in the product).
         ``force_exchange``: run both collectives even with one rank (rehearses the RCCL path on a 1-GPU box)."""
         self.ops, self.q_max, self.dim, self.group = ops, q_max, dim, group
         self.force_exchange = force_exchange
@@ -193,3 +235,25 @@ class ShardedGalleryMatcher:
         if marks:
             self.timing.append(marks)
         return out
+
+    def match_topk(self, Q, k):
+        """The k best global rows per local query: (idx i64[F_local,k], score f32[F_local,k]), ranked by score
+        descending, global row ascending; empty slots (-1, -1.0).  The same two collectives as ``match``; the second
+        carries k candidates per query slot (int32 [n*k, 3]: n * k * 12 bytes per rank)."""
+        F = Q.shape[0]
+        assert F <= self.q_max, "more local queries than q_max"
+        Qn = self.ops.renormalise(Q.to(torch.float32).contiguous())
+        if self.world == 1 and not self.force_exchange:
+            return self.ops.scan_topk(Qn, k)
+        dev = Q.device
+        seg = self.q_max + 1
+        send = self.ops.pack_queries(Qn, self.q_max)
+        allq = torch.empty((self.world * seg, self.dim), dtype=torch.float32, device=dev)
+        dist.all_gather_into_tensor(allq, send, group=self.group)
+        counts = self.ops.gathered_counts(allq, self.world, self.q_max)
+        idx, score = self.ops.scan_topk(allq, k, counts=counts, seg_len=seg)       # [n,k]: this shard's k best per slot
+        n = score.shape[0]
+        pair = self.ops.pack(idx.reshape(-1), score.reshape(-1))                   # element-wise: a flat n*k list
+        allp = torch.empty((self.world * n * k, 3), dtype=torch.int32, device=dev)
+        dist.all_gather_into_tensor(allp, pair, group=self.group)
+        return self.ops.reduce_topk(allp, self.world, n, k, self.rank * seg, F)

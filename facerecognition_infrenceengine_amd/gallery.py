@@ -14,6 +14,7 @@ import torch
 from . import _lib
 
 DIM = 512
+TOPK_MAX = 16                  # include/frhip.h FR_TOPK_MAX
 _PIN = threading.local()       # pinned host buffers of GalleryMatcher.match, per thread and query count
 
 
@@ -105,6 +106,32 @@ class GalleryMatcher:
                                           _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), cp, seg_len, s)
         return idx, score
 
+    def match_topk_device(self, Q, k, renormalise=True, row_offset=0, counts=None, seg_len=0):
+        """The ``k`` best rows per query (1 <= k <= 16): device tensors (idx int64[F,k], score float32[F,k]), ranked by
+        score descending, row ascending, among rows scoring > -1; slots past the number of such rows hold (-1, -1.0).
+        Column 0 is bit-identical to ``match_device``.  Always the exact f32 scan over the f32 rows, whatever ``scan``
+        the matcher was built with.  ``row_offset`` / ``counts`` / ``seg_len``: as ``match_device``."""
+        k = _check_k(k)
+        return _topk_device(self, Q, k, renormalise, None, self.G, self.G.shape[0], row_offset, counts, seg_len)
+
+    def match_topk(self, Q, k, min_score=None):
+        """Host-facing: (ids, scores float32[F,k], idx int64[F,k]); ``ids[f]`` is a list of k entries in rank order,
+        None for empty slots and for slots whose score is below ``min_score``."""
+        k = _check_k(k)
+        Q = torch.as_tensor(np.asarray(Q, np.float32)) if not torch.is_tensor(Q) else Q
+        idx, score = self.match_topk_device(Q, k)
+        # two results, ONE synchronisation: asynchronous copies into pinned host memory, then a stream sync
+        idx_h = torch.empty(idx.shape, dtype=torch.int64).pin_memory()
+        score_h = torch.empty(score.shape, dtype=torch.float32).pin_memory()
+        with torch.cuda.device(self.device):
+            idx_h.copy_(idx, non_blocking=True)
+            score_h.copy_(score, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        idx_h, score_h = idx_h.numpy().copy(), score_h.numpy().copy()
+        ids = [[self.ids[i] if i >= 0 and (min_score is None or s >= min_score) else None for i, s in zip(ri, rs)]
+               for ri, rs in zip(idx_h, score_h)]
+        return ids, score_h, idx_h
+
     def decide_device(self, idx, score, thr, unknown_thr=None):
         """1 recognised / 0 unknown / 2 dropped (peopleCount.py:876-887 band)."""
         d = torch.empty(idx.shape[0], dtype=torch.int32, device=self.device)
@@ -136,6 +163,40 @@ class GalleryMatcher:
         idx_h, score_h, dec_h = h[0].numpy().copy(), h[1].numpy().copy(), h[2].numpy().copy()
         ids = [self.ids[i] if (d == 1 and i >= 0) else None for i, d in zip(idx_h, dec_h)]
         return ids, score_h, idx_h
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError(f"k must be 1..{TOPK_MAX} (got {k})")
+    return int(k)
+
+
+def _topk_device(owner, Q, k, renormalise, view, G, N, row_offset=0, counts=None, seg_len=0):
+    """fr_gallery_topk_f32 (``view`` None) / fr_gallery_topk_view_f32 on the current stream of ``owner.device``."""
+    lib, dev = owner.lib, owner.device
+    Q = Q.to(dev, torch.float32).contiguous().reshape(-1, DIM)
+    F = Q.shape[0]
+    idx = torch.empty((F, k), dtype=torch.int64, device=dev)
+    score = torch.empty((F, k), dtype=torch.float32, device=dev)
+    if F == 0:
+        return idx, score
+    with torch.cuda.device(dev):
+        s = _lib.stream_ptr()
+        if renormalise:
+            Qn = torch.empty_like(Q)
+            lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
+            Q = Qn
+        ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_workspace(F, N, k))
+        if view is not None:
+            lib.fr_gallery_topk_view_f32(_lib.ptr(Q), _lib.ptr(G), _lib.ptr(view), F, N, DIM, k, _lib.ptr(idx),
+                                         _lib.ptr(score), _lib.ptr(ws), ws.numel(), s)
+            return idx, score
+        cp = _lib.ptr(counts) if counts is not None else None
+        if counts is not None:
+            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
+        lib.fr_gallery_topk_f32(_lib.ptr(Q), _lib.ptr(G), F, N, DIM, k, row_offset, _lib.ptr(idx), _lib.ptr(score),
+                                _lib.ptr(ws), ws.numel(), cp, seg_len, s)
+    return idx, score
 
 
 class DeviceGallery:
@@ -261,5 +322,13 @@ class GalleryView:
                                                _lib.ptr(ws), ws.numel(), s)
         return idx, score
 
+    def match_topk_device(self, Q, k, renormalise=True):
+        """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``."""
+        k = _check_k(k)
+        if self.generation != self.gallery.generation:
+            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
+        return _topk_device(self, Q, k, renormalise, self.slots, self.gallery.G, len(self.ids))
+
     decide_device = GalleryMatcher.decide_device
     match = GalleryMatcher.match
+    match_topk = GalleryMatcher.match_topk

@@ -269,6 +269,37 @@ class FaceRecognitionProcessor:
                             "det_score": float(det[f]), "recognition_score": 0})
         return out
 
+    def identify(self, frame, company_id, k=5, min_score=None):
+        """Ranked candidate list per face (1 <= k <= 16): a list of dicts {bbox int[4], det_score, candidates}, where
+        ``candidates`` is a list of {person_id, person_info, score} in rank order (score descending, gallery row order
+        on exact ties), at most k long: empty slots and slots scoring below ``min_score`` are left out.
+        ``candidates[0]`` is the row ``recognize`` matches, with the same score bits.  None when the company has no
+        gallery, as ``recognize``."""
+        if not 1 <= int(k) <= 16:
+            raise ValueError(f"k must be 1..16 (got {k})")
+        if self.face_detector is None:
+            self.initialize_detector()
+        matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
+        if len(matcher) == 0:
+            logger.warning("No embeddings found for company %s", company_id)
+            return None
+        r = _detect_embed(self.face_detector, frame)
+        matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
+                                                     r["normed_embedding"], k=int(k))
+        idx, score = idx.cpu().numpy(), score.cpu().numpy()
+        bbox = r["bbox"].cpu().numpy().astype(int)
+        det = r["det_score"].cpu().numpy()
+        out = []
+        for f in range(len(idx)):
+            cands = []
+            for i, s in zip(idx[f], score[f]):
+                if i < 0 or (min_score is not None and s < min_score):
+                    break                                     # ranked: everything behind is empty or lower
+                pid = matcher.ids[i]
+                cands.append({"person_id": pid, "person_info": metadata[pid], "score": s})
+            out.append({"bbox": bbox[f], "det_score": float(det[f]), "candidates": cands})
+        return out
+
     def recognize_batch(self, frames, company_id):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of same-sized BGR uint8
         frames (one per camera).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -415,15 +446,19 @@ def _detect_embed(detector, frame):
         return detector.detect_embed_device(dev)
 
 
-def _match_fresh(manager, company_id, matcher, metadata, Q):
+def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):
     """Scan through the company's view; a sync on another thread may have changed the slab's membership since the
-    view was fetched (its generation moved on): fetch the current view once and retry instead of dropping the frame."""
+    view was fetched (its generation moved on): fetch the current view once and retry instead of dropping the frame.
+    ``k``: the top-k form (idx / score [F,k]) instead of the single best row."""
     from .gallery import StaleViewError
+
+    def scan(m):
+        return m.match_device(Q) if k is None else m.match_topk_device(Q, k)
     try:
-        idx, score = matcher.match_device(Q)
+        idx, score = scan(matcher)
     except StaleViewError:
         matcher, metadata = manager.get_matcher_for_company(company_id)
-        idx, score = matcher.match_device(Q)
+        idx, score = scan(matcher)
     return matcher, metadata, idx, score
 
 

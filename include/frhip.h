@@ -31,9 +31,10 @@ extern "C" {
 typedef void* fr_stream_t;
 
 /* Version of THIS header's ABI: bumped whenever a signature or an argument struct changes shape (101: fr_conv_args gained
- * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads).  fr_version() returns the value the library was built
+ * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads; 103: the fr_gallery_topk_* / fr_match_reduce_shards_topk
+ * entries).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
-#define FR_ABI_VERSION 102
+#define FR_ABI_VERSION 103
 int fr_version(void);
 const char* fr_last_error_string(void);
 /* number of visible HIP devices (<=0: none); does not create a context on any device */
@@ -87,6 +88,24 @@ int fr_gallery_match_f8(const float* Q, const void* G8, const float* G32, int F,
                         int64_t row_offset, int64_t* out_idx, float* out_score,
                         void* workspace, size_t workspace_bytes, const int32_t* seg_counts, int seg_len,
                         fr_stream_t stream);
+/* a-7, K best: exact top-K identification.  The top-K list of a query is the first K rows under the total order
+ * (score descending, row ascending) among rows whose score is > -1.0f - the rule of a-7 (best starts at -1, strict
+ * '>', first maximum) extended from 1 to K; rows are counted in scan order (view position for a view).  Slots past
+ * the number of such rows hold (idx -1, score -1.0f), as does every slot of a padding query and of a NaN query.
+ * Scores are the same f32 dot products, in the same summation order, as fr_gallery_match_f32 computes, so column 0
+ * (out_idx[f][0], out_score[f][0]) is bit-identical to fr_gallery_match_f32 / _view_f32 for every K.
+ * 1 <= K <= FR_TOPK_MAX.  out_idx / out_score: [F][K]; filled slots carry row + row_offset.  workspace:
+ * fr_gallery_topk_workspace() bytes, holding the per-block partial lists [blocks][F][K] (f32 scores, then int64 rows).
+ * F == 0 returns FR_OK without reading a pointer; N == 0 writes (-1, -1.0f) everywhere.
+ * seg_counts / seg_len: see fr_gallery_match_f32. */
+#define FR_TOPK_MAX 16
+size_t fr_gallery_topk_workspace(int F, int64_t N, int K);
+int fr_gallery_topk_f32(const float* Q, const float* G, int F, int64_t N, int D, int K, int64_t row_offset,
+                        int64_t* out_idx /*[F][K]*/, float* out_score /*[F][K]*/, void* workspace,
+                        size_t workspace_bytes, const int32_t* seg_counts, int seg_len, fr_stream_t stream);
+int fr_gallery_topk_view_f32(const float* Q, const float* G, const int64_t* view, int F, int64_t Nview, int D,
+                             int K, int64_t* out_idx, float* out_score, void* workspace,
+                             size_t workspace_bytes, fr_stream_t stream);
 /* f32 -> fp8 e4m3 row conversion (x * FR_F8_SCALE, round to nearest even, n % 4 == 0) */
 int fr_f32_to_f8(const float* x, void* out, int64_t n, fr_stream_t stream);
 /* f32 -> f16 row conversion for building the device-resident gallery (infrenceServer.py:271) */
@@ -107,6 +126,12 @@ int fr_match_decide(const int64_t* idx, const float* score, int F, float thr, fl
 int fr_match_pack_candidates(const int64_t* idx, const float* score, int n, int32_t* cand, fr_stream_t stream);
 int fr_match_reduce_shards(const int32_t* cand_all, int R, int n, int q0, int F, int64_t* out_idx,
                            float* out_score, fr_stream_t stream);
+/*      Top-K form: every shard contributes its K best per query slot (fr_gallery_topk_f32 with row_offset);
+ *      fr_match_pack_candidates packs the flat n*K list unchanged, so cand_all is int32 [R][n][K][3].  The reduce
+ *      writes, for queries [q0, q0+F), the K best of the R lists under the same total order (score descending, global
+ *      row ascending) to out_idx / out_score [F][K]; a row < 0 is an empty slot, empty output slots are (-1, -1.0). */
+int fr_match_reduce_shards_topk(const int32_t* cand_all, int R, int n, int K, int q0, int F,
+                                int64_t* out_idx, float* out_score, fr_stream_t stream);
 /*      Exchange buffers of the same step: send f32 [q_max+1][D] = the rank's F unit query rows, zero rows up to q_max,
  *      and one trailing row whose first element is F (the face count rides in the one all-gather); after the gather
  *      (f32 [R][q_max+1][D]) counts[r] = that element of rank r's block.  The scan then walks the gathered buffer in
