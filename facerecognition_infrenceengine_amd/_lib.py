@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfrhip.so")
 
 _lock = threading.Lock()
 _lib = None
-ABI_VERSION = 103          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 104          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
 
 
 class FrError(RuntimeError):
@@ -46,10 +46,11 @@ class RolePtr(C.c_void_p):
 
 
 class PnetLevel(C.Structure):
-    """One pyramid level of fr_pnet_finish_levels (include/frhip.h fr_pnet_level)."""
+    """One pyramid level of fr_pnet_finish_levels / fr_pnet_pyramid_* (include/frhip.h fr_pnet_level)."""
     _fields_ = [("x1", C.c_void_p), ("head", C.c_void_p), ("workspace", C.c_void_p), ("H1", C.c_int), ("W1", C.c_int),
                 ("scale", C.c_float), ("boxes", C.c_void_p), ("scores", C.c_void_p), ("regs", C.c_void_p),
-                ("counts", C.c_void_p), ("block_counts", C.c_void_p)]
+                ("counts", C.c_void_p), ("block_counts", C.c_void_p),
+                ("x1s", C.c_void_p), ("hs", C.c_int), ("ws", C.c_int), ("f16", C.c_int)]      # the fr_pnet_pyramid_* launches
 
 
 class Call(C.Structure):
@@ -133,6 +134,9 @@ SIGNATURES = {
     "fr_pnet_band_tiles_count": (_Z, [_I, _I, _I]),
     "fr_pnet_band_tiles": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "fr_pnet_finish_levels": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P, _P]),
+    "fr_pnet_pyramid_conv1": (_I, [_I, _P, _I, _I, _I, C.POINTER(PnetLevel), _I, _P, _P, _P, _P, _P, _I, _P]),
+    "fr_pnet_pyramid_p23": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P]),
+    "fr_pnet_pyramid_band_tiles": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P]),
     "fr_pnet_candidates": (_I, [_P, _I, _I, _I, _F, _F, _I, _P, _P, _P, _P, _P, _P, _P, _F, _P]),
     "fr_sort_nms": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _I, _P]),
     "fr_box_refine": (_I, [_P, _P, _I, _P, _I, _I, _I, _P]),

@@ -39,6 +39,7 @@ constexpr int P1_TW = 64, P1_IW = P1_TW + 2;
 // against 577 / 266 us unrolled - no clear gain, so the loop stays unrolled.
 constexpr int P1_OCC = 3;
 constexpr int P1_CTU = 4;
+constexpr int P1_LEVEL_SHIFT = 27, P1_TILE_MASK = (1 << P1_LEVEL_SHIFT) - 1;     // LIST entries: level << 27 | tile (level 0 in a per-level list)
 
 __device__ __forceinline__ float dpp_xor1(float v) {        // value of lane ^ 1 (quad_perm [1,0,3,2])
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));
@@ -70,8 +71,10 @@ __device__ __forceinline__ float vmax(float x, float y, float pinf) { return __b
 // cycles, and a 4x4x1 MFMA holds the SIMD's vector issue for its whole 8 cycles.  The map differs from the f32 form's by the split format's error; the
 // cells whose decision that could touch are re-evaluated from an EXACT map: the f32 form below, run over the tiles such a cell's
 // window touches (LIST: tile numbers from fr_pnet_band_tiles).
-template <int RPW, int RPB, bool F16 = false, bool LIST = false>
-__global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_conv1_kernel(P1Args a) {
+// The body walks the items [item0, nitems) of its launch, at most RPB of them: a per-level launch hands block b the items
+// RPB b .. of the level (pnet_conv1_kernel), a pyramid-wide launch those of the level the block belongs to (pnet_conv1_levels).
+template <int RPW, int RPB, bool F16, bool LIST>
+__device__ __forceinline__ void pnet_conv1_body(const P1Args& a, const int item0, const int nitems) {
     constexpr int TH = 4 * RPW, IH = TH + 2, NPX = IH * P1_IW;
     constexpr int NPF = (NPX + 255) / 256;
     constexpr int NTAB = IH + P1_IW;
@@ -112,9 +115,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
     }
 
     const int per_img = a.regions_x * a.regions_y;
-    const int nitems = LIST ? min(*a.list_count, a.list_cap) : per_img * a.B;      // LIST: positions of the tile list
-    const int item0 = blockIdx.x * RPB;
-    auto tile_of = [&](int item) { return LIST ? a.list[item] : item; };
+    auto tile_of = [&](int item) { return LIST ? a.list[item] & P1_TILE_MASK : item; };      // LIST: items are positions of the tile list
     const float ryr = (float)a.FH / (float)a.H, rxr = (float)a.FW / (float)a.W;
     const int frame_bytes = a.FH * a.FW * 3;
 
@@ -497,12 +498,49 @@ __global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_c
 }
 
 template <int RPW, int RPB, bool F16 = false, bool LIST = false>
+__global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_conv1_kernel(P1Args a) {
+    const int nitems = LIST ? min(*a.list_count, a.list_cap) : a.regions_x * a.regions_y * a.B;
+    pnet_conv1_body<RPW, RPB, F16, LIST>(a, blockIdx.x * RPB, nitems);
+}
+
+// ALL pyramid levels of a batch in one launch: a block finds its level in a table in the kernel arguments (<= 16 entries,
+// block-uniform) and runs the per-level kernel's body with that level's geometry and maps - a tile is computed by the
+// instructions that compute it in a launch of its own.  Levels are laid out largest first, so the blocks of the small levels
+// fill the tail of the large ones instead of each level draining 256 CUs on its own.  Level l's blocks walk rpb[l] (<= RPB)
+// tiles each.  LIST: item i of the tile list is (level << 27 | tile of that level) and one block computes one item.
+#define P1_MAXL 16
+struct P1Levels {
+    float* y[P1_MAXL]; unsigned char* y_split[P1_MAXL];
+    int H[P1_MAXL], W[P1_MAXL], rpb[P1_MAXL], first[P1_MAXL + 1];      // first[l]: the level's first block
+    int nlevels;
+};
+template <int RPW, int RPB, bool F16 = false, bool LIST = false>
+__global__ __launch_bounds__(256, RPW == 4 ? (F16 ? P1_OCC : 3) : 6) void pnet_conv1_levels(P1Args a, P1Levels t) {
+    int l = 0, item0 = blockIdx.x, nitems = 0;
+    if constexpr (LIST) {
+        if (item0 >= min(*a.list_count, a.list_cap)) return;
+        l = min((int)((unsigned)a.list[item0] >> P1_LEVEL_SHIFT), t.nlevels - 1);
+        nitems = item0 + 1;
+    } else {
+        while (l + 1 < t.nlevels && (int)blockIdx.x >= t.first[l + 1]) ++l;
+    }
+    a.H = t.H[l]; a.W = t.W[l]; a.y = t.y[l]; a.y_split = t.y_split[l];
+    a.Ho = a.H - 2; a.Wo = a.W - 2; a.Hp = (a.Ho + 1) / 2; a.Wp = (a.Wo + 1) / 2;
+    a.regions_x = (a.Wo + P1_TW - 1) / P1_TW; a.regions_y = (a.Ho + 4 * RPW - 1) / (4 * RPW);
+    if constexpr (!LIST) {
+        item0 = ((int)blockIdx.x - t.first[l]) * t.rpb[l];
+        nitems = min(a.regions_x * a.regions_y * a.B, item0 + t.rpb[l]);
+    }
+    pnet_conv1_body<RPW, RPB, F16, LIST>(a, item0, nitems);
+}
+
+template <int RPW, int RPB, bool F16 = false, bool LIST = false>
 int launch_p1(P1Args a, hipStream_t s) {
     constexpr int TH = 4 * RPW;
     a.regions_x = (a.Wo + P1_TW - 1) / P1_TW;
     a.regions_y = (a.Ho + TH - 1) / TH;
     const int64_t nitems = LIST ? a.list_cap : (int64_t)a.regions_x * a.regions_y * a.B;
-    if (nitems >= (1ll << 31)) return FR_E_INVALID;
+    if (nitems >= (LIST ? 1ll << P1_LEVEL_SHIFT : 1ll << 31)) return FR_E_INVALID;
     pnet_conv1_kernel<RPW, RPB, F16, LIST><<<(unsigned)((nitems + RPB - 1) / RPB), 256, 0, s>>>(a);
     return FR_OK;
 }
@@ -544,5 +582,60 @@ extern "C" int fr_pnet_conv1_band(int mode, const uint8_t* frames, int B, int FH
     } else { FR_REQUIRE(false, "fr_pnet_conv1_band: mode must be 0 or 1"); }
     if (rc != FR_OK) { fr_set_error("fr_pnet_conv1_band: too many tiles"); return rc; }
     FR_CHECK_LAUNCH("pnet_conv1_kernel (band)");
+    return FR_OK;
+}
+
+// The same launches for ALL pyramid levels of a batch (the batch path's launch plan: mtcnn.py detect_batch).  A level entry
+// carries its size (hs, ws), its maps (x1 f32, x1s split) and which form computes it (f16).
+//   mode 0: the maps.  One launch of the f16 form over the levels with f16 != 0 (split map only), one of the f32 form over
+//           the others (f32 map + split map); tiles of 16 x 64 conv pixels on every level.
+//   mode 1: the exact f32 form over the tile list of fr_pnet_pyramid_band_tiles (entries level << 27 | tile): writes x1 of
+//           the f16 levels inside those tiles only.
+extern "C" int fr_pnet_pyramid_conv1(int mode, const uint8_t* frames, int B, int FH, int FW, const fr_pnet_level* levels, int nlevels,
+                                     const float* w, const float* bias, const float* slope, const int32_t* list,
+                                     const int32_t* list_count, int list_cap, fr_stream_t stream) {
+    FR_REQUIRE(frames && w && bias && slope && levels && B > 0 && FH > 0 && FW > 0 && nlevels > 0 && nlevels <= P1_MAXL,
+               "fr_pnet_pyramid_conv1: bad argument (1 .. %d levels)", P1_MAXL);
+    FR_REQUIRE(mode == 0 || mode == 1, "fr_pnet_pyramid_conv1: mode must be 0 or 1");
+    for (int l = 0; l < nlevels; ++l) {
+        const fr_pnet_level& L = levels[l];
+        FR_REQUIRE(L.x1 && L.x1s && L.hs >= 3 && L.ws >= 3 && L.H1 == (L.hs - 1) / 2 && L.W1 == (L.ws - 1) / 2,
+                   "fr_pnet_pyramid_conv1: level %d: bad entry", l);
+        FR_REQUIRE((int64_t)B * ((L.hs + 13) / 16) * ((L.ws + 61) / 64) < (1ll << P1_LEVEL_SHIFT), "fr_pnet_pyramid_conv1: level %d: too many tiles", l);
+    }
+    P1Args a{frames, B, FH, FW, 0, 0, w, bias, slope, nullptr, nullptr, 0, 0, 0, 0, 0, 0, list, list_count, list_cap};
+    hipStream_t s = fr_stream(stream);
+    if (mode == 1) {
+        FR_REQUIRE(list && list_count && list_cap > 0, "fr_pnet_pyramid_conv1: mode 1 needs a tile list");
+        P1Levels t{};
+        t.nlevels = nlevels;
+        for (int l = 0; l < nlevels; ++l) {          // indexed by the level number the list entries carry
+            t.y[l] = const_cast<float*>(levels[l].x1); t.y_split[l] = nullptr; t.H[l] = levels[l].hs; t.W[l] = levels[l].ws; t.rpb[l] = 1;
+        }
+        pnet_conv1_levels<4, 1, false, true><<<(unsigned)list_cap, 256, 0, s>>>(a, t);
+        FR_CHECK_LAUNCH("pnet_conv1_levels (tile list)");
+        return FR_OK;
+    }
+    for (int form = 1; form >= 0; --form) {          // the f16 levels (the large ones) first
+        P1Levels t{};
+        int64_t total = 0;
+        for (int l = 0; l < nlevels; ++l) {
+            const fr_pnet_level& L = levels[l];
+            if ((L.f16 != 0) != (form != 0)) continue;
+            const int k = t.nlevels++;
+            t.y[k] = form ? nullptr : const_cast<float*>(L.x1); t.y_split[k] = reinterpret_cast<unsigned char*>(L.x1s);
+            t.H[k] = L.hs; t.W[k] = L.ws;
+            const int64_t tiles = (int64_t)B * ((L.hs + 13) / 16) * ((L.ws + 61) / 64);
+            t.rpb[k] = tiles >= 4096 ? 8 : 1;         // the per-level launches' rule: blocks persistent over 8 tiles on the large levels
+            t.first[k] = (int)total;
+            total += (tiles + t.rpb[k] - 1) / t.rpb[k];
+        }
+        if (!t.nlevels) continue;
+        FR_REQUIRE(total < (1ll << 31), "fr_pnet_pyramid_conv1: too many tiles");
+        t.first[t.nlevels] = (int)total;
+        if (form) pnet_conv1_levels<4, 8, true><<<(unsigned)total, 256, 0, s>>>(a, t);
+        else pnet_conv1_levels<4, 8><<<(unsigned)total, 256, 0, s>>>(a, t);
+        FR_CHECK_LAUNCH("pnet_conv1_levels");
+    }
     return FR_OK;
 }

@@ -52,9 +52,10 @@ struct P23Args {
     int B, H1, W1, H3, W3, tiles_x, tiles_y, ntiles;
 };
 
-__global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
+// The body is block `vb` of a grid of `vgrid` blocks over the level's tiles: the whole launch (pnet23_split_f16), or the
+// level's share of a pyramid-wide one (pnet23_split_levels) - the level's workspace is laid out for `vgrid` blocks either way.
+__device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, const int vgrid, char* lds) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    extern __shared__ __attribute__((aligned(16))) char lds[];
     char* x1t = lds;                                        // hi plane [448 px][32 B] | lo plane [448][32] (432 used; 448 = 14 DMA pieces)
     char* x2t = x1t + 2 * P23_X1PL;                         // hi plane [340 px][32 B] | lo plane
     char* wf = x2t + 2 * P23_X2PL;                          // fragments: conv2 [5 ks][2 planes][64 lanes][16 B], conv3 [2 ct][5][2][64][16]
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
     for (int e = tid; e < 32; e += P23_NT) { cst[32 + e] = a.b3[e]; cst[64 + e] = a.s3[e] - 1.f; }
     for (int e = tid; e < 8; e += P23_NT) cst[96 + e] = e < 6 ? a.hb[e] : 0.f;
     if (tid == 0) *lcnt = 0;
-    int* const seg = a.list + (size_t)blockIdx.x * a.seg_cap;
+    int* const seg = a.list + (size_t)vb * a.seg_cap;
 
     // per-lane tap offsets of the 5 K steps (lane quarter fq < 2: tap 2ks, else tap 2ks+1; tap 9 does not exist: its
     // weights are zero, it reads tap 8's pixels)
@@ -131,8 +132,8 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
         const float w = fr < 6 ? a.hw[co * 6 + fr] : 0.f;
         split_f16(w, hwh, hwl, j);
     }
-    issue_window(blockIdx.x);
-    for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    issue_window(vb);
+    for (int tile = vb; tile < a.ntiles; tile += vgrid) {
         const int per = a.tiles_x * a.tiles_y;
         const int n = tile / per, rem = tile - n * per;
         const int ty0 = (rem / a.tiles_x) * P23_RH, tx0 = (rem % a.tiles_x) * P23_RW;
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
             }
         }
         __syncthreads();
-        if (tile + (int)gridDim.x < a.ntiles) issue_window(tile + gridDim.x);      // next window lands under conv3 + heads
+        if (tile + vgrid < a.ntiles) issue_window(tile + vgrid);      // next window lands under conv3 + heads
         // ---- conv3 on the 8 x 32 cells: 16 pixel tiles, 2 per wave, 2 cout tiles; then the heads
         {
             int pb[2];
@@ -271,8 +272,35 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
         }
     }
     __syncthreads();
-    if (tid == 0) a.counts[blockIdx.x] = *lcnt;
+    if (tid == 0) a.counts[vb] = *lcnt;
 #endif
+}
+
+__global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    pnet23_body(a, (int)blockIdx.x, (int)gridDim.x, lds);
+}
+
+// ALL pyramid levels of a batch in one launch (fr_pnet_pyramid_p23): level l owns the blocks first[l] .. first[l + 1] - the
+// grid its own launch would have had, so its workspace (dl | counts | list segments) is what fr_pnet_band_tiles and
+// fr_pnet_finish_levels expect - largest level first: the small levels' blocks start as the large ones' finish.
+#define P23_MAXL 16
+struct P23Levels {
+    const unsigned char* x1s[P23_MAXL]; float* head[P23_MAXL]; float* dl[P23_MAXL];
+    int H1[P23_MAXL], W1[P23_MAXL], seg_cap[P23_MAXL], first[P23_MAXL + 1];
+    int nlevels;
+};
+__global__ __launch_bounds__(P23_NT, 4) void pnet23_split_levels(P23Args a, P23Levels t) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    int l = 0;
+    while (l + 1 < t.nlevels && (int)blockIdx.x >= t.first[l + 1]) ++l;
+    a.H1 = t.H1[l]; a.W1 = t.W1[l]; a.H3 = a.H1 - 4; a.W3 = a.W1 - 4;
+    a.tiles_x = (a.W3 + P23_RW - 1) / P23_RW; a.tiles_y = (a.H3 + P23_RH - 1) / P23_RH;
+    a.ntiles = a.B * a.tiles_x * a.tiles_y;
+    a.x1s = t.x1s[l]; a.x1s_bytes = (unsigned)a.B * a.H1 * a.W1 * 64; a.head = t.head[l];
+    a.dl = t.dl[l]; a.counts = reinterpret_cast<int*>(a.dl + (size_t)a.B * a.H3 * a.W3); a.list = a.counts + 512;
+    a.seg_cap = t.seg_cap[l];
+    pnet23_body(a, (int)blockIdx.x - t.first[l], t.first[l + 1] - t.first[l], lds);
 }
 
 // ---------------------------------------------------------------- exact f32 re-evaluation of the cells that matter
@@ -567,5 +595,102 @@ extern "C" int fr_pnet_band_tiles(const void* workspace, int B, int H1, int W1, 
     if (hipMemsetAsync(tbuf, 0, (1 + (ntile + 31) / 32) * sizeof(int32_t), s) != hipSuccess) { fr_set_error("fr_pnet_band_tiles: memset failed"); return FR_E_LAUNCH; }
     pnet_band_tiles_kernel<<<grid, 256, 0, s>>>(counts + 512, counts, seg_cap, H1 - 4, W1 - 4, regions_x, regions_y, tbuf, tiles);
     FR_CHECK_LAUNCH("pnet_band_tiles_kernel");
+    return FR_OK;
+}
+
+// ---------------------------------------------------------------- the pyramid-wide launches (the batch path's launch plan)
+// conv2 / conv3 / heads of every level in ONE launch; the exact pass is always deferred to fr_pnet_finish_levels.  A level's
+// workspace is that of its own fr_pnet23_split_f16 call (fr_pnet23_workspace_bytes).
+extern "C" int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
+                                   const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                                   const float* hb, int all_heads, float refine_logit_thr, float refine_band_hi, fr_stream_t stream) {
+    FR_REQUIRE(levels && nlevels > 0 && nlevels <= P23_MAXL && nframes > 0, "fr_pnet_pyramid_p23: 1 .. %d levels", P23_MAXL);
+    FR_REQUIRE(w2 && b2 && s2 && w3 && b3 && s3 && hw && hb, "fr_pnet_pyramid_p23: null pointer");
+    P23Levels t;
+    t.nlevels = nlevels;
+    long long total = 0;
+    for (int l = 0; l < nlevels; ++l) {
+        const fr_pnet_level& L = levels[l];
+        FR_REQUIRE(L.x1s && L.head && L.workspace && L.H1 >= 5 && L.W1 >= 5, "fr_pnet_pyramid_p23: level %d: bad entry", l);
+        FR_REQUIRE((int64_t)nframes * L.H1 * L.W1 * 64 < (1ll << 31), "fr_pnet_pyramid_p23: level %d: the split conv1 map must stay below 2 GiB", l);
+        long long ncell, nt; int grid, seg_cap;
+        p23_layout(nframes, L.H1, L.W1, ncell, nt, grid, seg_cap);
+        t.x1s[l] = reinterpret_cast<const unsigned char*>(L.x1s); t.head[l] = L.head; t.dl[l] = reinterpret_cast<float*>(L.workspace);
+        t.H1[l] = L.H1; t.W1[l] = L.W1; t.seg_cap[l] = seg_cap;
+        t.first[l] = (int)total;
+        total += grid;
+    }
+    t.first[nlevels] = (int)total;
+    P23Args a{};
+    a.w2 = w2; a.b2 = b2; a.s2 = s2; a.w3 = w3; a.b3 = b3; a.s3 = s3; a.hw = hw; a.hb = hb; a.all_heads = all_heads & 1;
+    a.logit_thr = refine_logit_thr; a.band_hi = refine_band_hi; a.B = nframes;
+    constexpr size_t lds = (size_t)2 * P23_X1PL + (size_t)2 * P23_X2PL + 30 * 1024 + 108 * 4;
+    static FrDevLatch latch;
+    if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_split_levels), lds, latch)) { fr_set_error("fr_pnet_pyramid_p23: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+    pnet23_split_levels<<<(unsigned)total, P23_NT, lds, fr_stream(stream)>>>(a, t);
+    FR_CHECK_LAUNCH("pnet23_split_levels");
+    return FR_OK;
+}
+
+// fr_pnet_band_tiles for every level whose conv1 ran in its f16 form, in one launch: tbuf = [count | level bitmaps one after the
+// other], ONE tile list with entries (level << 27 | tile) - what fr_pnet_pyramid_conv1 mode 1 walks.
+struct PBandLevels {
+    const int* counts[PREF_MAXL];
+    int seg_cap[PREF_MAXL], H1[PREF_MAXL], W1[PREF_MAXL], word0[PREF_MAXL], level[PREF_MAXL], first[PREF_MAXL + 1];
+    int nlevels;
+};
+__global__ __launch_bounds__(256) void pnet_band_tiles_levels(PBandLevels t, int32_t* __restrict__ tbuf, int32_t* __restrict__ tiles, int cap) {
+    int l = 0;
+    while (l + 1 < t.nlevels && (int)blockIdx.x >= t.first[l + 1]) ++l;
+    const int b = (int)blockIdx.x - t.first[l];
+    const int n_list = t.counts[l][b];
+    const int* lst = t.counts[l] + 512 + (size_t)b * t.seg_cap[l];
+    const int H3 = t.H1[l] - 4, W3 = t.W1[l] - 4, hw3 = H3 * W3;
+    const int regions_y = (t.H1[l] + 7) / 8, regions_x = (t.W1[l] + 31) / 32;
+    unsigned* bitmap = reinterpret_cast<unsigned*>(tbuf) + 1 + t.word0[l];
+    for (int i = threadIdx.x; i < n_list; i += 256) {
+        const int c = lst[i];
+        const int n = c / hw3, r = c - n * hw3, y = r / W3, x = r - y * W3;
+        const int ry0 = (2 * y) >> 4, ry1 = min((2 * y + 9) >> 4, regions_y - 1);
+        const int rx0 = (2 * x) >> 6, rx1 = min((2 * x + 9) >> 6, regions_x - 1);
+        for (int ry = ry0; ry <= ry1; ++ry)
+            for (int rx = rx0; rx <= rx1; ++rx) {
+                const int tl = (n * regions_y + ry) * regions_x + rx;
+                const unsigned bit = 1u << (tl & 31);
+                const unsigned old = atomicOr(bitmap + (tl >> 5), bit);
+                if (!(old & bit)) {
+                    const int at = atomicAdd(tbuf, 1);
+                    if (at < cap) tiles[at] = (t.level[l] << 27) | tl;
+                }
+            }
+    }
+}
+
+extern "C" int fr_pnet_pyramid_band_tiles(const fr_pnet_level* levels, int nlevels, int nframes, int32_t* tbuf, int32_t* tiles,
+                                          fr_stream_t stream) {
+    FR_REQUIRE(levels && nlevels > 0 && nlevels <= PREF_MAXL && nframes > 0 && tbuf && tiles, "fr_pnet_pyramid_band_tiles: bad argument");
+    PBandLevels t;
+    t.nlevels = 0;
+    long long blocks = 0, words = 0, cap = 0;
+    for (int l = 0; l < nlevels; ++l) {
+        const fr_pnet_level& L = levels[l];
+        if (!L.f16) continue;
+        FR_REQUIRE(L.workspace && L.H1 >= 5 && L.W1 >= 5, "fr_pnet_pyramid_band_tiles: level %d: bad entry", l);
+        long long ncell, nt; int grid, seg_cap;
+        p23_layout(nframes, L.H1, L.W1, ncell, nt, grid, seg_cap);
+        const long long ntile = (long long)fr_pnet_band_tiles_count(nframes, L.H1, L.W1);
+        FR_REQUIRE(ntile < (1ll << 27), "fr_pnet_pyramid_band_tiles: level %d: too many tiles", l);
+        const int k = t.nlevels++;
+        t.counts[k] = reinterpret_cast<const int*>(reinterpret_cast<const float*>(L.workspace) + ncell);
+        t.seg_cap[k] = seg_cap; t.H1[k] = L.H1; t.W1[k] = L.W1; t.word0[k] = (int)words; t.level[k] = l;
+        t.first[k] = (int)blocks;
+        blocks += grid; words += (ntile + 31) / 32; cap += ntile;
+    }
+    FR_REQUIRE(t.nlevels > 0 && cap < (1ll << 31), "fr_pnet_pyramid_band_tiles: no level in the f16 form");
+    t.first[t.nlevels] = (int)blocks;
+    hipStream_t s = fr_stream(stream);
+    if (hipMemsetAsync(tbuf, 0, (size_t)(1 + words) * sizeof(int32_t), s) != hipSuccess) { fr_set_error("fr_pnet_pyramid_band_tiles: memset failed"); return FR_E_LAUNCH; }
+    pnet_band_tiles_levels<<<(unsigned)blocks, 256, 0, s>>>(t, tbuf, tiles, (int)cap);
+    FR_CHECK_LAUNCH("pnet_band_tiles_levels");
     return FR_OK;
 }

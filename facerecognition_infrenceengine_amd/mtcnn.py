@@ -205,10 +205,17 @@ class MTCNNHIP:
         self.pnet_band = True
         self.split_pconv1 = True            # with pnet_band: conv1 on the f16 matrix cores too; the exact pass gets an exact f32 map
                                             # under its cells' windows from the f32 conv1 kernel run over just those tiles
-        self.split_pconv1_min_px = 100000   # ... on levels whose conv1 map has at least this many pixels (the level pays four more
-                                            # small launches for it.  64 x 1080p, detector alone, by the number of levels that take it:
-                                            # 0: 4.74 ms, 1: 4.65, 2: 4.68, 3: 4.71, 4: 4.75, 6: 4.91, all 12: 5.26 - level 0 of a 1080p
-                                            # pyramid (186 k pixels), levels 0 - 2 of a 4K one; profiles/r05_detector_crossover.txt)
+        self.split_pconv1_min_px = 10000    # ... on levels whose conv1 map has at least this many pixels.  The exact tiles of ALL such
+                                            # levels share one list and one launch (pyramid_launch).  64 x 1080p, detector alone, by the
+                                            # number of levels that take it: 0: 5.01 ms, 1: 4.95, 2: 4.89, 3: 4.86, 4: 4.89, 5: 4.83, 6: 4.83,
+                                            # 7: 4.87, 9: 4.84, all 12: 4.82 (profiles/pnet_pyramid_ab.txt; a second box orders them otherwise)
+                                            # - flat within +- 0.05 ms from three levels on: levels 0 - 4 of a 1080p pyramid (11.7 k pixels and
+                                            # more), 0 - 6 of a 4K one.  With a launch chain per level
+                                            # (pyramid_launch False) every such level pays four small launches of its own and one level was
+                                            # the best (profiles/r05_detector_crossover.txt)
+        self.pyramid_launch = True          # batches: every P-Net layer launched ONCE over the whole pyramid, on the caller's stream
+                                            # (_pnet_pyramid); False: the per-level launches (pnet_level) dealt over the level streams
+        self.level_tensors = None           # tests: a list -> one dict per pyramid level of the last batch call (its maps, heads, workspace)
         self.refined_cells = None           # optional device int32[1]: cells re-evaluated exactly (diagnostics)
         self.p23_all_heads = False          # True: the fused kernel also writes the approximate heads of the cells it rules out
         self.use_sequence = True            # eager single-frame calls of a known frame shape replay a recorded C call list (fr_detect_sequence)
@@ -405,6 +412,8 @@ class MTCNNHIP:
                 self._dl = (wsp, lt - self.refine_margin)
                 self._tls.level_done = True
                 self._tls.keep = (x, xs, head, wsp, tbuf, tiles, bc)      # alive until the stream has been joined (detect_batch)
+                if self.level_tensors is not None:
+                    self.level_tensors.append(dict(h=h, w=w, f16=True, x=x, xs=xs, head=head, wsp=wsp, tbuf=tbuf, tiles=tiles))
                 return head, h - 4, w - 4
             x, h, w = self._dconv(None, self.p1, N, hs, ws, frames=frames, y_split=xs)
             head = self._f32(N, h - 4, w - 4, 6)
@@ -414,6 +423,8 @@ class MTCNNHIP:
                                          lt - self.refine_margin, lt + self.refine_margin if band else float("-inf"),
                                          _lib.ptr(self.refined_cells), _lib.ptr(ws), ws.numel() * 4, self._s)
             self._dl = (ws, math.log(t0 / (1.0 - t0)) - self.refine_margin)     # pre-filter for fr_pnet_candidates
+            if self.level_tensors is not None:
+                self.level_tensors.append(dict(h=h, w=w, f16=False, x=x, xs=xs, head=head, wsp=ws))
             return head, h - 4, w - 4
         # A level too large for 32-bit offsets into the split map (detect_batch cuts batches so that this does not happen; what is
         # left is a single frame beyond ~ 8K x 16K): the three P-Net layers as generic f32 launches.  Same results, slower - said aloud.
@@ -428,6 +439,58 @@ class MTCNNHIP:
         x, h, w = self._dconv(x, self.p2, N, h, w)
         head, h, w = self._dconv(x, self.p3, N, h, w)
         return head, h, w
+
+    def _pyramid_levels(self, N, H, W, scales):
+        """(hs, ws, h, w) of every pyramid level: the level's size and its conv1 map's."""
+        out = []
+        for s in scales:
+            hs, ws = int(math.ceil(H * s)), int(math.ceil(W * s))
+            out.append((hs, ws) + tuple(self.p1.out_hw(hs, ws)))
+        return out
+
+    def _pnet_pyramid(self, frames, scales, geo, cand):
+        """The P-Net of ALL pyramid levels of a batch with every layer launched once, on the current stream
+        (fr_pnet_pyramid_*: a block finds its level in a table, largest level first): conv1 (its f16 form over the levels
+        ``split_pconv1`` selects, its f32 form over the rest) -> conv2/3/heads -> the exact conv1 tiles under the band cells of
+        the f16 levels -> the exact pass + the candidates of every level.  The values are those of ``pnet_level`` per level, bit
+        for bit; twelve levels are 9 launches instead of 64.  cand: (thr, cap, boxes, scores, regs, counts) with a leading level axis."""
+        N, H, W, _ = frames.shape
+        lib, p1, path, nlev = self.lib, self.p1, self._tls.path, len(scales)
+        t0, cap, lb, ls, lr, lc = cand
+        lt = math.log(t0 / (1.0 - t0))
+        band = self.pnet_band
+        lv = (_lib.PnetLevel * nlev)()
+        keep, ntile, words = [], 0, 0
+        for li, (s, (hs, ws, h, w)) in enumerate(zip(scales, geo)):
+            f16 = bool(band and self.split_pconv1 and h * w >= self.split_pconv1_min_px)
+            xs = self._new((N, h, w, 64), torch.uint8)     # split-f16 copy of conv1's map
+            x = self._f32(N, h, w, 12)                     # f16 levels: SPARSE, written inside the listed tiles only (see pnet_level)
+            head = self._f32(N, h - 4, w - 4, 6)
+            wsp = self._new((lib.fr_pnet23_workspace_bytes(N, h, w) // 4,), torch.float32)
+            bc = self._i32(N * (-(-(h - 4) * (w - 4) // 256)))
+            lv[li] = _lib.PnetLevel(x.data_ptr(), head.data_ptr(), wsp.data_ptr(), h, w, float(s), lb[li].data_ptr(), ls[li].data_ptr(),
+                                    lr[li].data_ptr(), lc[li].data_ptr(), bc.data_ptr(), xs.data_ptr(), hs, ws, int(f16))
+            keep.append(dict(h=h, w=w, f16=f16, x=x, xs=xs, head=head, wsp=wsp, bc=bc))
+            if f16:
+                nt = lib.fr_pnet_band_tiles_count(N, h, w)
+                ntile, words = ntile + nt, words + (nt + 31) // 32
+                path["pconv1_mfma_levels"].append((h, w))
+        path["fused_levels"] += nlev
+        path["band_levels"] += nlev if band else 0
+        p23 = [_lib.ptr(t) for t in self._p23]
+        lib.fr_pnet_pyramid_conv1(0, self._fptr(frames), N, H, W, lv, nlev, _lib.ptr(p1.w), _lib.ptr(p1.b), _lib.ptr(p1.slope),
+                                  None, None, 0, self._s)
+        lib.fr_pnet_pyramid_p23(lv, nlev, N, *p23, 1 if self.p23_all_heads else 0, lt - self.refine_margin,
+                                lt + self.refine_margin if band else float("-inf"), self._s)
+        if ntile:
+            tbuf, tiles = self._i32(1 + words), self._i32(ntile)
+            lib.fr_pnet_pyramid_band_tiles(lv, nlev, N, _lib.ptr(tbuf), _lib.ptr(tiles), self._s)
+            lib.fr_pnet_pyramid_conv1(1, self._fptr(frames), N, H, W, lv, nlev, _lib.ptr(p1.w), _lib.ptr(p1.b), _lib.ptr(p1.slope),
+                                      _lib.ptr(tiles), _lib.ptr(tbuf), ntile, self._s)
+            keep[0].update(tbuf=tbuf, tiles=tiles)
+        lib.fr_pnet_finish_levels(lv, nlev, N, *p23, t0, cap, lt - self.refine_margin, _lib.ptr(self.refined_cells), self._s)
+        if self.level_tensors is not None:
+            self.level_tensors.extend(keep)
 
     def crop_conv1(self, net, frames, boxes, counts, cap):
         """frames u8 [N,H,W,3], boxes f32 [N,cap,4], counts i32 [N] -> the net's pooled conv1 map of every valid slot."""
@@ -548,7 +611,7 @@ class MTCNNHIP:
         """frames: uint8 [N,H,W,3] BGR device tensor (contiguous).
 
         level_streams: side HIP streams (1 or 2) the pyramid levels 1.. are dealt over; level 0 stays on the caller's
-        stream.  Default ``self.level_streams`` = 2 since round 4 (split-precision R-/O-Net, band-only exact P-Net pass: a 64 x 1080p
+        stream.  (Per-level launches only: a batch under ``pyramid_launch`` runs its whole P-Net on the caller's stream.)  Default ``self.level_streams`` = 2 since round 4 (split-precision R-/O-Net, band-only exact P-Net pass: a 64 x 1080p
         batch alone 5.30 ms with one side stream, 4.9 - 5.1 with two; inside the bench C2 24 150 -> 25 400 faces/s, C5 25 470 -> 27 070, C3
         20 780 -> 20 880: tools/ab_bench_knobs.sh).  Round 3 had measured: a 64 x 1080p batch ALONE (tools/bench_det_phases.py):
         one side stream + an NMS launch per level 6.80 ms, two side streams 6.47, one launch for the NMS of all levels
@@ -677,11 +740,25 @@ class MTCNNHIP:
                             lib.note(9, side.cuda_stream, rec_events[0].cuda_event)
             lb, ls, lr, lc = self._f32(nlev, N, cs, 4), self._f32(nlev, N, cs), self._f32(nlev, N, cs, 4), self._i32(nlev, N)
             kb, ks, ka, kc = self._f32(nlev, N, ksz, 4), self._f32(nlev, N, ksz), self._f32(nlev, N, ksz, 4), self._i32(nlev, N)
+            # A batch: every P-Net layer is ONE launch over the whole pyramid on the caller's stream - no per-level chains, no
+            # side streams (the small levels fill the tail of the large ones inside the launch).  Single frames, recorded call
+            # lists, captured graphs and traces keep the per-level launches below.
+            geo = self._pyramid_levels(N, H, W, scales)
+            pyramid = (self.pyramid_launch and batch and trace is None and self.fused_pnet
+                       and all(N * h * w * 64 < 2 ** 31 for _, _, h, w in geo))
+            if self.level_tensors is not None:
+                del self.level_tensors[:]
+            if pyramid:
+                self._pnet_pyramid(frames, scales, geo, (t0, cs, lb, ls, lr, lc))
+                if not self.merged_level_nms:
+                    for li in range(nlev):
+                        self._nms(lb[li], ls[li], lr[li], 4, lc[li], N, 1, cs, 0, 0.5, 0, ksz, out=(kb[li], ks[li], ka[li], kc[li]))
+                solo = True                         # no level stream was used: nothing to fork, nothing to join
             if not solo:
                 for side in sides:
                     side.wait_stream(main)
             keep = []
-            for li, s in enumerate(scales):
+            for li, s in ([] if pyramid else enumerate(scales)):
                 side = sides[(li - 1) % len(sides)] if li else sides[0]
                 with (contextlib.nullcontext() if solo else torch.cuda.stream(main if li == 0 else side)):
                     if not solo:
@@ -724,6 +801,8 @@ class MTCNNHIP:
                     t.record_stream(main)
             keep = None                                         # (hundreds of MB at level 0 of 64 x 1080p: back to the allocator now)
             self._mark("pnet")
+            if self.level_tensors is not None:
+                self.level_tensors.append(dict(cand=(lb, ls, lr, lc)))      # the candidate lists [level, frame, slot]
             if few or self.merged_level_nms:
                 self._nms(lb, ls, lr, 4, lc, nlev * N, 1, cs, 0, 0.5, 0, ksz, out=(kb, ks, ka, kc))
             # cross-level NMS 0.7 -> cap_p

@@ -32,9 +32,9 @@ typedef void* fr_stream_t;
 
 /* Version of THIS header's ABI: bumped whenever a signature or an argument struct changes shape (101: fr_conv_args gained
  * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads; 103: the fr_gallery_topk_* / fr_match_reduce_shards_topk
- * entries).  fr_version() returns the value the library was built
+ * entries; 104: fr_pnet_level gained x1s / hs / ws / f16, the fr_pnet_pyramid_* entries).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
-#define FR_ABI_VERSION 103
+#define FR_ABI_VERSION 104
 int fr_version(void);
 const char* fr_last_error_string(void);
 /* number of visible HIP devices (<=0: none); does not create a context on any device */
@@ -483,10 +483,30 @@ typedef struct {
     const float* x1; float* head; void* workspace;
     int H1, W1; float scale;
     float* boxes; float* scores; float* regs; int32_t* counts; int32_t* block_counts;
+    /* the pyramid descriptor of the fr_pnet_pyramid_* launches (fr_pnet_finish_levels does not read these) */
+    void* x1s;            /* the split conv1 map [nframes, H1, W1, 64 B] */
+    int hs, ws;           /* the level's size (the frame is resized to it inside conv1's tile load) */
+    int f16;              /* != 0: conv1 in its f16 form (split map only) + exact f32 tiles under the band cells' windows */
 } fr_pnet_level;
 int fr_pnet_finish_levels(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
                           const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
                           const float* hb, float thr, int cap, float dl_min, int32_t* refined_count, fr_stream_t stream);
+/* The P-Net of a whole pyramid with each layer launched ONCE (batches): a block of a launch finds its level in a table built
+ * from `levels` (largest level first) and runs what the level's own launch would have run - every value is bit for bit that of
+ * the per-level calls above.  Every entry carries x1, x1s, hs, ws, H1 = (hs - 1) / 2, W1 = (ws - 1) / 2, head and the level's own
+ * workspace (fr_pnet23_workspace_bytes).  Call order: fr_pnet_pyramid_conv1 mode 0 (the f16 form over the levels with f16 != 0 -
+ * split map only - and the f32 form over the others: x1 and x1s), fr_pnet_pyramid_p23 (fr_pnet23_split_f16 of every level, the
+ * exact pass deferred), then - when some level has f16 != 0 - fr_pnet_pyramid_band_tiles (tbuf: int32 [1 + sum over those levels
+ * of ceil(fr_pnet_band_tiles_count / 32)] = [count | bitmaps], zeroed here; tiles: int32 [sum of fr_pnet_band_tiles_count],
+ * entries level << 27 | tile) and fr_pnet_pyramid_conv1 mode 1 (list = tiles, list_count = tbuf, list_cap = the capacity of
+ * `tiles`: the exact f32 form over those tiles, x1 of the f16 levels is written inside them only), and fr_pnet_finish_levels. */
+int fr_pnet_pyramid_conv1(int mode, const uint8_t* frames, int B, int FH, int FW, const fr_pnet_level* levels, int nlevels,
+                          const float* w, const float* bias, const float* slope, const int32_t* list, const int32_t* list_count,
+                          int list_cap, fr_stream_t stream);
+int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2, const float* s2,
+                        const float* w3, const float* b3, const float* s3, const float* hw, const float* hb, int all_heads,
+                        float refine_logit_thr, float refine_band_hi, fr_stream_t stream);
+int fr_pnet_pyramid_band_tiles(const fr_pnet_level* levels, int nlevels, int nframes, int32_t* tbuf, int32_t* tiles, fr_stream_t stream);
 
 /* A recorded run of detector calls replayed by ONE C call (an eager single-frame get() is bound by the interpreter: ~50
  * ctypes calls per frame; FaceAnalysis.get, infrenceServer.py:528).  `fn` names the entry point, `a` carries its arguments
