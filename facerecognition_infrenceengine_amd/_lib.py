@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfrhip.so")
 
 _lock = threading.Lock()
 _lib = None
-ABI_VERSION = 104          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 105          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
 
 
 class FrError(RuntimeError):
@@ -51,6 +51,12 @@ class PnetLevel(C.Structure):
                 ("scale", C.c_float), ("boxes", C.c_void_p), ("scores", C.c_void_p), ("regs", C.c_void_p),
                 ("counts", C.c_void_p), ("block_counts", C.c_void_p),
                 ("x1s", C.c_void_p), ("hs", C.c_int), ("ws", C.c_int), ("f16", C.c_int)]      # the fr_pnet_pyramid_* launches
+
+
+class FrameRef(C.Structure):
+    """One frame of a ragged batch (include/frhip.h fr_frame_ref, 32 bytes): device pointer, size, size on the canvas."""
+    _fields_ = [("data", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("nh", C.c_int32), ("nw", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class Call(C.Structure):
@@ -115,6 +121,10 @@ SIGNATURES = {
     "fr_fc_reduce_l2norm": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "fr_warp_affine_5pt": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "fr_warp_affine_5pt_slots": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
+    "fr_warp_affine_5pt_refs": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "fr_warp_affine_5pt_slots_refs": (_I, [_P, _I, _P, _P, _I, _I, _P, _P]),
+    "fr_letterbox_u8": (_I, [_P, _I, _P, _I, _I, _P]),
+    "fr_detections_unscale": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "fr_pyramid_resize_norm": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "fr_dconv_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "fr_dconv_mfma_f32": (_I, [_I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _P, _P]),

@@ -122,10 +122,12 @@ class CameraManager:
                 logger.error("Error processing cameras %s: %s", [s for s, _ in batch], e)
 
     def process_batch(self, batch, company_id):
-        """batch: [(source, frame)].  Frames of one size go through the engine together; results leave in batch order."""
+        """batch: [(source, frame)].  Frames of one size go through the engine together - all of them in ONE call when the
+        processor takes mixed sizes (``accepts_mixed_sizes``: an engine with a ``det_size``); results leave in batch order."""
         by_shape = {}
+        mixed = getattr(self.processor, "accepts_mixed_sizes", False)
         for k, (_, f) in enumerate(batch):
-            by_shape.setdefault(tuple(f.shape), []).append(k)
+            by_shape.setdefault(None if mixed else tuple(f.shape), []).append(k)
         results = [None] * len(batch)
         for ks in by_shape.values():
             res = self.processor.recognize_batch([batch[k][1] for k in ks], company_id)

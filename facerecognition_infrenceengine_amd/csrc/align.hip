@@ -9,7 +9,11 @@ __constant__ double ARC_DST[5][2] = {{38.2946, 51.6963}, {73.5318, 51.5014}, {56
                                      {41.5493, 92.3655}, {70.7299, 92.2041}};
 
 #define WARP_NB 7
-__global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict__ frames, int nframes, int H, int W,
+// REFS: the frames are entries of a device table (fr_frame_ref: frames of differing sizes), not slices of one [nframes,H,W,3]
+// tensor; a frame's pointer and size are then block-uniform loads and the arithmetic is the same.
+template <bool REFS>
+__global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict__ frames, const fr_frame_ref* __restrict__ refs,
+                                                       int nframes, int H, int W,
                                                        const float* __restrict__ kps,
                                                        const int32_t* __restrict__ frame_idx,
                                                        const int32_t* __restrict__ count,
@@ -48,8 +52,16 @@ __global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict
     }
     __syncthreads();
     const int fidx = valid ? (slot_counts ? f / slot_cap : frame_idx[f]) : 0;
-    const uint8_t* fr = frames + (int64_t)fidx * H * W * 3;
-    const long long lim = fidx == nframes - 1 ? (long long)H * W * 3 - 8 : (1ll << 62);     // last frame: never read past the buffer
+    const uint8_t* fr;
+    long long lim;               // the last offset an 8-byte load may start at
+    if constexpr (REFS) {        // independent allocations: every frame ends a buffer
+        const fr_frame_ref r = refs[min(max(fidx, 0), nframes - 1)];
+        fr = r.data; H = r.H; W = r.W;
+        lim = (long long)H * W * 3 - 8;
+    } else {
+        fr = frames + (int64_t)fidx * H * W * 3;
+        lim = fidx == nframes - 1 ? (long long)H * W * 3 - 8 : (1ll << 62);     // last frame: never read past the buffer
+    }
     half_t* o = out + (int64_t)f * size * size * 8;
     const int rows = (size + WARP_NB - 1) / WARP_NB;
     const int t_end = min((band + 1) * rows, size) * size;
@@ -66,7 +78,7 @@ __global__ __launch_bounds__(256) void warp_affine_5pt(const uint8_t* __restrict
             // the two columns of a source row are 6 adjacent bytes (BGR BGR): ONE unaligned 8-byte load per row when both
             // lie inside the frame (pulled back at the very end of the last frame's buffer), byte loads otherwise
             double pb[2][2][3];
-            const bool pair = x0 >= 0 && x0 + 1 < W;
+            const bool pair = x0 >= 0 && x0 + 1 < W && lim >= 0;      // (a frame below 8 bytes: byte loads)
 #pragma unroll
             for (int a = 0; a < 2; ++a) {
                 const long long yy = y0 + a;
@@ -117,7 +129,7 @@ extern "C" int fr_warp_affine_5pt(const uint8_t* frames, int nframes, int H, int
     if (F <= 0) return FR_OK;
     FR_REQUIRE(frames && kps && frame_idx && out_f16_nhwc8, "fr_warp_affine_5pt: null pointer");
     FR_REQUIRE(nframes > 0 && H > 0 && W > 0 && size > 0, "fr_warp_affine_5pt: bad size");
-    warp_affine_5pt<<<F * WARP_NB, 256, 0, fr_stream(stream)>>>(frames, nframes, H, W, kps, frame_idx, count, nullptr, 1, size,
+    warp_affine_5pt<false><<<F * WARP_NB, 256, 0, fr_stream(stream)>>>(frames, nullptr, nframes, H, W, kps, frame_idx, count, nullptr, 1, size,
                                                       reinterpret_cast<half_t*>(out_f16_nhwc8), out_u8_bgr, M_out);
     FR_CHECK_LAUNCH("warp_affine_5pt");
     return FR_OK;
@@ -130,8 +142,31 @@ extern "C" int fr_warp_affine_5pt_slots(const uint8_t* frames, int nframes, int 
                                         fr_stream_t stream) {
     FR_REQUIRE(frames && kps && counts && out_f16_nhwc8 && nframes > 0 && cap > 0 && H > 0 && W > 0 && size > 0,
                "fr_warp_affine_5pt_slots: bad argument");
-    warp_affine_5pt<<<nframes * cap * WARP_NB, 256, 0, fr_stream(stream)>>>(frames, nframes, H, W, kps, nullptr, nullptr, counts, cap, size,
+    warp_affine_5pt<false><<<nframes * cap * WARP_NB, 256, 0, fr_stream(stream)>>>(frames, nullptr, nframes, H, W, kps, nullptr, nullptr, counts, cap, size,
                                                                   reinterpret_cast<half_t*>(out_f16_nhwc8), nullptr, nullptr);
     FR_CHECK_LAUNCH("warp_affine_5pt");
+    return FR_OK;
+}
+
+// The same two forms over a table of frames of differing sizes (include/frhip.h fr_frame_ref).
+extern "C" int fr_warp_affine_5pt_refs(const fr_frame_ref* refs, int nframes, const float* kps, const int32_t* frame_idx,
+                                       const int32_t* count, int F, int size, void* out_f16_nhwc8, uint8_t* out_u8_bgr,
+                                       float* M_out, fr_stream_t stream) {
+    if (F <= 0) return FR_OK;
+    FR_REQUIRE(refs && kps && frame_idx && out_f16_nhwc8, "fr_warp_affine_5pt_refs: null pointer");
+    FR_REQUIRE(nframes > 0 && size > 0, "fr_warp_affine_5pt_refs: bad size");
+    warp_affine_5pt<true><<<F * WARP_NB, 256, 0, fr_stream(stream)>>>(nullptr, refs, nframes, 0, 0, kps, frame_idx, count, nullptr, 1, size,
+                                                            reinterpret_cast<half_t*>(out_f16_nhwc8), out_u8_bgr, M_out);
+    FR_CHECK_LAUNCH("warp_affine_5pt (refs)");
+    return FR_OK;
+}
+
+extern "C" int fr_warp_affine_5pt_slots_refs(const fr_frame_ref* refs, int nframes, const float* kps, const int32_t* counts,
+                                             int cap, int size, void* out_f16_nhwc8, fr_stream_t stream) {
+    FR_REQUIRE(refs && kps && counts && out_f16_nhwc8 && nframes > 0 && cap > 0 && size > 0,
+               "fr_warp_affine_5pt_slots_refs: bad argument");
+    warp_affine_5pt<true><<<nframes * cap * WARP_NB, 256, 0, fr_stream(stream)>>>(nullptr, refs, nframes, 0, 0, kps, nullptr, nullptr, counts, cap, size,
+                                                                        reinterpret_cast<half_t*>(out_f16_nhwc8), nullptr, nullptr);
+    FR_CHECK_LAUNCH("warp_affine_5pt (refs)");
     return FR_OK;
 }

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib, weights
+from .letterbox import check_det_size, frame_table
 
 
 class Face(dict):
@@ -35,6 +36,14 @@ class Face(dict):
 
 def _model_dir(name, root):
     return os.path.join(os.path.expanduser(root), "models", name)
+
+
+class _Ragged:
+    """A batch handed to the kernels as a frame table (include/frhip.h fr_frame_ref): frames of differing sizes, or a uniform
+    stack under ``det_size``.  table: device u8 [N*32]; det_scale: device f32 [N]; keep: what the table points into."""
+
+    def __init__(self, n, table, det_scale, keep):
+        self.n, self.table, self.det_scale, self.keep = n, table, det_scale, keep
 
 
 class FaceAnalysis:
@@ -58,6 +67,7 @@ class FaceAnalysis:
         self.det_kwargs = {k: kwargs[k] for k in ("minsize", "factor", "thresholds", "cap_scale", "keep_scale",
                                                   "cap_p", "cap_r", "cap_o") if k in kwargs}
         self.synthetic = None
+        self.det_size = None
 
     def _load_states(self):
         d = _model_dir(self.name, self.root)
@@ -96,11 +106,20 @@ class FaceAnalysis:
         return (rec or weights.synth_iresnet_state(self.arch), det or weights.synth_mtcnn_states())
 
     def prepare(self, ctx_id=0, det_thresh=None, det_size=None):
-        """``ctx_id`` = HIP device ordinal (infrenceServer.py:416).  ``det_size`` is accepted and
-        ignored (MTCNN runs the full pyramid of the frame)."""
+        """``ctx_id`` = HIP device ordinal (infrenceServer.py:416).
+
+        ``det_size=(dw, dh)`` (insightface's order, width first; the reference's ``prepare(ctx_id=0)`` means (640, 640)):
+        every frame is resized on the device to fit a dw x dh detection canvas (aspect kept, top-left, zero padded, bilinear
+        without antialiasing like ``cv2.resize``'s default: ``letterbox_geometry``, csrc/letterbox.hip), the detector runs on
+        the canvas, boxes and landmarks are divided by the frame's scale and alignment samples the ORIGINAL frame.
+        ``minsize`` and the pyramid then apply to CANVAS pixels: a 20-pixel minimum face on the 640 x 360 image of a 1080p
+        frame is 60 pixels in the frame.  Detector cost no longer grows with the camera's resolution, and frames of
+        differing sizes go through one call (``get_batch`` / ``detect_embed_*`` take a list of them).
+        ``det_size=None`` (default): MTCNN walks the full pyramid of the full frame, and a batch is frames of one size."""
         from .iresnet import IResNetHIP
         from .mtcnn import MTCNNHIP
         _lib.require_gpu()
+        self.det_size = check_det_size(det_size)
         self.device = torch.device(f"cuda:{max(int(ctx_id), 0)}")
         rec, det = self._load_states()
         self._det_states = det
@@ -117,17 +136,14 @@ class FaceAnalysis:
         activation scales).  Returns the number of convs switched."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
-        if not torch.is_tensor(frames):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        frames = frames.to(self.device).contiguous()
-        N, H, W, _ = frames.shape
+        frames = self._to_device(frames)
         with self._lock, torch.cuda.device(self.device):
-            boxes, scores, kps, counts = self.det.detect_batch(frames)
+            frames, src = self._source(frames)
+            N = src.n if src is not None else frames.shape[0]
+            boxes, scores, kps, counts = self._detect(frames, src)
             cap = boxes.shape[1]
-            kps = kps.contiguous()
             crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
-            self.lib.fr_warp_affine_5pt_slots(_lib.ptr(frames), N, H, W, _lib.ptr(kps), _lib.ptr(counts), cap,
-                                              112, _lib.ptr(crops), _lib.stream_ptr())
+            self._warp_slots(frames, src, kps, counts, cap, crops)
             valid = (torch.arange(cap, device=self.device)[None, :] < counts[:, None]).reshape(-1).nonzero().squeeze(1)
             if valid.numel() == 0:
                 raise _lib.FrError("calibrate_fp8: no face detected in the calibration frames")
@@ -135,32 +151,132 @@ class FaceAnalysis:
             self._graphs = {}                     # captured graphs hold the f16 launch sequence
         return n
 
-    def clone_with(self, **det_kwargs):
+    def clone_with(self, det_size="same", **det_kwargs):
         """A second engine on the same device that SHARES this one's embed network (weights resident once) and
-        has its own detector with other capacities / thresholds (e.g. ``cap_o=1`` for single-face frames)."""
+        has its own detector with other capacities / thresholds (e.g. ``cap_o=1`` for single-face frames).  It keeps this
+        engine's ``det_size`` unless one is given (``None``: no detection canvas)."""
         from .mtcnn import MTCNNHIP
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         other = FaceAnalysis(self.name, self.root, providers=self.providers, arch=self.arch)
         other.device, other.rec, other.lib, other.synthetic = self.device, self.rec, self.lib, self.synthetic
         other._det_states = self._det_states
+        other.det_size = self.det_size if isinstance(det_size, str) and det_size == "same" else check_det_size(det_size)
         other.det_kwargs = {**self.det_kwargs, **det_kwargs}
         other.det = MTCNNHIP(*self._det_states, device=self.device, **other.det_kwargs)
         other._use_graphs, other._graphs = False, {}
         other._shares_rec = self._shares_rec = True          # neither engine may free the shared network's plans
         return other
 
+    # ------------------------------------------------------------------ det_size / ragged batches
+    def _to_device(self, frames):
+        """host array(s) -> device tensor(s): a [N,H,W,3] array / tensor stays one tensor, a list stays a list"""
+        def one(f):
+            if not torch.is_tensor(f):
+                f = torch.from_numpy(np.ascontiguousarray(np.asarray(f)))
+            return f.to(self.device).contiguous()
+        return [one(f) for f in frames] if isinstance(frames, (list, tuple)) else one(frames)
+
+    def _source(self, frames, table=None, det_scale=None):
+        """What a pipeline call was given -> ``(frames, src)``.  src None: a uniform [N,H,W,3] stack and no ``det_size`` -
+        the kernels take (frames, N, H, W) as always.  Otherwise a ``_Ragged``: a list of [Hi,Wi,3] device frames or a
+        stack, as a frame table written on the host (no device work is waited for).  ``table`` / ``det_scale``: already
+        on the device (``RaggedIngest.upload``)."""
+        if table is not None:
+            if self.det_size is not None and det_scale is None:
+                raise ValueError("a frame table under det_size comes with its det_scale (RaggedIngest.det_scale)")
+            return frames, _Ragged(table.numel() // 32, table, det_scale, frames)
+        if isinstance(frames, (list, tuple)):
+            if not frames:
+                raise ValueError("no frames")
+            for f in frames:
+                if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
+                    raise ValueError("frames must be contiguous uint8 [H,W,3] BGR device tensors")
+            if self.det_size is None:
+                if any(f.shape != frames[0].shape for f in frames):
+                    raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
+                return torch.stack(list(frames)), None
+            ptrs, shapes = [f.data_ptr() for f in frames], [tuple(f.shape[:2]) for f in frames]
+        else:
+            if not (frames.dim() == 4 and frames.shape[3] == 3 and frames.dtype == torch.uint8):
+                raise ValueError("frames must be uint8 [N,H,W,3] BGR")
+            if self.det_size is None:
+                return frames, None
+            frames = frames.contiguous()
+            N, H, W, _ = frames.shape
+            ptrs, shapes = [frames.data_ptr() + i * H * W * 3 for i in range(N)], [(H, W)] * N
+        tab, scale = frame_table(ptrs, shapes, self.det_size)
+        # pinned staging from torch's caching host allocator (it holds a block back until the copy that read it is done):
+        # the two small copies are asynchronous and ordered on the current stream in front of the kernels that read them
+        table = torch.from_numpy(tab).pin_memory().to(self.device, non_blocking=True)
+        det_scale = torch.from_numpy(scale).pin_memory().to(self.device, non_blocking=True)
+        return frames, _Ragged(len(ptrs), table, det_scale, frames)
+
+    def _canvas(self, src):
+        dw, dh = self.det_size
+        canvas = torch.empty((src.n, dh, dw, 3), dtype=torch.uint8, device=self.device)
+        self.lib.fr_letterbox_u8(_lib.ptr(src.table), src.n, _lib.ptr(canvas), dh, dw, _lib.stream_ptr())
+        return canvas
+
+    def letterbox(self, frames):
+        """The detection canvases of ``frames`` ([N,H,W,3], or a list of [Hi,Wi,3] frames of any sizes; host arrays or
+        device tensors) under this engine's ``det_size``: ``(canvas u8 [N,dh,dw,3], det_scale f32 [N])``, device tensors.
+        Canvas coordinates divided by ``det_scale[f]`` are frame pixels."""
+        if self.det is None:
+            raise _lib.FrError("FaceAnalysis.prepare() has not been called")
+        if self.det_size is None:
+            raise ValueError("letterbox() needs prepare(det_size=(w, h))")
+        with torch.cuda.device(self.device):
+            frames, src = self._source(self._to_device(frames))
+            canvas = self._canvas(src)
+        return canvas, src.det_scale
+
+    def _detect(self, frames, src, contiguous_kps=True):
+        """The detector on the current stream -> boxes, scores, kps, counts in FRAME pixels.  Under ``det_size``: canvas,
+        cascade on the canvas, division by det_scale on the device - no host sync."""
+        if src is None or self.det_size is None:
+            if src is not None:
+                raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
+            boxes, scores, kps, counts = self.det.detect_batch(frames)
+            return boxes, scores, kps.contiguous() if contiguous_kps else kps, counts
+        with torch.cuda.device(self.device):
+            boxes, scores, kps, counts = self.det.detect_batch(self._canvas(src))
+            boxes, kps = boxes.contiguous(), kps.contiguous()
+            self.lib.fr_detections_unscale(_lib.ptr(boxes), _lib.ptr(kps), _lib.ptr(counts), _lib.ptr(src.det_scale),
+                                           src.n, boxes.shape[1], _lib.stream_ptr())
+        return boxes, scores, kps, counts
+
+    def _warp_slots(self, frames, src, kps, counts, cap, crops):
+        if src is None:
+            N, H, W, _ = frames.shape
+            self.lib.fr_warp_affine_5pt_slots(_lib.ptr(frames), N, H, W, _lib.ptr(kps), _lib.ptr(counts), cap, 112,
+                                              _lib.ptr(crops), _lib.stream_ptr())
+        else:
+            self.lib.fr_warp_affine_5pt_slots_refs(_lib.ptr(src.table), src.n, _lib.ptr(kps), _lib.ptr(counts), cap, 112,
+                                                   _lib.ptr(crops), _lib.stream_ptr())
+
+    def _warp_faces(self, frames, src, kps, frame_idx, F, crops):
+        if src is None:
+            N, H, W, _ = frames.shape
+            self.lib.fr_warp_affine_5pt(_lib.ptr(frames), N, H, W, _lib.ptr(kps), _lib.ptr(frame_idx), None,
+                                        F, 112, _lib.ptr(crops), None, None, _lib.stream_ptr())
+        else:
+            self.lib.fr_warp_affine_5pt_refs(_lib.ptr(src.table), src.n, _lib.ptr(kps), _lib.ptr(frame_idx), None,
+                                             F, 112, _lib.ptr(crops), None, None, _lib.stream_ptr())
+
     # ------------------------------------------------------------------ device-side pipeline
     def detect_embed_device(self, frames):
-        """frames: uint8 [N,H,W,3] BGR on the device.  One host sync (face counts).
+        """frames: uint8 [N,H,W,3] BGR on the device, or - with ``det_size`` - a list of [Hi,Wi,3] device frames of any
+        sizes.  One host sync (face counts).
 
         Returns dict of device tensors for the F detected faces (frame-major, descending score
         within a frame): frame_idx i32 [F], bbox f32 [F,4], kps f32 [F,5,2], det_score f32 [F],
         embedding f32 [F,512], normed_embedding f32 [F,512]; plus counts (host list)."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
-        N, H, W, _ = frames.shape
-        boxes, scores, kps, counts = self.det.detect_batch(frames)
+        frames, src = self._source(frames)
+        N = src.n if src is not None else frames.shape[0]
+        boxes, scores, kps, counts = self._detect(frames, src, contiguous_kps=False)
         cap = boxes.shape[1]
         cnt = counts.cpu()                                            # the one sync of the pipeline
         if N == 1:                                                    # a single frame: its valid slots are a prefix - views, no gathers
@@ -181,16 +297,17 @@ class FaceAnalysis:
         if F:
             with torch.cuda.device(self.device):
                 crops = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
-                self.lib.fr_warp_affine_5pt(_lib.ptr(frames), N, H, W, _lib.ptr(out["kps"]), _lib.ptr(frame_idx), None,
-                                            F, 112, _lib.ptr(crops), None, None, _lib.stream_ptr())
+                self._warp_faces(frames, src, out["kps"], frame_idx, F, crops)
                 emb, normed = self.rec.forward(crops)
         out["embedding"], out["normed_embedding"] = emb, normed
         return out
 
-    def detect_embed_slots(self, frames, det_stream=None, ready_event=None, compact_embed=False, crops_out=None):
+    def detect_embed_slots(self, frames, det_stream=None, ready_event=None, compact_embed=False, crops_out=None,
+                           table=None, det_scale=None):
         """Sync-free form for streaming/serving: every frame owns ``cap_o`` face slots.
 
-        frames: uint8 [N,H,W,3] BGR on the device.  Returns device tensors only (no host sync):
+        frames: uint8 [N,H,W,3] BGR on the device; with ``det_size`` also a list of [Hi,Wi,3] device frames of any sizes,
+        or the arena, ``table`` and ``det_scale`` of a ``RaggedIngest``.  Returns device tensors only (no host sync):
         counts i32 [N]; bbox f32 [N,cap,4]; kps f32 [N,cap,5,2]; det_score f32 [N,cap];
         embedding / normed_embedding f32 [N*cap,512] (rows of empty slots are meaningless: mask with counts).
 
@@ -209,20 +326,20 @@ class FaceAnalysis:
         returned dict holds the detector outputs, and the caller runs ``embed_slots`` over the whole buffer."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
-        N, H, W, _ = frames.shape
         cur = torch.cuda.current_stream(self.device)
         if ready_event is not None:
             (det_stream if det_stream is not None else cur).wait_event(ready_event)
         if det_stream is None:
-            boxes, scores, kps, counts = self.det.detect_batch(frames)
-            kps = kps.contiguous()
+            frames, src = self._source(frames, table, det_scale)
+            boxes, scores, kps, counts = self._detect(frames, src)
         else:
             with torch.cuda.stream(det_stream):
-                boxes, scores, kps, counts = self.det.detect_batch(frames)     # overlapped with the embedder
-                kps = kps.contiguous()
+                frames, src = self._source(frames, table, det_scale)           # (a table made here is uploaded on det_stream)
+                boxes, scores, kps, counts = self._detect(frames, src)         # overlapped with the embedder
             cur.wait_stream(det_stream)
-            for t in (boxes, scores, kps, counts):
+            for t in (boxes, scores, kps, counts) + ((src.table,) if src is not None and table is None else ()):
                 t.record_stream(cur)
+        N = src.n if src is not None else frames.shape[0]
         cap = boxes.shape[1]
         if compact_embed:
             cnt = counts.cpu()                                            # the extra sync
@@ -238,8 +355,7 @@ class FaceAnalysis:
                     # may be handed the same block before the kernel has read it
                     kps_sel = kps.reshape(-1, 5, 2)[sel].contiguous()
                     frame_idx = (sel // cap).to(torch.int32)
-                    self.lib.fr_warp_affine_5pt(_lib.ptr(frames), N, H, W, _lib.ptr(kps_sel), _lib.ptr(frame_idx), None,
-                                                F, 112, _lib.ptr(crops), None, None, _lib.stream_ptr())
+                    self._warp_faces(frames, src, kps_sel, frame_idx, F, crops)
                     e, nm = self.rec.forward(crops)
                     emb[sel], normed[sel] = e, nm
             return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
@@ -248,8 +364,7 @@ class FaceAnalysis:
             if crops_out is not None:                  # the caller embeds several calls' slots in ONE forward (embed_slots)
                 assert crops_out.shape == (N * cap, 112, 112, 8) and crops_out.dtype == torch.float16 and crops_out.is_contiguous()
             crops = crops_out if crops_out is not None else torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
-            self.lib.fr_warp_affine_5pt_slots(_lib.ptr(frames), N, H, W, _lib.ptr(kps), _lib.ptr(counts), cap, 112,
-                                              _lib.ptr(crops), _lib.stream_ptr())
+            self._warp_slots(frames, src, kps, counts, cap, crops)
             if crops_out is not None:
                 return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores}
             emb, normed = self.rec.forward(crops)
@@ -270,7 +385,8 @@ class FaceAnalysis:
     def enable_graphs(self, on=True):
         """Single-frame calls are launch-bound (~250 kernel launches for a 640x480 frame): with graphs on, ``get`` /
         ``get_batch`` capture the sync-free slot pipeline once per input shape into a HIP graph (pinned staging buffers
-        on both sides) and replay it.  Results are bit-identical to the eager path (same kernels, same order)."""
+        on both sides) and replay it.  Results are bit-identical to the eager path (same kernels, same order).
+        Not under ``det_size``: an engine with a detection canvas runs every call eagerly, graphs on or off."""
         self._use_graphs = bool(on)
         if not on:
             self._graphs = {}
@@ -287,24 +403,38 @@ class FaceAnalysis:
 
     # ------------------------------------------------------------------ reference-shaped API
     def get_batch(self, frames):
-        """list/array of same-sized BGR uint8 frames -> list (per frame) of lists of Face."""
-        arr = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames]) if not isinstance(frames, np.ndarray)
-                                   else frames)
+        """list/array of BGR uint8 frames -> list (per frame) of lists of Face.  The frames are of one size; under
+        ``det_size`` a list may mix sizes (bbox / kps are in each frame's own pixels)."""
+        if not isinstance(frames, np.ndarray):
+            frames = [np.ascontiguousarray(np.asarray(f)) for f in frames]
+            if any(f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 for f in frames):
+                raise ValueError("frames must be uint8 [H,W,3] BGR")
+            if len(frames) and any(f.shape != frames[0].shape for f in frames):
+                if self.det_size is None:
+                    raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
+                with self._lock:
+                    return self._faces_of(self.detect_embed_device(self._to_device(frames)))
+            frames = np.stack(frames)
+        arr = np.ascontiguousarray(frames)
         if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
             raise ValueError("frames must be uint8 [N,H,W,3] BGR")
-        if getattr(self, "_use_graphs", False):
+        if getattr(self, "_use_graphs", False) and self.det_size is None:
             with self._lock:
                 counts, host = self._graph_for(tuple(arr.shape)).run(arr)
             return _faces_from_slots(counts, host)
         with self._lock:
             dev = torch.from_numpy(arr).to(self.device)
-            r = self.detect_embed_device(dev)
-            # ONE device-to-host copy (and sync) for the five result tensors instead of five
-            F = r["bbox"].shape[0]
-            pack = torch.cat([r["bbox"].reshape(F, 4), r["kps"].reshape(F, 10), r["det_score"].reshape(F, 1),
-                              r["embedding"], r["normed_embedding"]], dim=1).cpu().numpy()
-            host = {"bbox": pack[:, 0:4], "kps": pack[:, 4:14].reshape(F, 5, 2), "det_score": pack[:, 14],
-                    "embedding": pack[:, 15:527], "normed_embedding": pack[:, 527:1039]}
+            return self._faces_of(self.detect_embed_device(dev))
+
+    @staticmethod
+    def _faces_of(r):
+        """``detect_embed_device``'s result -> per-frame lists of Face"""
+        # ONE device-to-host copy (and sync) for the five result tensors instead of five
+        F = r["bbox"].shape[0]
+        pack = torch.cat([r["bbox"].reshape(F, 4), r["kps"].reshape(F, 10), r["det_score"].reshape(F, 1),
+                          r["embedding"], r["normed_embedding"]], dim=1).cpu().numpy()
+        host = {"bbox": pack[:, 0:4], "kps": pack[:, 4:14].reshape(F, 5, 2), "det_score": pack[:, 14],
+                "embedding": pack[:, 15:527], "normed_embedding": pack[:, 527:1039]}
         res, i = [], 0
         for n in r["counts"]:
             faces = []

@@ -74,3 +74,64 @@ class FrameIngest:
         ev = torch.cuda.Event()
         ev.record(stream if stream is not None else torch.cuda.current_stream(self.device))
         self._busy[slot % self.depth] = ev
+
+
+class RaggedIngest:
+    """``FrameIngest`` for frames of DIFFERING sizes (cameras of several resolutions in one batch): keyed by the tuple of frame
+    shapes.  A slot is ONE pinned host arena holding the frames back to back at 16-byte-aligned offsets and a device arena
+    of the same layout: one H2D copy per batch, the same ``upload`` / ``release`` protocol.  The frame table the kernels
+    read (include/frhip.h fr_frame_ref: pointers into the slot's device arena, sizes, and - with ``det_size`` - the sizes on
+    the detection canvas) and ``det_scale`` depend on the shapes alone: they are written on the host and uploaded once,
+    here, so a batch adds no copy and no synchronisation for them."""
+
+    def __init__(self, shapes, det_size=None, device="cuda:0", depth=3):
+        from .letterbox import check_det_size, frame_table
+        _lib.require_gpu()
+        self.device = torch.device(device)
+        self.shapes = tuple((int(s[0]), int(s[1])) for s in shapes)
+        self.det_size, self.depth = check_det_size(det_size), int(depth)
+        self.offsets, off = [], 0
+        for h, w in self.shapes:
+            self.offsets.append(off)
+            off += (h * w * 3 + 15) // 16 * 16
+        self.nbytes = max(off, 16)
+        self._host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        self._dev = [torch.empty(self.nbytes, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
+        self._stream = torch.cuda.Stream(device=self.device)
+        self._busy = [None] * self.depth
+        self.tables = []
+        for d in self._dev:
+            tab, scale = frame_table([d.data_ptr() + o for o in self.offsets], self.shapes, self.det_size)
+            self.tables.append(torch.from_numpy(tab).to(self.device))
+        self.det_scale = torch.from_numpy(scale).to(self.device)
+        torch.cuda.synchronize(self.device)              # construction time: the tables are in place before the first upload
+
+    def host_frame(self, slot, index):
+        """NumPy view ``uint8 [H,W,3]`` of frame ``index`` in the slot's pinned arena: the capture side writes here."""
+        h, w = self.shapes[index]
+        o = self.offsets[index]
+        return self._host[slot % self.depth].numpy()[o:o + h * w * 3].reshape(h, w, 3)
+
+    def device_frame(self, slot, index):
+        """The same frame in the slot's device arena (a view)."""
+        h, w = self.shapes[index]
+        o = self.offsets[index]
+        return self._dev[slot % self.depth][o:o + h * w * 3].view(h, w, 3)
+
+    def upload(self, slot):
+        """Start the H2D copy of the slot's arena; returns (device arena, frame table on the device, event that fires when
+        the frames have landed).  The copy waits for the slot's previous consumer (see ``release``)."""
+        k = slot % self.depth
+        with torch.cuda.stream(self._stream):
+            if self._busy[k] is not None:
+                self._stream.wait_event(self._busy[k])
+            self._dev[k].copy_(self._host[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(self._stream)
+        return self._dev[k], self.tables[k], ev
+
+    def release(self, slot, stream=None):
+        """Mark the slot's device arena free once the work queued so far on ``stream`` (default: current) is done."""
+        ev = torch.cuda.Event()
+        ev.record(stream if stream is not None else torch.cuda.current_stream(self.device))
+        self._busy[slot % self.depth] = ev

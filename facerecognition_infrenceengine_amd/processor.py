@@ -300,14 +300,23 @@ class FaceRecognitionProcessor:
             out.append({"bbox": bbox[f], "det_score": float(det[f]), "candidates": cands})
         return out
 
+    @property
+    def accepts_mixed_sizes(self):
+        """True when ``recognize_batch`` takes frames of differing sizes in one call: the engine has a detection canvas
+        (``FaceAnalysis.prepare(det_size=...)``).  The camera batcher then stops grouping frames by shape."""
+        if self.face_detector is None:
+            self.initialize_detector()
+        return getattr(self.face_detector, "det_size", None) is not None
+
     def recognize_batch(self, frames, company_id):
-        """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of same-sized BGR uint8
-        frames (one per camera).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
+        """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
+        camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
+        in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
         copy stream -> detect -> align -> embed -> company view scan -> decision), one host synchronisation at the
         end.  Returns a list (per frame) of lists of the dicts ``recognize`` returns, or None when the company has
         no gallery (the reference returns the frame untouched then, infrenceServer.py:523-525)."""
         import torch
-        from .ingest import FrameIngest
+        from .ingest import FrameIngest, RaggedIngest
         if self.face_detector is None:
             self.initialize_detector()
         det = self.face_detector
@@ -317,22 +326,31 @@ class FaceRecognitionProcessor:
             return None
         arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
         n, (h, w) = len(arr), arr[0].shape[:2]
-        if any(a.shape != (h, w, 3) or a.dtype != np.uint8 for a in arr):
-            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size")
+        det_size = getattr(det, "det_size", None)
+        if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr) or \
+                (det_size is None and any(a.shape != (h, w, 3) for a in arr)):
+            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
         stages = self.__dict__.setdefault("_stages", {})
-        key = (n, h, w)
+        key = (n, h, w) if det_size is None else (tuple(a.shape[:2] for a in arr), det_size)
         if key not in stages:
             while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
                 stages.pop(next(iter(stages)))
-            stages[key] = [FrameIngest(n, h, w, det.device, depth=2), 0]
+            stages[key] = [FrameIngest(n, h, w, det.device, depth=2) if det_size is None else
+                           RaggedIngest(key[0], det_size, det.device, depth=2), 0]
         ring, turn = stages[key]
         stages[key][1] = turn + 1
         with det._lock, torch.cuda.device(det.device):
-            host = ring.host_buffer(turn)
-            for i, a in enumerate(arr):
-                host[i] = a
-            dev, ready = ring.upload(turn)
-            r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True)      # results go to the host anyway
+            if det_size is None:
+                host = ring.host_buffer(turn)
+                for i, a in enumerate(arr):
+                    host[i] = a
+                dev, ready = ring.upload(turn)
+                r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True)      # results go to the host anyway
+            else:                                         # one arena, one copy, one engine pass whatever the frames' sizes
+                for i, a in enumerate(arr):
+                    ring.host_frame(turn, i)[...] = a
+                dev, table, ready = ring.upload(turn)
+                r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, table=table, det_scale=ring.det_scale)
             ring.release(turn)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
                                                      r["normed_embedding"])

@@ -32,9 +32,10 @@ typedef void* fr_stream_t;
 
 /* Version of THIS header's ABI: bumped whenever a signature or an argument struct changes shape (101: fr_conv_args gained
  * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads; 103: the fr_gallery_topk_* / fr_match_reduce_shards_topk
- * entries; 104: fr_pnet_level gained x1s / hs / ws / f16, the fr_pnet_pyramid_* entries).  fr_version() returns the value the library was built
+ * entries; 104: fr_pnet_level gained x1s / hs / ws / f16, the fr_pnet_pyramid_* entries;
+ * 105: fr_frame_ref, fr_letterbox_u8, fr_detections_unscale, the fr_warp_affine_5pt*_refs entries).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
-#define FR_ABI_VERSION 104
+#define FR_ABI_VERSION 105
 int fr_version(void);
 const char* fr_last_error_string(void);
 /* number of visible HIP devices (<=0: none); does not create a context on any device */
@@ -305,6 +306,22 @@ int fr_warp_affine_5pt_slots(const uint8_t* frames, int nframes, int H, int W, c
                              const int32_t* counts, int cap, int size, void* out_f16_nhwc8,
                              fr_stream_t stream);
 
+/* Ragged batches: frames of differing sizes, each described by one 32-byte entry of a DEVICE table.  data: u8 [H,W,3] BGR
+ * (device memory, any byte alignment); nh x nw: the size the frame takes on a detection canvas (fr_letterbox_u8; the warps
+ * below do not read them).  Nothing outside [data, data + H*W*3) is read. */
+typedef struct {
+    const uint8_t* data;
+    int32_t H, W, nh, nw;
+    int32_t reserved[2];
+} fr_frame_ref;
+/* The two warps above over a frame table in place of (frames, nframes, H, W): frame_idx / the slot's frame number index
+ * `refs`.  Same kernel body, same arithmetic: a face gives the bits fr_warp_affine_5pt gives for its frame alone. */
+int fr_warp_affine_5pt_refs(const fr_frame_ref* refs, int nframes, const float* kps, const int32_t* frame_idx,
+                            const int32_t* count, int F, int size, void* out_f16_nhwc8, uint8_t* out_u8_bgr,
+                            float* M_out, fr_stream_t stream);
+int fr_warp_affine_5pt_slots_refs(const fr_frame_ref* refs, int nframes, const float* kps, const int32_t* counts,
+                                  int cap, int size, void* out_f16_nhwc8, fr_stream_t stream);
+
 /* --------------------------------------------------------------- detect ----
  * a-2  MTCNN cascade (detector half of FaceAnalysis.get, infrenceServer.py:528); the
  * conventions (resize, ordering, capacities) are those of oracle/detect.py. */
@@ -507,6 +524,19 @@ int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int nframes, c
                         const float* w3, const float* b3, const float* s3, const float* hw, const float* hb, int all_heads,
                         float refine_logit_thr, float refine_band_hi, fr_stream_t stream);
 int fr_pnet_pyramid_band_tiles(const fr_pnet_level* levels, int nlevels, int nframes, int32_t* tbuf, int32_t* tiles, fr_stream_t stream);
+
+/* det_size: the detection canvas of insightface's FaceAnalysis.prepare(det_size=(dw, dh)) (the reference's prepare(ctx_id=0)
+ * means 640 x 640, infrenceServer.py:416).  ONE launch for a ragged batch: frame f of `refs` is resized to refs[f].nh x
+ * refs[f].nw - the pyramid's bilinear resize (f32, half-pixel centres, edge clamp: oracle/detect.py resize_bilinear) of the
+ * BGR bytes, rounded floor(v + 0.5) and clamped to [0, 255] - and placed top-left on canvas[f] (u8 [nframes,dh,dw,3]); every
+ * other byte of the canvas is written 0 by the same launch.  nh == H and nw == W is an exact copy.  1 <= nh <= dh,
+ * 1 <= nw <= dw per entry (the host computes them: letterbox_geometry); entries outside that are clamped to the canvas.
+ * dw % 16 == 0 takes 16-byte canvas stores, any other width byte stores. */
+int fr_letterbox_u8(const fr_frame_ref* refs, int nframes, uint8_t* canvas, int dh, int dw, fr_stream_t stream);
+/* Detections of the canvas back to frame pixels, in place: every coordinate of boxes f32 [nframes,cap,4] and kps f32
+ * [nframes,cap,5,2] of the slots j < counts[f] is divided (IEEE f32) by det_scale[f]; other slots are left untouched. */
+int fr_detections_unscale(float* boxes, float* kps, const int32_t* counts, const float* det_scale, int nframes, int cap,
+                          fr_stream_t stream);
 
 /* A recorded run of detector calls replayed by ONE C call (an eager single-frame get() is bound by the interpreter: ~50
  * ctypes calls per frame; FaceAnalysis.get, infrenceServer.py:528).  `fn` names the entry point, `a` carries its arguments
