@@ -10,7 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libfrhip.so")
 
 _lock = threading.Lock()
 _lib = None
-ABI_VERSION = 105          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
+ABI_VERSION = 106          # include/frhip.h FR_ABI_VERSION this binding was written against (tests/test_abi.py compares)
 
 
 class FrError(RuntimeError):
@@ -86,6 +86,11 @@ SIGNATURES = {
     "fr_gallery_match_f16": (_I, [_P, _P, _P, _I, _L, _I, _L, _P, _P, _P, _Z, _P, _I, _P]),
     "fr_gallery_match_f8_workspace": (_Z, [_I, _L]),
     "fr_gallery_match_f8": (_I, [_P, _P, _P, _I, _L, _I, _L, _P, _P, _P, _Z, _P, _I, _P]),
+    "fr_gallery_update_rows_shadow": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "fr_gallery_match_view_f16_workspace": (_Z, [_I, _L]),
+    "fr_gallery_match_view_f16": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _P, _P, _P, _Z, _P]),
+    "fr_gallery_match_view_f8_workspace": (_Z, [_I, _L]),
+    "fr_gallery_match_view_f8": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _P, _P, _P, _Z, _P]),
     "fr_f32_to_f8": (_I, [_P, _P, _L, _P]),
     "fr_f32_to_f16": (_I, [_P, _P, _L, _P]),
     "fr_match_decide": (_I, [_P, _P, _I, _F, _F, _P, _P]),

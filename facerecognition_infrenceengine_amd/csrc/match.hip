@@ -149,7 +149,11 @@ extern "C" int fr_gallery_match_view_f32(const float* Q, const float* G, const i
 
 // ---------------------------------------------------------------- in-place gallery row update
 // one wave per row: G[slots[i]] = rows[i] (optionally / ||rows[i]||, the ingest's normalise)
-__global__ void gallery_update_rows(float* __restrict__ G, const int64_t* __restrict__ slots,
+// SHADOW 1 / 2: the same wave also writes the row's coarse copy into slot slots[i] of the f16 / fp8 slab the view scans
+// read (scan_gemm.hip), from the very values it stores in G and with the conversions of fr_f32_to_f16 / fr_f32_to_f8
+// (same bits, the +-448 saturation included): the coarse row is never older than the f32 row by more than this launch.
+template <int SHADOW>
+__global__ void gallery_update_rows(float* __restrict__ G, void* __restrict__ shadow, const int64_t* __restrict__ slots,
                                     const float* __restrict__ rows, int n, int normalise) {
     const int i = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -165,9 +169,20 @@ __global__ void gallery_update_rows(float* __restrict__ G, const int64_t* __rest
         v0.x /= nrm; v0.y /= nrm; v0.z /= nrm; v0.w /= nrm;
         v1.x /= nrm; v1.y /= nrm; v1.z /= nrm; v1.w /= nrm;
     }
-    float* o = G + slots[i] * GD;
+    const int64_t slot = slots[i];
+    float* o = G + slot * GD;
     *reinterpret_cast<float4*>(o + lane * 4) = v0;
     *reinterpret_cast<float4*>(o + 256 + lane * 4) = v1;
+    if (SHADOW == 1) {
+        half_t* h = reinterpret_cast<half_t*>(shadow) + slot * GD;
+        *reinterpret_cast<half4*>(h + lane * 4) = half4{(half_t)v0.x, (half_t)v0.y, (half_t)v0.z, (half_t)v0.w};
+        *reinterpret_cast<half4*>(h + 256 + lane * 4) = half4{(half_t)v1.x, (half_t)v1.y, (half_t)v1.z, (half_t)v1.w};
+    } else if (SHADOW == 2) {
+        int* b = reinterpret_cast<int*>(reinterpret_cast<char*>(shadow) + slot * GD);
+        const float sc = FR_F8_SCALE;
+        b[lane] = pack_fp8x4(v0.x * sc, v0.y * sc, v0.z * sc, v0.w * sc);
+        b[64 + lane] = pack_fp8x4(v1.x * sc, v1.y * sc, v1.z * sc, v1.w * sc);
+    }
 }
 
 extern "C" int fr_gallery_update_rows_f32(float* G, const int64_t* slots, const float* rows, int n, int D,
@@ -176,7 +191,23 @@ extern "C" int fr_gallery_update_rows_f32(float* G, const int64_t* slots, const 
     FR_REQUIRE(n >= 0, "fr_gallery_update_rows_f32: negative size");
     if (n == 0) return FR_OK;
     FR_REQUIRE(G && slots && rows, "fr_gallery_update_rows_f32: null pointer");
-    gallery_update_rows<<<fr_cdiv(n, 4), 256, 0, fr_stream(stream)>>>(G, slots, rows, n, normalise);
+    gallery_update_rows<0><<<fr_cdiv(n, 4), 256, 0, fr_stream(stream)>>>(G, nullptr, slots, rows, n, normalise);
+    FR_CHECK_LAUNCH("gallery_update_rows");
+    return FR_OK;
+}
+
+extern "C" int fr_gallery_update_rows_shadow(float* G, void* shadow, int shadow_kind, const int64_t* slots,
+                                             const float* rows, int n, int D, int normalise, fr_stream_t stream) {
+    FR_REQUIRE(D == GD, "fr_gallery_update_rows_shadow: D must be %d (got %d)", GD, D);
+    FR_REQUIRE(shadow_kind == FR_SHADOW_F16 || shadow_kind == FR_SHADOW_F8,
+               "fr_gallery_update_rows_shadow: shadow_kind must be FR_SHADOW_F16 or FR_SHADOW_F8 (got %d)", shadow_kind);
+    FR_REQUIRE(n >= 0, "fr_gallery_update_rows_shadow: negative size");
+    if (n == 0) return FR_OK;
+    FR_REQUIRE(G && shadow && slots && rows, "fr_gallery_update_rows_shadow: null pointer");
+    if (shadow_kind == FR_SHADOW_F16)
+        gallery_update_rows<1><<<fr_cdiv(n, 4), 256, 0, fr_stream(stream)>>>(G, shadow, slots, rows, n, normalise);
+    else
+        gallery_update_rows<2><<<fr_cdiv(n, 4), 256, 0, fr_stream(stream)>>>(G, shadow, slots, rows, n, normalise);
     FR_CHECK_LAUNCH("gallery_update_rows");
     return FR_OK;
 }

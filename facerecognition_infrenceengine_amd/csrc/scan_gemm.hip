@@ -24,6 +24,16 @@
 //   f16, 8 for fp8: the fp8 score error is ~2e-3, the gap to the K-th best of 10^6..10^7 random rows is 7 sigma of
 //   it; the tests count); near-duplicate neighbouring rows share a group and cannot crowd each other out.
 // Algorithmic bytes: N * 512 * b per pass per 256 queries (b = 2 / 1); FLOP: 2 * N * F * 512.
+//
+// VIEW form (fr_gallery_match_view_f16 / _f8): the scanned "row r" is slot view[r] of a slab [capacity][512] that
+//   DeviceGallery keeps coherent with its f32 rows (gallery_update_rows in match.hip).  Only the SOURCE address of the
+//   LDS-DMA changes: the lane that fetches tile row r reads 16 B of slot view[r0 + t*64 + r] through a 64-bit global
+//   LDS load (global_load_lds_dwordx4), so any slot of a slab of any size is addressed exactly; the LDS image, its
+//   swizzle, the fragments, the group lists and the barrier are those of the contiguous scan.  A lane needs NPIECE slot
+//   numbers per tile (the rows of its pieces); they are loaded as plain 32-bit loads right after tile t + 1 has been
+//   issued, for tile t + 2, and land under tile t's MFMAs: the DMA stays one tile ahead.  Positions past the view's end
+//   in the last tile re-read the view's last slot (never view[] out of bounds) and are masked to -inf like the
+//   zero-filled rows of the contiguous scan.  Candidates, groups and results are VIEW positions.
 #include "common.h"
 
 #define GD 512
@@ -54,6 +64,7 @@ struct ScanP {
     float* ws_score; int* ws_idx;                       // [F][nranges*4][K]
     const int32_t* seg_counts; int seg_len;
     float qscale;                                       // fp8: queries are multiplied by this before conversion
+    const int64_t* view;                                // VIEW: row r of the scan is slab slot view[r] (G = the slab)
 };
 
 __device__ __forceinline__ int4v sg_pack_f16(const float* q) {
@@ -79,7 +90,7 @@ __device__ __forceinline__ int4v sg_pack_fp8(const float* q, float sc) {
 // Within a 128-B chunk, lane quarter fq uses bytes [16 fq, +16) ("lo") and [64 + 16 fq, +16) ("hi"): for f16 these
 // are the fragments of the chunk's two K = 32 MFMAs; for fp8 both halves feed ONE K = 128 MFMA (the k order inside
 // an MFMA is free as long as A and B agree), so the LDS image and its conflict-free ds_read_b128 pattern are shared.
-template <bool FP8, int TK>
+template <bool FP8, int TK, bool VIEW>
 __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int RB = FP8 ? 512 : 1024;               // gallery row bytes
@@ -129,24 +140,54 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
             }
             if (!ok) { blo[n][kc] = int4v{0, 0, 0, 0}; bhi[n][kc] = int4v{0, 0, 0, 0}; }
         }
+        // VIEW: one query's fragments are packed before the next one's loads return (two load rounds; else all 256
+        // f32 query values stay live into the first tile's address arithmetic and some spill); the contiguous
+        // kernels keep the code they were measured with
+        if (VIEW) {
+#pragma unroll
+            for (int kc = 0; kc < NKC; ++kc) asm volatile("" : "+v"(blo[n][kc]), "+v"(bhi[n][kc]));
+        }
     }
 
     // ---- gallery stream: wave w fills pieces w*NPIECE + i of a tile; piece = (kc, 8-row group)
-    __amdgpu_buffer_rsrc_t grs = buffer_rsrc(reinterpret_cast<const char*>(p.G) + r0 * RB, (unsigned)((int64_t)nrows * RB));
-    unsigned voff[NPIECE];
+    // contiguous: one buffer resource over the range, 32-bit offsets.  VIEW: the buffer spans nothing (unused)
+    __amdgpu_buffer_rsrc_t grs = buffer_rsrc(reinterpret_cast<const char*>(p.G) + (VIEW ? 0 : r0 * RB),
+                                             VIEW ? 0u : (unsigned)((int64_t)nrows * RB));
+    unsigned voff[NPIECE];                               // VIEW: the byte offset inside the slot's row
     unsigned ldst[NPIECE];
+    int vrow[NPIECE];                                    // VIEW: the tile row this lane fetches for piece i
+    int vslot = 0;                                       // VIEW: slab slot of row `lane` of the tile that is issued NEXT
 #pragma unroll
     for (int i = 0; i < NPIECE; ++i) {
         const int pc = wave * NPIECE + i, kc = pc >> 3, rg = pc & 7;
         const int row = rg * 8 + (lane >> 3);
-        voff[i] = (unsigned)(row * RB + kc * 128 + (((lane & 7) ^ (row & 7)) << 4));   // rows past the range read 0
+        const unsigned in_row = (unsigned)(kc * 128 + (((lane & 7) ^ (row & 7)) << 4));
+        voff[i] = VIEW ? in_row : (unsigned)(row * RB) + in_row;                        // rows past the range read 0
         ldst[i] = (unsigned)((kc * SG_ROWS + rg * 8) * 128);
+        vrow[i] = row;
     }
+    // slots of tile t's rows; positions past the range end name the range's last row (masked below, never read past view[])
+    auto load_slots = [&](int t) {
+        if (VIEW && t < ntiles)                          // the low word of the int64 slot (capacity < 2^31)
+            vslot = reinterpret_cast<const int*>(p.view + r0 + min(t * SG_ROWS + lane, nrows - 1))[0];
+    };
     auto issue_tile = [&](int t) {
         char* dst = lds + (t & 1) * TILE_B;
+        if (VIEW) {
+            unsigned slot[NPIECE];                       // all exchanges first: one LDS round trip, not one per piece
 #pragma unroll
-        for (int i = 0; i < NPIECE; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(grs, (lds_ptr_t)(dst + ldst[i]), 16, voff[i] + (unsigned)t * TILE_B, 0, 0, 0);
+            for (int i = 0; i < NPIECE; ++i) slot[i] = (unsigned)__shfl(vslot, vrow[i], 64);
+#pragma unroll
+            for (int i = 0; i < NPIECE; ++i) {
+                const char* src = reinterpret_cast<const char*>(p.G) + (uint64_t)slot[i] * RB + voff[i];
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                 (lds_ptr_t)(dst + ldst[i]), 16, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPIECE; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(grs, (lds_ptr_t)(dst + ldst[i]), 16, voff[i] + (unsigned)t * TILE_B, 0, 0, 0);
+        }
     };
 
     TopK<TK> top[2];
@@ -158,11 +199,14 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
     const int key = fr & 7;
     const unsigned a_lo = (unsigned)(fr * 128 + ((fq ^ key) << 4)), a_hi = (unsigned)(fr * 128 + (((4 + fq) ^ key) << 4));
 
+    load_slots(0);
     issue_tile(0);
+    load_slots(1);
     for (int t = 0; t < ntiles; ++t) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of tile t have landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of tile t have landed (VIEW: and tile t+1's slots)
         __builtin_amdgcn_s_barrier();                               // everyone's have; buffer (t+1)&1 is free again
         if (t + 1 < ntiles) issue_tile(t + 1);
+        load_slots(t + 2);                                          // under this tile's MFMAs
         const char* buf = lds + (t & 1) * TILE_B;
         float4v acc[4][2];
 #pragma unroll
@@ -197,7 +241,7 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
         }
         // acc[m][n] = coarse scores of the 4-row group (t*64 + m*16 + 4*fq)/4 for query q0w + n*16 + fr; groups ascend in m
         const int rbase = t * SG_ROWS + 4 * fq;
-        if (t == ntiles - 1) {                                       // rows past the range end read as zeros: not candidates
+        if (t == ntiles - 1) {                                       // rows past the range end (zeros / VIEW: the last row again): not candidates
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -233,8 +277,10 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
 }
 
 // one wave per query: merge the candidate lists (coarse scores), keep the best K, re-score them in f32
-template <int K>
+// VIEW: candidates are view positions; position pos is re-scored against G32[view[pos]] and reported as pos
+template <int K, bool VIEW>
 __global__ __launch_bounds__(64) void gallery_rerank(const float* __restrict__ Q, const float* __restrict__ G32,
+                                                     const int64_t* __restrict__ view,
                                                      const float* __restrict__ ws_score, const int* __restrict__ ws_idx,
                                                      int F, int64_t N, int ncand, int64_t row_offset, float coarse_unscale,
                                                      int64_t* __restrict__ out_idx, float* __restrict__ out_score,
@@ -288,7 +334,7 @@ __global__ __launch_bounds__(64) void gallery_rerank(const float* __restrict__ Q
         float s = bs[k] * coarse_unscale;                          // G32 == NULL: the group's coarse maximum stands for its rows
         const bool ok = row < N;
         if (G32) {                                                 // exact f32 dot, one row per 16 lanes
-            const float* gg = G32 + (ok ? row : 0) * GD;
+            const float* gg = G32 + (ok ? (VIEW ? view[row] : row) : 0) * GD;
             const float* qq = Q + (int64_t)q * GD;
             float pp = 0.f;
 #pragma unroll
@@ -349,8 +395,8 @@ static size_t scan_ws_bytes(int F, int64_t N) {
 extern "C" size_t fr_gallery_match_f16_workspace(int F, int64_t N) { return scan_ws_bytes<FR_TOPK>(F, N); }
 extern "C" size_t fr_gallery_match_f8_workspace(int F, int64_t N) { return scan_ws_bytes<FR_TOPK8>(F, N); }
 
-template <bool FP8, int TK>
-static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, const float* G32, int F, int64_t N, int D,
+template <bool FP8, int TK, bool VIEW>
+static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, const float* G32, const int64_t* view, int F, int64_t N, int D,
                             int64_t row_offset, int64_t* out_idx, float* out_score, void* workspace,
                             size_t workspace_bytes, const int32_t* seg_counts, int seg_len, float qscale,
                             float coarse_unscale, fr_stream_t stream) {
@@ -358,6 +404,7 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
     FR_REQUIRE(F >= 0 && N >= 0 && N < (1ll << 31), "%s: bad size", who);
     if (F == 0) return FR_OK;
     FR_REQUIRE(Q && out_idx && out_score && (Gc || N == 0), "%s: null pointer", who);
+    FR_REQUIRE(!VIEW || ((view && G32) || N == 0), "%s: null view or null f32 slab", who);
     FR_REQUIRE(!seg_counts || (seg_len > 0 && F % seg_len == 0), "%s: seg_len must divide F", who);
     FR_REQUIRE(workspace && workspace_bytes >= scan_ws_bytes<TK>(F, N), "%s: workspace too small (%zu < %zu)", who,
                workspace_bytes, scan_ws_bytes<TK>(F, N));
@@ -370,13 +417,14 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
         ScanP p;
         p.Q = Q; p.G = Gc; p.F = F; p.N = N; p.nqt = pl.nqt; p.nranges = pl.nranges; p.rows_per_range = pl.rows_per_range;
         p.ws_score = ws_score; p.ws_idx = ws_idx; p.seg_counts = seg_counts; p.seg_len = seg_len; p.qscale = qscale;
+        p.view = view;
         constexpr int lds = 2 * SG_ROWS * (FP8 ? 512 : 1024);
         static FrDevLatch latch;
-        if (!fr_raise_lds(reinterpret_cast<const void*>(gallery_gemm_scan<FP8, TK>), lds, latch)) {
+        if (!fr_raise_lds(reinterpret_cast<const void*>(gallery_gemm_scan<FP8, TK, VIEW>), lds, latch)) {
             fr_set_error("%s: cannot raise dynamic LDS", who);
             return FR_E_LAUNCH;
         }
-        gallery_gemm_scan<FP8, TK><<<pl.grid, 512, lds, s>>>(p);
+        gallery_gemm_scan<FP8, TK, VIEW><<<pl.grid, 512, lds, s>>>(p);
         FR_CHECK_LAUNCH("gallery_gemm_scan");
     } else {
         if (hipMemsetAsync(ws_idx, 0xff, (size_t)F * ncand * sizeof(int), s) != hipSuccess) {   // no candidates
@@ -384,7 +432,7 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
             return FR_E_LAUNCH;
         }
     }
-    gallery_rerank<TK><<<F, 64, 0, s>>>(Q, G32, ws_score, ws_idx, F, N, ncand, row_offset, coarse_unscale, out_idx, out_score,
+    gallery_rerank<TK, VIEW><<<F, 64, 0, s>>>(Q, G32, view, ws_score, ws_idx, F, N, ncand, row_offset, coarse_unscale, out_idx, out_score,
                                         seg_counts, seg_len);
     FR_CHECK_LAUNCH("gallery_rerank");
     return FR_OK;
@@ -393,16 +441,43 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
 extern "C" int fr_gallery_match_f16(const float* Q, const void* G16, const float* G32, int F, int64_t N, int D,
                                     int64_t row_offset, int64_t* out_idx, float* out_score, void* workspace,
                                     size_t workspace_bytes, const int32_t* seg_counts, int seg_len, fr_stream_t stream) {
-    return gemm_scan_launch<false, FR_TOPK>("fr_gallery_match_f16", Q, G16, G32, F, N, D, row_offset, out_idx, out_score,
+    return gemm_scan_launch<false, FR_TOPK, false>("fr_gallery_match_f16", Q, G16, G32, nullptr, F, N, D, row_offset, out_idx, out_score,
                                             workspace, workspace_bytes, seg_counts, seg_len, 1.0f, 1.0f, stream);
 }
 
 extern "C" int fr_gallery_match_f8(const float* Q, const void* G8, const float* G32, int F, int64_t N, int D,
                                    int64_t row_offset, int64_t* out_idx, float* out_score, void* workspace,
                                    size_t workspace_bytes, const int32_t* seg_counts, int seg_len, fr_stream_t stream) {
-    return gemm_scan_launch<true, FR_TOPK8>("fr_gallery_match_f8", Q, G8, G32, F, N, D, row_offset, out_idx, out_score,
+    return gemm_scan_launch<true, FR_TOPK8, false>("fr_gallery_match_f8", Q, G8, G32, nullptr, F, N, D, row_offset, out_idx, out_score,
                                             workspace, workspace_bytes, seg_counts, seg_len, FR_F8_SCALE,
                                             1.0f / (FR_F8_SCALE * FR_F8_SCALE), stream);
+}
+
+// The view forms: S16 / S8 is the coarse slab [capacity][512] beside the f32 slab G32, view[0..Nview) its slots.
+// capacity < 2^31: the scan reads slot numbers as 32-bit values (a 64-bit address is formed from them, so the slab's
+// BYTE size is not limited); every view[i] must lie in [0, capacity).
+extern "C" size_t fr_gallery_match_view_f16_workspace(int F, int64_t Nview) { return scan_ws_bytes<FR_TOPK>(F, Nview); }
+extern "C" size_t fr_gallery_match_view_f8_workspace(int F, int64_t Nview) { return scan_ws_bytes<FR_TOPK8>(F, Nview); }
+
+extern "C" int fr_gallery_match_view_f16(const float* Q, const void* S16, const float* G32, const int64_t* view, int F,
+                                         int64_t Nview, int64_t capacity, int D, int64_t* out_idx, float* out_score,
+                                         void* workspace, size_t workspace_bytes, fr_stream_t stream) {
+    FR_REQUIRE(capacity >= 0 && capacity < (1ll << 31) && Nview <= capacity,
+               "fr_gallery_match_view_f16: capacity %lld must be below 2^31 slots and hold the view (%lld rows)",
+               (long long)capacity, (long long)Nview);
+    return gemm_scan_launch<false, FR_TOPK, true>("fr_gallery_match_view_f16", Q, S16, G32, view, F, Nview, D, 0, out_idx,
+                                                  out_score, workspace, workspace_bytes, nullptr, 0, 1.0f, 1.0f, stream);
+}
+
+extern "C" int fr_gallery_match_view_f8(const float* Q, const void* S8, const float* G32, const int64_t* view, int F,
+                                        int64_t Nview, int64_t capacity, int D, int64_t* out_idx, float* out_score,
+                                        void* workspace, size_t workspace_bytes, fr_stream_t stream) {
+    FR_REQUIRE(capacity >= 0 && capacity < (1ll << 31) && Nview <= capacity,
+               "fr_gallery_match_view_f8: capacity %lld must be below 2^31 slots and hold the view (%lld rows)",
+               (long long)capacity, (long long)Nview);
+    return gemm_scan_launch<true, FR_TOPK8, true>("fr_gallery_match_view_f8", Q, S8, G32, view, F, Nview, D, 0, out_idx,
+                                                  out_score, workspace, workspace_bytes, nullptr, 0, FR_F8_SCALE,
+                                                  1.0f / (FR_F8_SCALE * FR_F8_SCALE), stream);
 }
 
 // f32 unit rows -> fp8 e4m3 (OCP) rows scaled by FR_F8_SCALE = 256: |element| <= 1 maps into [-256, 256] (e4m3

@@ -15,6 +15,8 @@ from . import _lib
 
 DIM = 512
 TOPK_MAX = 16                  # include/frhip.h FR_TOPK_MAX
+SCANS = ("f32", "f16", "f8")
+_SHADOW_KIND = {"f16": 1, "f8": 2}      # include/frhip.h FR_SHADOW_F16 / FR_SHADOW_F8
 _PIN = threading.local()       # pinned host buffers of GalleryMatcher.match, per thread and query count
 
 
@@ -32,7 +34,7 @@ class GalleryMatcher:
         configs C4 / C5); the f32 rows are kept.  ``f16_scan=True`` is the older spelling of scan="f16"."""
         _lib.require_gpu()
         self.scan = scan or ("f16" if f16_scan else "f32")
-        if self.scan not in ("f32", "f16", "f8"):
+        if self.scan not in SCANS:
             raise ValueError("scan must be 'f32', 'f16' or 'f8'")
         self.f16_scan = self.scan == "f16"
         self.G16 = None                       # the coarse copy (f16 or fp8 e4m3 x 256)
@@ -209,13 +211,22 @@ class DeviceGallery:
     changed rows into their slots in place (new ids take a free slot, capacity doubles when full),
     ``remove`` frees slots, and a company view is only an int64 slot list in the reference's dict order -
     ``GalleryView.match_device`` scans the slab through it (no per-company copy of the rows).
+
+    ``scan``: "f32" (default), "f16" or "f8", spelt and meant as ``GalleryMatcher``'s.  With "f16" / "f8" the gallery
+    keeps a coarse shadow slab ``S`` beside ``G`` (f16, or fp8 e4m3 x 256: 1 KB / 0.5 KB more per slot) that every
+    ``upsert`` writes in the same launch as the f32 rows, and views match by the one-pass coarse scan through the slot
+    list with the exact f32 re-rank: the ids are those of the f32 scan.  For large galleries / many queries.
     """
 
-    def __init__(self, device="cuda:0", capacity=1024):
+    def __init__(self, device="cuda:0", capacity=1024, scan="f32"):
+        if scan not in SCANS:
+            raise ValueError("scan must be 'f32', 'f16' or 'f8'")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device)
+        self.scan = scan
         self.G = torch.zeros((max(int(capacity), 1), DIM), dtype=torch.float32, device=self.device)
+        self.S = self._new_shadow(self.G.shape[0])       # the coarse slab; None for scan="f32"
         self.slot_of = {}                # id -> slot
         self._free = []                  # freed slots, reused LIFO
         self._next = 0                   # first never-used slot
@@ -228,6 +239,11 @@ class DeviceGallery:
     def capacity(self):
         return self.G.shape[0]
 
+    def _new_shadow(self, capacity):
+        if self.scan == "f32":
+            return None
+        return torch.zeros((capacity, DIM), dtype=torch.float16 if self.scan == "f16" else torch.uint8, device=self.device)
+
     def _grow(self, need):
         cap = self.capacity
         while cap < need:
@@ -235,6 +251,10 @@ class DeviceGallery:
         if cap != self.capacity:
             G = torch.zeros((cap, DIM), dtype=torch.float32, device=self.device)
             G[: self.capacity].copy_(self.G)
+            if self.S is not None:                       # the coarse rows move with their slots: bytes, not a reconversion
+                S = self._new_shadow(cap)
+                S[: self.capacity].copy_(self.S)
+                self.S = S
             self.G = G
 
     def upsert(self, ids, rows, normalise=False):
@@ -265,8 +285,13 @@ class DeviceGallery:
             self.generation += 1
         slots = torch.tensor([self.slot_of[i] for i in ids], dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            self.lib.fr_gallery_update_rows_f32(_lib.ptr(self.G), _lib.ptr(slots), _lib.ptr(rows), len(ids), DIM,
-                                                1 if normalise else 0, _lib.stream_ptr())
+            if self.S is None:
+                self.lib.fr_gallery_update_rows_f32(_lib.ptr(self.G), _lib.ptr(slots), _lib.ptr(rows), len(ids), DIM,
+                                                    1 if normalise else 0, _lib.stream_ptr())
+            else:                                        # f32 row + its coarse copy: one launch, one stream
+                self.lib.fr_gallery_update_rows_shadow(_lib.ptr(self.G), _lib.ptr(self.S), _SHADOW_KIND[self.scan],
+                                                       _lib.ptr(slots), _lib.ptr(rows), len(ids), DIM,
+                                                       1 if normalise else 0, _lib.stream_ptr())
 
     def remove(self, ids):
         n = 0
@@ -301,7 +326,8 @@ class GalleryView:
         return self.gallery.G[self.slots]
 
     def match_device(self, Q, renormalise=True):
-        """As ``GalleryMatcher.match_device``; idx is the position in ``self.ids`` (-1: empty view)."""
+        """As ``GalleryMatcher.match_device``; idx is the position in ``self.ids`` (-1: empty view).  On a gallery built
+        with scan="f16" / "f8": the coarse scan of the shadow slab through the slot list, re-ranked exactly in f32."""
         if self.generation != self.gallery.generation:
             raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
         Q = Q.to(self.device, torch.float32).contiguous().reshape(-1, DIM)
@@ -316,6 +342,15 @@ class GalleryView:
                 Qn = torch.empty_like(Q)
                 self.lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
                 Q = Qn
+            g = self.gallery
+            if g.S is not None:
+                wsz, fn = ((self.lib.fr_gallery_match_view_f16_workspace, self.lib.fr_gallery_match_view_f16)
+                           if g.scan == "f16" else
+                           (self.lib.fr_gallery_match_view_f8_workspace, self.lib.fr_gallery_match_view_f8))
+                ws = GalleryMatcher._workspace(self, wsz(F, len(self.ids)))
+                fn(_lib.ptr(Q), _lib.ptr(g.S), _lib.ptr(g.G), _lib.ptr(self.slots), F, len(self.ids), g.capacity, DIM,
+                   _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), s)
+                return idx, score
             ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_match_workspace(F, len(self.ids)))
             self.lib.fr_gallery_match_view_f32(_lib.ptr(Q), _lib.ptr(self.gallery.G), _lib.ptr(self.slots), F,
                                                len(self.ids), DIM, _lib.ptr(idx), _lib.ptr(score),
@@ -323,7 +358,8 @@ class GalleryView:
         return idx, score
 
     def match_topk_device(self, Q, k, renormalise=True):
-        """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``."""
+        """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``.  Always the exact f32 scan over the
+        f32 rows, whatever ``scan`` the gallery was built with (there is no coarse top-K)."""
         k = _check_k(k)
         if self.generation != self.gallery.generation:
             raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")

@@ -81,11 +81,15 @@ class InMemoryStore:
 class EmbeddingManager:
     """Same public surface as infrenceServer.py:36-398; ``store`` replaces the Mongo connection."""
 
-    def __init__(self, mongodb_uri=None, database_name=None, store=None, device="cuda:0", sync_interval=30):
+    def __init__(self, mongodb_uri=None, database_name=None, store=None, device="cuda:0", sync_interval=30, scan="f32"):
+        """``scan``: how the views of the device gallery match - "f32" (default, the exact f32 scan), or "f16" / "f8" for
+        a large gallery: the one-pass coarse scan with the exact f32 re-rank (``DeviceGallery``), same ids."""
         if store is None:
             raise ValueError("EmbeddingManager needs store=<store object> (the reference's module-level MongoDB "
                              "connection is not reproduced; see INTEGRATION.md for a pymongo adapter)")
-        self.store, self.device = store, device
+        if scan not in ("f32", "f16", "f8"):
+            raise ValueError("scan must be 'f32', 'f16' or 'f8'")
+        self.store, self.device, self.scan = store, device, scan
         self.embeddings = {}                 # id -> unit float32[512]; dict order = row order
         self.employee_metadata = {}
         self.embeddings_lock = threading.Lock()
@@ -195,7 +199,8 @@ class EmbeddingManager:
         writes); removed people free their slots.  Called under the lock."""
         from .gallery import DeviceGallery
         if self._gallery is None:
-            self._gallery = DeviceGallery(self.device, capacity=max(1024, 2 * len(self.embeddings)))
+            coarse = {} if self.scan == "f32" else {"scan": self.scan}        # "f32": the call as it always was
+            self._gallery = DeviceGallery(self.device, capacity=max(1024, 2 * len(self.embeddings)), **coarse)
         if self._gone:
             self._gallery.remove(self._gone)
             self._gone = set()

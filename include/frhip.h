@@ -33,9 +33,10 @@ typedef void* fr_stream_t;
 /* Version of THIS header's ABI: bumped whenever a signature or an argument struct changes shape (101: fr_conv_args gained
  * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads; 103: the fr_gallery_topk_* / fr_match_reduce_shards_topk
  * entries; 104: fr_pnet_level gained x1s / hs / ws / f16, the fr_pnet_pyramid_* entries;
- * 105: fr_frame_ref, fr_letterbox_u8, fr_detections_unscale, the fr_warp_affine_5pt*_refs entries).  fr_version() returns the value the library was built
+ * 105: fr_frame_ref, fr_letterbox_u8, fr_detections_unscale, the fr_warp_affine_5pt*_refs entries;
+ * 106: fr_gallery_match_view_f16 / _f8 with their _workspace functions, fr_gallery_update_rows_shadow).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
-#define FR_ABI_VERSION 105
+#define FR_ABI_VERSION 106
 int fr_version(void);
 const char* fr_last_error_string(void);
 /* number of visible HIP devices (<=0: none); does not create a context on any device */
@@ -107,6 +108,32 @@ int fr_gallery_topk_f32(const float* Q, const float* G, int F, int64_t N, int D,
 int fr_gallery_topk_view_f32(const float* Q, const float* G, const int64_t* view, int F, int64_t Nview, int D,
                              int K, int64_t* out_idx, float* out_score, void* workspace,
                              size_t workspace_bytes, fr_stream_t stream);
+/* The coarse scan through a view: a deployment's synced slab at the sizes above.  S16 / S8 is a second slab
+ * [capacity,512] beside the f32 slab G32, f16 or OCP fp8 e4m3 x FR_F8_SCALE, whose slot s holds exactly
+ * fr_f32_to_f16 / fr_f32_to_f8 of G32's slot s; fr_gallery_update_rows_shadow keeps it so by writing both slabs in
+ * ONE launch (shadow_kind FR_SHADOW_F16 / FR_SHADOW_F8; otherwise fr_gallery_update_rows_f32's contract).  Slots no
+ * view names may hold anything.
+ * fr_gallery_match_view_f16 / _f8 scan the coarse rows S[view[0..Nview)] on the matrix cores, keep the FR_TOPK /
+ * FR_TOPK8 best groups of 4 consecutive VIEW positions per query and re-score those exactly in f32 against
+ * G32[view[pos]].  The result contract is fr_gallery_match_view_f32's: out_idx is the VIEW position of the maximum f32
+ * score, the lowest position on exact ties, (-1, -1.0f) when Nview == 0 or no score exceeds -1; out_score is the f32
+ * dot.  workspace: the matching _workspace(F, Nview) bytes.
+ * Limits: Nview < 2^31 and capacity < 2^31 slots; every view[i] must lie in [0, capacity) (slot numbers are read as
+ * 32-bit values, and nothing checks them).  Each row is fetched through a 64-bit address, so the slab's BYTE size is
+ * not limited: a 4 M-slot f16 slab (4 GiB) or a 10 M-slot fp8 slab (5 GiB) is addressed exactly.  A capacity or Nview
+ * past the limit is refused with FR_E_INVALID, never wrapped. */
+#define FR_SHADOW_F16 1
+#define FR_SHADOW_F8 2
+int fr_gallery_update_rows_shadow(float* G, void* shadow, int shadow_kind, const int64_t* slots, const float* rows,
+                                  int n, int D, int normalise, fr_stream_t stream);
+size_t fr_gallery_match_view_f16_workspace(int F, int64_t Nview);
+int fr_gallery_match_view_f16(const float* Q, const void* S16, const float* G32, const int64_t* view, int F,
+                              int64_t Nview, int64_t capacity, int D, int64_t* out_idx, float* out_score,
+                              void* workspace, size_t workspace_bytes, fr_stream_t stream);
+size_t fr_gallery_match_view_f8_workspace(int F, int64_t Nview);
+int fr_gallery_match_view_f8(const float* Q, const void* S8, const float* G32, const int64_t* view, int F,
+                             int64_t Nview, int64_t capacity, int D, int64_t* out_idx, float* out_score,
+                             void* workspace, size_t workspace_bytes, fr_stream_t stream);
 /* f32 -> fp8 e4m3 row conversion (x * FR_F8_SCALE, round to nearest even, n % 4 == 0) */
 int fr_f32_to_f8(const float* x, void* out, int64_t n, fr_stream_t stream);
 /* f32 -> f16 row conversion for building the device-resident gallery (infrenceServer.py:271) */
