@@ -3,86 +3,10 @@
 // maximum) extended from 1 to K.  Scores are the same k-ordered f32 MFMA chains as gallery_scan_f32 (match.hip), so
 // column 0 is bit-identical to the top-1 match for every K.
 //
-// A candidate list is KP = 2 / 4 / 8 / 16 (score, row) pairs in REGISTERS, best first; an empty slot is
-// (-inf, -1) and loses to every row.  Every index into a list is a compile-time constant (fully unrolled loops): a
-// dynamically indexed list would live in scratch memory.  Two operations:
-//   insert:      the scan's step.  One compare drops a score that is not '>' the lane's K-th entry - rows ascend
-//                within a lane, so an equal score with a higher row loses, as it must; otherwise an unrolled
-//                compare-and-shift puts the pair behind every entry with score >= s.
-//   merge:       the K best of two sorted lists, as a bitonic merge: c[j] = better(a[j], b[KP-1-j]) holds the K best
-//                of both as a bitonic sequence, log2(KP) compare-exchange stages sort it.  Used by every merge level:
-//                half-waves (__shfl_xor 32), waves (LDS), blocks (workspace), shards.
+// The candidate list (TopK<KP>: registers only, insert for the scan's step, a bitonic merge for every merge level) is
+// topk_list.h's; the certified re-rank of the coarse scan (scan_gemm.hip) sorts with the same merge.
 #include "match_scan.h"
-
-#define TOPK_EMPTY_S (-INFINITY)
-
-// a before b in the total order; rows are distinct among real candidates, all empty slots are equal
-__device__ __forceinline__ bool topk_before(float as, int64_t ai, float bs, int64_t bi) {
-    return ai >= 0 && (bi < 0 || as > bs || (as == bs && ai < bi));
-}
-
-template <int KP>
-struct TopK {
-    float s[KP];
-    int64_t i[KP];
-
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int j = 0; j < KP; ++j) { s[j] = TOPK_EMPTY_S; i[j] = -1; }
-    }
-
-    // scan step: row gi ascends from call to call, s is finite or NaN (a NaN is never '>': never listed)
-    __device__ __forceinline__ void insert(float v, int64_t gi) {
-        if (!(v > s[KP - 1])) return;
-#pragma unroll
-        for (int j = KP - 1; j > 0; --j) {
-            if (v > s[j - 1]) { s[j] = s[j - 1]; i[j] = i[j - 1]; }
-            else if (v > s[j]) { s[j] = v; i[j] = gi; }
-        }
-        if (v > s[0]) { s[0] = v; i[0] = gi; }
-    }
-
-    // this = the KP best of this and o (both sorted)
-    __device__ __forceinline__ void merge(const TopK& o) {
-#pragma unroll
-        for (int j = 0; j < KP; ++j)
-            if (topk_before(o.s[KP - 1 - j], o.i[KP - 1 - j], s[j], i[j])) { s[j] = o.s[KP - 1 - j]; i[j] = o.i[KP - 1 - j]; }
-#pragma unroll
-        for (int d = KP / 2; d >= 1; d >>= 1) {
-#pragma unroll
-            for (int j = 0; j < KP; ++j) {
-                if ((j & d) == 0 && topk_before(s[j + d], i[j + d], s[j], i[j])) {
-                    const float ts = s[j]; const int64_t ti = i[j];
-                    s[j] = s[j + d]; i[j] = i[j + d];
-                    s[j + d] = ts; i[j + d] = ti;
-                }
-            }
-        }
-    }
-
-    __device__ __forceinline__ TopK shfl_xor(int mask) const {
-        TopK o;
-#pragma unroll
-        for (int j = 0; j < KP; ++j) { o.s[j] = __shfl_xor(s[j], mask, 64); o.i[j] = __shfl_xor(i[j], mask, 64); }
-        return o;
-    }
-
-    // entries [0, K) from ps / pi (stride 1), the rest empty
-    __device__ __forceinline__ void load(const float* ps, const int64_t* pi, int K) {
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const bool in = j < K;
-            s[j] = in ? ps[j] : TOPK_EMPTY_S;
-            i[j] = in ? pi[j] : -1;
-        }
-    }
-
-    __device__ __forceinline__ void store(float* ps, int64_t* pi, int K) const {
-#pragma unroll
-        for (int j = 0; j < KP; ++j)
-            if (j < K) { ps[j] = s[j]; pi[j] = i[j]; }
-    }
-};
+#include "topk_list.h"
 
 // Same orientation and arithmetic as gallery_scan_f32: a lane owns ONE query and 16 rows of a tile, its list is
 // lane-local inside the scan.  Partial lists go to ws_score / ws_idx [gridDim.x][F][K].
@@ -265,6 +189,17 @@ extern "C" int fr_gallery_topk_view_f32(const float* Q, const float* G, const in
     // Nview == 0: the scan kernel sees no tiles and the reduce writes (-1, -1.0) everywhere
     return gallery_topk_launch("fr_gallery_topk_view_f32", Q, G, Nview ? view : nullptr, F, Nview, D, K, 0, out_idx,
                                out_score, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+// fr_gallery_topk_view_f32 for the queries a mask names: query f is scanned iff mask[f] > 0 (the padding rule of the
+// contiguous entry with seg_len = 1), every other query costs no scan work and reports (-1, -1.0).  The exact fallback
+// of the certified coarse top-K (scan_gemm.hip) runs this with the re-rank's flags as the mask.
+extern "C" int fr_gallery_topk_view_masked_f32(const float* Q, const float* G, const int64_t* view, int F, int64_t Nview,
+                                               int D, int K, int64_t* out_idx, float* out_score, void* workspace,
+                                               size_t workspace_bytes, const int32_t* mask, fr_stream_t stream) {
+    FR_REQUIRE(view || Nview == 0, "fr_gallery_topk_view_masked_f32: null view");
+    return gallery_topk_launch("fr_gallery_topk_view_masked_f32", Q, G, Nview ? view : nullptr, F, Nview, D, K, 0, out_idx,
+                               out_score, workspace, workspace_bytes, mask, mask ? 1 : 0, stream);
 }
 
 extern "C" int fr_match_reduce_shards_topk(const int32_t* cand, int R, int n, int K, int q0, int F, int64_t* out_idx,

@@ -34,18 +34,18 @@
 //   issued, for tile t + 2, and land under tile t's MFMAs: the DMA stays one tile ahead.  Positions past the view's end
 //   in the last tile re-read the view's last slot (never view[] out of bounds) and are masked to -inf like the
 //   zero-filled rows of the contiguous scan.  Candidates, groups and results are VIEW positions.
-#include "common.h"
+#include "match_scan.h"
+#include "topk_list.h"
 
-#define GD 512
 #define SG_ROWS 64            // gallery rows per LDS tile
 #define SG_QW 32              // queries per wave (2 MFMA n-tiles)
 #define SG_QB 256             // queries per block (8 waves)
 
 template <int K>
-struct TopK { float s[K]; int i[K]; };
+struct GroupTop { float s[K]; int i[K]; };
 
 template <int K>
-__device__ __forceinline__ void topk_insert(TopK<K>& t, float s, int i) {
+__device__ __forceinline__ void topk_insert(GroupTop<K>& t, float s, int i) {
     // static indices only (a runtime-indexed store would push the lists to scratch memory)
     if (!(s > t.s[K - 1])) return;
     t.s[K - 1] = s; t.i[K - 1] = i;
@@ -58,6 +58,15 @@ __device__ __forceinline__ void topk_insert(TopK<K>& t, float s, int i) {
     }
 }
 
+// topk_insert that reports what the list lets go of: s itself when it is not kept, else the entry pushed off the end
+template <int K>
+__device__ __forceinline__ float topk_insert_spill(GroupTop<K>& t, float s, int i) {
+    if (!(s > t.s[K - 1])) return s;
+    const float out = t.s[K - 1];
+    topk_insert<K>(t, s, i);
+    return out;
+}
+
 struct ScanP {
     const float* Q; const void* G; int F; int64_t N;
     int nqt, nranges; int64_t rows_per_range;          // rows_per_range: multiple of SG_ROWS
@@ -65,6 +74,7 @@ struct ScanP {
     const int32_t* seg_counts; int seg_len;
     float qscale;                                       // fp8: queries are multiplied by this before conversion
     const int64_t* view;                                // VIEW: row r of the scan is slab slot view[r] (G = the slab)
+    float* ws_spill;                                    // SPILL: [F][nranges*4] spill bounds, beside the lists
 };
 
 __device__ __forceinline__ int4v sg_pack_f16(const float* q) {
@@ -90,7 +100,11 @@ __device__ __forceinline__ int4v sg_pack_fp8(const float* q, float sc) {
 // Within a 128-B chunk, lane quarter fq uses bytes [16 fq, +16) ("lo") and [64 + 16 fq, +16) ("hi"): for f16 these
 // are the fragments of the chunk's two K = 32 MFMAs; for fp8 both halves feed ONE K = 128 MFMA (the k order inside
 // an MFMA is free as long as A and B agree), so the LDS image and its conflict-free ds_read_b128 pattern are shared.
-template <bool FP8, int TK, bool VIEW>
+// SPILL (the certified top-K, below): a lane also keeps the best group maximum its list did NOT keep - dropped at the
+// door or pushed off the end; -inf if it never let a group go - so every row the candidate lists do not name has a
+// coarse score <= the spill bound of its (range, lane quarter, query).  NaN maxima are not bounded by it (fmaxf drops
+// them); they only arise from non-finite operands, which the re-rank refuses to certify.
+template <bool FP8, int TK, bool VIEW, bool SPILL = false>
 __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int RB = FP8 ? 512 : 1024;               // gallery row bytes
@@ -190,11 +204,12 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
         }
     };
 
-    TopK<TK> top[2];
+    GroupTop<TK> top[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
         for (int k = 0; k < TK; ++k) { top[n].s[k] = -INFINITY; top[n].i[k] = -1; }
+    float spill[2] = {-INFINITY, -INFINITY};
 
     const int key = fr & 7;
     const unsigned a_lo = (unsigned)(fr * 128 + ((fq ^ key) << 4)), a_hi = (unsigned)(fr * 128 + (((4 + fq) ^ key) << 4));
@@ -257,7 +272,12 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
             if (mx > top[n].s[TK - 1]) {                             // rare once the lists have warmed up
                 const int g0 = (int)((r0 + rbase) >> 2);             // r0 and rbase are multiples of 4
 #pragma unroll
-                for (int m = 0; m < 4; ++m) topk_insert<TK>(top[n], gm[m], g0 + m * 4);
+                for (int m = 0; m < 4; ++m) {
+                    if constexpr (SPILL) spill[n] = fmaxf(spill[n], topk_insert_spill<TK>(top[n], gm[m], g0 + m * 4));
+                    else topk_insert<TK>(top[n], gm[m], g0 + m * 4);
+                }
+            } else if constexpr (SPILL) {
+                spill[n] = fmaxf(spill[n], mx);
             }
         }
     }
@@ -271,6 +291,7 @@ __global__ __launch_bounds__(512, 2) void gallery_gemm_scan(ScanP p) {
             int* io = p.ws_idx + ((int64_t)q * slots + slot) * TK;
 #pragma unroll
             for (int k = 0; k < TK; ++k) { so[k] = top[n].s[k]; io[k] = top[n].i[k]; }
+            if constexpr (SPILL) p.ws_spill[(int64_t)q * slots + slot] = spill[n];
         }
     }
 #endif
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(64) void gallery_rerank(const float* __restrict__ Q
     }
     // ONE pass over the candidates: every lane keeps the best K of its strided share (order: coarse score, then lowest
     // group id), then K rounds of wave-wide argmax over the lanes' list heads pop the overall best K.
-    TopK<K> loc;
+    GroupTop<K> loc;
 #pragma unroll
     for (int k = 0; k < K; ++k) { loc.s[k] = -INFINITY; loc.i[k] = 0x7fffffff; }
     for (int c = lane; c < ncand; c += 64) {
@@ -417,7 +438,7 @@ static int gemm_scan_launch(const char* who, const float* Q, const void* Gc, con
         ScanP p;
         p.Q = Q; p.G = Gc; p.F = F; p.N = N; p.nqt = pl.nqt; p.nranges = pl.nranges; p.rows_per_range = pl.rows_per_range;
         p.ws_score = ws_score; p.ws_idx = ws_idx; p.seg_counts = seg_counts; p.seg_len = seg_len; p.qscale = qscale;
-        p.view = view;
+        p.view = view; p.ws_spill = nullptr;
         constexpr int lds = 2 * SG_ROWS * (FP8 ? 512 : 1024);
         static FrDevLatch latch;
         if (!fr_raise_lds(reinterpret_cast<const void*>(gallery_gemm_scan<FP8, TK, VIEW>), lds, latch)) {
@@ -497,5 +518,297 @@ extern "C" int fr_f32_to_f8(const float* x, void* out, int64_t n, fr_stream_t st
     if (blocks > 8192) blocks = 8192;
     f32_to_f8_k<<<(int)blocks, 256, 0, fr_stream(stream)>>>(x, reinterpret_cast<int*>(out), n / 4, FR_F8_SCALE);
     FR_CHECK_LAUNCH("f32_to_f8");
+    return FR_OK;
+}
+
+// ---------------------------------------------------------------- certified coarse top-K
+// fr_gallery_topk_f16 / _view_f16: the K best rows per query with the bits of fr_gallery_topk_f32 / _view_f32, from the
+// f16 coarse pass above whenever that is PROVABLY enough, from the exact scan otherwise - decided per query on the
+// device, no host synchronisation.
+//   1. gallery_gemm_scan<false, FR_TOPK, VIEW, SPILL>: the coarse pass with spill bounds.
+//   2. gallery_rerank_topk<KP, VIEW>, one wave per query: takes the C best candidate groups by coarse score (C = 8 / 8 /
+//      16 / 32 for KP = 2 / 4 / 8 / 16), re-scores their 4 C rows with scan_tile_f32 - the exact scan's own MFMA chain, the
+//      query in every B column - so a score is the bit pattern gallery_scan_topk_f32 produces for that (row, query); sorts
+//      them with TopK<KP>::merge under the exact scan's total order; then certifies:
+//          B   = max(coarse score of the (C+1)-th candidate group, every spill bound of the query)
+//          s_K = the K-th exact score found, or -1 when fewer than K re-scored rows score > -1
+//          certified  <=>  query finite and within f16 range, and  s_K > B + eps      (strict)
+//      eps = FR_CERT_C 2^-10 |q| Gmax + FR_CERT_ABS (|q| + Gmax) + 2^-40 bounds |coarse - exact f32| for every row of
+//      the gallery (derivation: DESIGN.md 4.6b), so a row that was not re-scored has an exact score < s_K and cannot be,
+//      or tie with, one of the K best.  flags[q] = 0 certified / 1 not.
+//   3. the exact top-K scan with the flags as its mask (seg_len 1: unflagged queries cost no scan work), and one select
+//      launch that takes the exact lists for flagged queries.
+#define FR_CERT_C 1.125f
+#define FR_CERT_ABS 0x1p-20f
+
+template <int KP> struct RerankBudget { static constexpr int C = KP <= 4 ? 8 : 2 * KP; };      // groups re-scored (<= 64)
+
+template <int KP, bool VIEW>
+__global__ __launch_bounds__(64) void gallery_rerank_topk(const float* __restrict__ Q, const float* __restrict__ G32,
+                                                          const int64_t* __restrict__ view,
+                                                          const float* __restrict__ ws_score, const int* __restrict__ ws_idx,
+                                                          const float* __restrict__ ws_spill, int64_t N, int K, int ncand,
+                                                          int nlists, int64_t row_offset, const float* __restrict__ gmax,
+                                                          int64_t* __restrict__ out_idx, float* __restrict__ out_score,
+                                                          int32_t* __restrict__ flags,
+                                                          const int32_t* __restrict__ seg_counts, int seg_len) {
+    constexpr int C = RerankBudget<KP>::C;
+    constexpr int NONE = 0x7fffffff;
+    extern __shared__ __attribute__((aligned(16))) char lds[];      // candidates: score [ncand], group [ncand]; picks [C]
+    float* cs = reinterpret_cast<float*>(lds);
+    int* ci = reinterpret_cast<int*>(cs + ncand);
+    int* selg = ci + ncand;
+    const int q = blockIdx.x, lane = threadIdx.x;
+    if (seg_counts && !slot_valid(seg_counts, seg_len, q)) {
+        if (lane < K) { out_idx[(int64_t)q * K + lane] = -1; out_score[(int64_t)q * K + lane] = -1.0f; }
+        if (lane == 0) flags[q] = 0;
+        return;
+    }
+    // |q| and the query's fitness for the bound: every element finite and inside the f16 range
+    const float* qq = Q + (int64_t)q * GD;
+    float qn;
+    bool bad;
+    {
+        const float4 a = *reinterpret_cast<const float4*>(qq + lane * 4), b = *reinterpret_cast<const float4*>(qq + 256 + lane * 4);
+        float ss = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+        ss += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+        const float m = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
+                              fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
+        const bool nan = a.x != a.x || a.y != a.y || a.z != a.z || a.w != a.w || b.x != b.x || b.y != b.y || b.z != b.z || b.w != b.w;
+        bad = __ballot(nan || !(m <= 65504.0f)) != 0;
+        qn = sqrtf(wave_sum(ss));
+    }
+    // stage the candidates; a lane remembers the best of its strided share (order: coarse score, then lowest group)
+    float ls = -INFINITY; int li = NONE, lp = 0;
+    auto rescan = [&]() {
+        ls = -INFINITY; li = NONE; lp = 0;
+        for (int c = lane; c < ncand; c += 64) {
+            const float s = cs[c]; const int i = ci[c];
+            if (i >= 0 && (s > ls || (s == ls && i < li))) { ls = s; li = i; lp = c; }
+        }
+    };
+    for (int c = lane; c < ncand; c += 64) {
+        const int i = ws_idx[(int64_t)q * ncand + c];
+        cs[c] = ws_score[(int64_t)q * ncand + c]; ci[c] = i;
+    }
+    if (lane < C) selg[lane] = -1;
+    float sp = -INFINITY;
+    for (int c = lane; c < nlists; c += 64) sp = fmaxf(sp, ws_spill[(int64_t)q * nlists + c]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sp = fmaxf(sp, __shfl_xor(sp, o, 64));
+    __syncthreads();
+    rescan();
+    // C rounds pop the best remaining group (its owner lane rescans its share); round C reads the (C+1)-th score
+    float bound = -INFINITY;
+    for (int round = 0; round <= C; ++round) {
+        float ms = ls; int mi = li;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float os = __shfl_xor(ms, o, 64); const int oi = __shfl_xor(mi, o, 64);
+            if (os > ms || (os == ms && oi < mi)) { ms = os; mi = oi; }
+        }
+        mi = __builtin_amdgcn_readfirstlane(mi);
+        if (mi == NONE) break;                                     // fewer than C + 1 candidates: nothing left unseen in the lists
+        if (round == C) { bound = ms; break; }
+        if (li == mi) {                                            // group ids are unique: exactly one lane
+            selg[round] = mi;
+            ci[lp] = -1;
+            rescan();
+        }
+    }
+    bound = fmaxf(bound, sp);
+    __syncthreads();
+    // exact scores of the picked groups' rows: tiles of 32 rows = 8 groups on the exact scan's MFMA chain
+    TopK<KP> top;
+    top.clear();
+    const int r = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int t = 0; t < C / 8; ++t) {
+        if (selg[t * 8] < 0) break;                                // picks fill in order: an empty first group = an empty tile
+        const int j = t * 32 + r, g = selg[j >> 2];
+        const int64_t row = (int64_t)g * 4 + (j & 3);
+        const bool ok = g >= 0 && row < N;
+        const int64_t slot = ok ? (VIEW ? view[row] : row) : 0;
+        const float16v acc = scan_tile_f32(G32 + slot * GD + 4 * h, qq + 4 * h, ok);
+        // acc[reg] = score of tile row (reg & 3) + 8 * (reg >> 2) + 4 * h in EVERY column: lane (r < 16, h) takes reg = r
+        float v = acc[0];
+#pragma unroll
+        for (int reg = 1; reg < 16; ++reg) v = (r == reg) ? acc[reg] : v;
+        const int j2 = t * 32 + (r & 3) + 8 * ((r >> 2) & 3) + 4 * h, g2 = selg[j2 >> 2];
+        const int64_t row2 = (int64_t)g2 * 4 + (j2 & 3);
+        if (r < 16 && g2 >= 0 && row2 < N && v == v) {
+            TopK<KP> o;
+            o.clear();
+            o.s[0] = v; o.i[0] = row2;
+            top.merge(o);
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) top.merge(top.shfl_xor(m));
+    if (lane == 0) {
+        float sk = -1.0f;
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            if (j < K) {
+                const bool has = top.i[j] >= 0 && top.s[j] > -1.0f;
+                out_idx[(int64_t)q * K + j] = has ? top.i[j] + row_offset : -1;
+                out_score[(int64_t)q * K + j] = has ? top.s[j] : -1.0f;
+                if (j == K - 1 && has) sk = top.s[j];
+            }
+        }
+        const float gm = gmax[0];
+        const float eps = FR_CERT_C * 0x1p-10f * qn * gm + FR_CERT_ABS * (qn + gm) + 0x1p-40f;
+        flags[q] = (!bad && sk > bound + eps) ? 0 : 1;            // a NaN on either side (Gmax = +inf) compares false
+    }
+}
+
+// out[f][:] = exact[f][:] for flagged queries
+__global__ void topk_select_flagged(const int32_t* __restrict__ flags, const int64_t* __restrict__ xi,
+                                    const float* __restrict__ xs, int n, int K, int64_t* __restrict__ out_idx,
+                                    float* __restrict__ out_score) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n && flags[e / K] != 0) { out_idx[e] = xi[e]; out_score[e] = xs[e]; }
+}
+
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// workspace: coarse lists | spill bounds | exact idx [F][K] | exact score [F][K] | the exact scan's own workspace
+struct TopkF16Ws { size_t cand, spill, xi, xs, total; };
+static TopkF16Ws topk_f16_ws(int F, int64_t N, int K) {
+    const ScanPlan pl = scan_plan(F, N);
+    const size_t f = (size_t)(F > 0 ? F : 1), k = (size_t)(K > 0 ? K : 1);
+    TopkF16Ws w;
+    w.cand = up256(f * pl.nranges * 4 * FR_TOPK * 8);
+    w.spill = up256(f * pl.nranges * 4 * sizeof(float));
+    w.xi = up256(f * k * sizeof(int64_t));
+    w.xs = up256(f * k * sizeof(float));
+    w.total = w.cand + w.spill + w.xi + w.xs + fr_gallery_topk_workspace(F, N, K);
+    return w;
+}
+
+extern "C" size_t fr_gallery_topk_f16_workspace(int F, int64_t N, int K) { return topk_f16_ws(F, N, K).total; }
+extern "C" size_t fr_gallery_topk_view_f16_workspace(int F, int64_t Nview, int K) { return topk_f16_ws(F, Nview, K).total; }
+
+template <int KP, bool VIEW>
+static int rerank_topk_launch(const float* Q, const float* G32, const int64_t* view, const float* ws_score, const int* ws_idx,
+                              const float* ws_spill, int F, int64_t N, int K, int ncand, int nlists, int64_t row_offset,
+                              const float* gmax, int64_t* out_idx, float* out_score, int32_t* flags,
+                              const int32_t* seg_counts, int seg_len, hipStream_t s) {
+    const size_t lds = (size_t)ncand * 8 + RerankBudget<KP>::C * sizeof(int);
+    gallery_rerank_topk<KP, VIEW><<<F, 64, lds, s>>>(Q, G32, view, ws_score, ws_idx, ws_spill, N, K, ncand, nlists, row_offset,
+                                                     gmax, out_idx, out_score, flags, seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_rerank_topk");
+    return FR_OK;
+}
+
+template <bool VIEW>
+static int topk_f16_launch(const char* who, const float* Q, const void* G16, const float* G32, const int64_t* view, int F,
+                           int64_t N, int D, int K, int64_t row_offset, const float* gmax, int64_t* out_idx,
+                           float* out_score, int32_t* flags, void* workspace, size_t workspace_bytes,
+                           const int32_t* seg_counts, int seg_len, fr_stream_t stream) {
+    FR_REQUIRE(K >= 1 && K <= FR_TOPK_MAX, "%s: K must be 1..%d (got %d)", who, FR_TOPK_MAX, K);
+    FR_REQUIRE(D == GD, "%s: D must be %d (got %d)", who, GD, D);
+    // 2^28 rows: at most 256 scan ranges, so a query's candidate lists (<= 4096 groups) fit the re-rank's LDS
+    FR_REQUIRE(F >= 0 && N >= 0 && N <= (1ll << 28), "%s: bad size (N must be 0..2^28)", who);
+    FR_REQUIRE(!seg_counts || (seg_len > 0 && F % seg_len == 0), "%s: seg_len must divide F", who);
+    if (F == 0) return FR_OK;
+    FR_REQUIRE(Q && out_idx && out_score && flags && gmax && ((G16 && G32) || N == 0), "%s: null pointer", who);
+    FR_REQUIRE(!VIEW || view || N == 0, "%s: null view", who);
+    const TopkF16Ws w = topk_f16_ws(F, N, K);
+    FR_REQUIRE(workspace && workspace_bytes >= w.total, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, w.total);
+    hipStream_t s = fr_stream(stream);
+    const ScanPlan pl = scan_plan(F, N);
+    const int nlists = N > 0 ? pl.nranges * 4 : 0, ncand = nlists * FR_TOPK;
+    char* base = reinterpret_cast<char*>(workspace);
+    float* ws_score = reinterpret_cast<float*>(base);
+    int* ws_idx = reinterpret_cast<int*>(ws_score + (size_t)F * ncand);
+    float* ws_spill = reinterpret_cast<float*>(base + w.cand);
+    int64_t* xi = reinterpret_cast<int64_t*>(base + w.cand + w.spill);
+    float* xs = reinterpret_cast<float*>(base + w.cand + w.spill + w.xi);
+    void* xws = base + w.cand + w.spill + w.xi + w.xs;
+    if (N > 0) {
+        ScanP p;
+        p.Q = Q; p.G = G16; p.F = F; p.N = N; p.nqt = pl.nqt; p.nranges = pl.nranges; p.rows_per_range = pl.rows_per_range;
+        p.ws_score = ws_score; p.ws_idx = ws_idx; p.seg_counts = seg_counts; p.seg_len = seg_len; p.qscale = 1.0f;
+        p.view = view; p.ws_spill = ws_spill;
+        constexpr int lds = 2 * SG_ROWS * 1024;
+        static FrDevLatch latch;
+        if (!fr_raise_lds(reinterpret_cast<const void*>(gallery_gemm_scan<false, FR_TOPK, VIEW, true>), lds, latch)) {
+            fr_set_error("%s: cannot raise dynamic LDS", who);
+            return FR_E_LAUNCH;
+        }
+        gallery_gemm_scan<false, FR_TOPK, VIEW, true><<<pl.grid, 512, lds, s>>>(p);
+        FR_CHECK_LAUNCH("gallery_gemm_scan");
+    }
+    int rc;
+#define FR_RERANK(KP) rerank_topk_launch<KP, VIEW>(Q, G32, view, ws_score, ws_idx, ws_spill, F, N, K, ncand, nlists, row_offset, \
+                                                   gmax, out_idx, out_score, flags, seg_counts, seg_len, s)
+    if (K <= 2) rc = FR_RERANK(2);
+    else if (K <= 4) rc = FR_RERANK(4);
+    else if (K <= 8) rc = FR_RERANK(8);
+    else rc = FR_RERANK(16);
+#undef FR_RERANK
+    if (rc != FR_OK) return rc;
+    // the exact scan for the flagged queries only (a padding slot is never flagged), then the select
+    const size_t xbytes = workspace_bytes - (w.total - fr_gallery_topk_workspace(F, N, K));
+    rc = VIEW ? fr_gallery_topk_view_masked_f32(Q, G32, view, F, N, D, K, xi, xs, xws, xbytes, flags, stream)
+              : fr_gallery_topk_f32(Q, G32, F, N, D, K, row_offset, xi, xs, xws, xbytes, flags, 1, stream);
+    if (rc != FR_OK) return rc;
+    topk_select_flagged<<<fr_cdiv((int64_t)F * K, 256), 256, 0, s>>>(flags, xi, xs, F * K, K, out_idx, out_score);
+    FR_CHECK_LAUNCH("topk_select_flagged");
+    return FR_OK;
+}
+
+extern "C" int fr_gallery_topk_f16(const float* Q, const void* G16, const float* G32, int F, int64_t N, int D, int K,
+                                   int64_t row_offset, const float* gmax, int64_t* out_idx, float* out_score,
+                                   int32_t* flags, void* workspace, size_t workspace_bytes, const int32_t* seg_counts,
+                                   int seg_len, fr_stream_t stream) {
+    return topk_f16_launch<false>("fr_gallery_topk_f16", Q, G16, G32, nullptr, F, N, D, K, row_offset, gmax, out_idx, out_score,
+                                  flags, workspace, workspace_bytes, seg_counts, seg_len, stream);
+}
+
+extern "C" int fr_gallery_topk_view_f16(const float* Q, const void* S16, const float* G32, const int64_t* view, int F,
+                                        int64_t Nview, int64_t capacity, int D, int K, const float* gmax, int64_t* out_idx,
+                                        float* out_score, int32_t* flags, void* workspace, size_t workspace_bytes,
+                                        fr_stream_t stream) {
+    FR_REQUIRE(capacity >= 0 && capacity < (1ll << 31) && Nview <= capacity,
+               "fr_gallery_topk_view_f16: capacity %lld must be below 2^31 slots and hold the view (%lld rows)",
+               (long long)capacity, (long long)Nview);
+    return topk_f16_launch<true>("fr_gallery_topk_view_f16", Q, S16, G32, view, F, Nview, D, K, 0, gmax, out_idx, out_score,
+                                 flags, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+// Gmax: gmax[0] = max(gmax[0], largest |row| among the n rows G[slots[i]] (slots NULL: rows 0..n)), +inf as soon as a row
+// holds an element that is not finite or overflows f16 (|x| > 65504).  A wave walks rows, 8 elements per lane summed in
+// order, then the xor butterfly of wave_sum; one vector atomicMax per wave on the float's bit pattern (|row| >= 0, so
+// unsigned order is float order).
+__global__ __launch_bounds__(256) void gallery_gmax_update(const float* __restrict__ G, const int64_t* __restrict__ slots,
+                                                           int64_t n, unsigned* __restrict__ gmax) {
+    const int lane = threadIdx.x & 63;
+    float best = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += (int64_t)gridDim.x * 4) {
+        const float* p = G + (slots ? slots[i] : i) * GD;
+        const float4 a = *reinterpret_cast<const float4*>(p + lane * 4), b = *reinterpret_cast<const float4*>(p + 256 + lane * 4);
+        float ss = a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
+        ss += b.x * b.x + b.y * b.y + b.z * b.z + b.w * b.w;
+        const float m = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
+                              fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
+        const bool nan = a.x != a.x || a.y != a.y || a.z != a.z || a.w != a.w || b.x != b.x || b.y != b.y || b.z != b.z || b.w != b.w;
+        const bool bad = __ballot(nan || !(m <= 65504.0f)) != 0;
+        const float nrm = sqrtf(wave_sum(ss));
+        best = (bad || !(nrm < INFINITY)) ? INFINITY : fmaxf(best, nrm);
+    }
+    if (lane == 0 && best > 0.f) atomicMax(gmax, __float_as_uint(best));
+}
+
+extern "C" int fr_gallery_gmax_update(const float* G, const int64_t* slots, int64_t n, int D, float* gmax, fr_stream_t stream) {
+    FR_REQUIRE(D == GD, "fr_gallery_gmax_update: D must be %d (got %d)", GD, D);
+    FR_REQUIRE(n >= 0, "fr_gallery_gmax_update: negative size");
+    if (n == 0) return FR_OK;
+    FR_REQUIRE(G && gmax, "fr_gallery_gmax_update: null pointer");
+    int64_t blocks = (n + 3) / 4;
+    if (blocks > 2048) blocks = 2048;
+    gallery_gmax_update<<<(int)blocks, 256, 0, fr_stream(stream)>>>(G, slots, n, reinterpret_cast<unsigned*>(gmax));
+    FR_CHECK_LAUNCH("gallery_gmax_update");
     return FR_OK;
 }

@@ -18,6 +18,17 @@ TOPK_MAX = 16                  # include/frhip.h FR_TOPK_MAX
 SCANS = ("f32", "f16", "f8")
 _SHADOW_KIND = {"f16": 1, "f8": 2}      # include/frhip.h FR_SHADOW_F16 / FR_SHADOW_F8
 _PIN = threading.local()       # pinned host buffers of GalleryMatcher.match, per thread and query count
+_TLS = threading.local()       # .topk: what this thread's last top-K call ran (last_topk())
+# Rows from which an f16-coarse gallery answers top-K by the certified coarse pass instead of the exact scan.  Not yet
+# measured on hardware for the top-K path: the size where the top-1 coarse view scan won (profiles/view_scan.txt).
+COARSE_TOPK_MIN_ROWS = 100_000
+
+
+def last_topk():
+    """What the calling thread's last ``match_topk_device`` ran, without a synchronisation: {"path": "coarse" | "exact",
+    "flags": device int32 [F] or None}.  On the coarse path flags[f] is 0 where the coarse pass was certified to give the
+    exact top-K and 1 where query f was answered by the exact scan instead; both give the same bits."""
+    return getattr(_TLS, "topk", None)
 
 
 class StaleViewError(_lib.FrError):
@@ -38,13 +49,18 @@ class GalleryMatcher:
             raise ValueError("scan must be 'f32', 'f16' or 'f8'")
         self.f16_scan = self.scan == "f16"
         self.G16 = None                       # the coarse copy (f16 or fp8 e4m3 x 256)
+        self.coarse_topk_min_rows = COARSE_TOPK_MIN_ROWS
         self.lib = _lib.load()
         self.device = torch.device(device)
         self.ids = []
         self.G = torch.empty((0, DIM), dtype=torch.float32, device=self.device)
+        # scan="f16": the largest row norm in G (+inf: a row the f16 copy cannot hold), for the top-K certificate
+        self.gmax = torch.zeros(1, dtype=torch.float32, device=self.device) if self.scan == "f16" else None
 
     def __len__(self):
         return self.G.shape[0]
+
+    last_topk = property(lambda self: last_topk())
 
     def set_rows(self, ids, rows, normalise=True):
         """rows: float32 [N,512] (host or device).  ``normalise`` applies v/||v|| on the
@@ -66,6 +82,9 @@ class GalleryMatcher:
                 if self.scan == "f16":
                     self.G16 = torch.empty(rows.shape, dtype=torch.float16, device=self.device)
                     self.lib.fr_f32_to_f16(_lib.ptr(rows), _lib.ptr(self.G16), rows.numel(), _lib.stream_ptr())
+                    self.gmax = torch.zeros(1, dtype=torch.float32, device=self.device)      # a new gallery: a new bound
+                    self.lib.fr_gallery_gmax_update(_lib.ptr(rows), None, rows.shape[0], DIM, _lib.ptr(self.gmax),
+                                                    _lib.stream_ptr())
                 else:
                     self.G16 = torch.empty(rows.shape, dtype=torch.uint8, device=self.device)
                     self.lib.fr_f32_to_f8(_lib.ptr(rows), _lib.ptr(self.G16), rows.numel(), _lib.stream_ptr())
@@ -111,10 +130,17 @@ class GalleryMatcher:
     def match_topk_device(self, Q, k, renormalise=True, row_offset=0, counts=None, seg_len=0):
         """The ``k`` best rows per query (1 <= k <= 16): device tensors (idx int64[F,k], score float32[F,k]), ranked by
         score descending, row ascending, among rows scoring > -1; slots past the number of such rows hold (-1, -1.0).
-        Column 0 is bit-identical to ``match_device``.  Always the exact f32 scan over the f32 rows, whatever ``scan``
-        the matcher was built with.  ``row_offset`` / ``counts`` / ``seg_len``: as ``match_device``."""
+        Column 0 is bit-identical to ``match_device``.  The result is that of the exact f32 scan over the f32 rows,
+        bit for bit, whatever ``scan`` the matcher was built with.  scan="f16" with at least ``coarse_topk_min_rows``
+        rows gets it from the certified coarse pass (one pass over the f16 rows, exact f32 re-scoring of the best
+        groups, the exact scan only for queries the certificate refuses: DESIGN.md 4.6b); "f32", "f8" and smaller
+        galleries run the exact scan.  ``last_topk`` tells which.  ``row_offset`` / ``counts`` / ``seg_len``: as
+        ``match_device``."""
         k = _check_k(k)
-        return _topk_device(self, Q, k, renormalise, None, self.G, self.G.shape[0], row_offset, counts, seg_len)
+        coarse = None
+        if self.scan == "f16" and self.G16 is not None and self.G.shape[0] >= self.coarse_topk_min_rows:
+            coarse = (self.G16, self.gmax, 0)
+        return _topk_device(self, Q, k, renormalise, None, self.G, self.G.shape[0], row_offset, counts, seg_len, coarse)
 
     def match_topk(self, Q, k, min_score=None):
         """Host-facing: (ids, scores float32[F,k], idx int64[F,k]); ``ids[f]`` is a list of k entries in rank order,
@@ -173,13 +199,15 @@ def _check_k(k):
     return int(k)
 
 
-def _topk_device(owner, Q, k, renormalise, view, G, N, row_offset=0, counts=None, seg_len=0):
-    """fr_gallery_topk_f32 (``view`` None) / fr_gallery_topk_view_f32 on the current stream of ``owner.device``."""
+def _topk_device(owner, Q, k, renormalise, view, G, N, row_offset=0, counts=None, seg_len=0, coarse=None):
+    """fr_gallery_topk_f32 (``view`` None) / fr_gallery_topk_view_f32 on the current stream of ``owner.device``;
+    ``coarse`` = (f16 rows, gmax, capacity): fr_gallery_topk_f16 / _view_f16 instead.  Records ``last_topk()``."""
     lib, dev = owner.lib, owner.device
     Q = Q.to(dev, torch.float32).contiguous().reshape(-1, DIM)
     F = Q.shape[0]
     idx = torch.empty((F, k), dtype=torch.int64, device=dev)
     score = torch.empty((F, k), dtype=torch.float32, device=dev)
+    _TLS.topk = {"path": "exact" if coarse is None else "coarse", "flags": None}
     if F == 0:
         return idx, score
     with torch.cuda.device(dev):
@@ -188,14 +216,28 @@ def _topk_device(owner, Q, k, renormalise, view, G, N, row_offset=0, counts=None
             Qn = torch.empty_like(Q)
             lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
             Q = Qn
+        cp = _lib.ptr(counts) if counts is not None else None
+        if counts is not None:
+            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
+        if coarse is not None:
+            G16, gmax, capacity = coarse
+            flags = _TLS.topk["flags"] = torch.empty(F, dtype=torch.int32, device=dev)
+            if view is not None:
+                ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_view_f16_workspace(F, N, k))
+                lib.fr_gallery_topk_view_f16(_lib.ptr(Q), _lib.ptr(G16), _lib.ptr(G), _lib.ptr(view), F, N, capacity, DIM, k,
+                                             _lib.ptr(gmax), _lib.ptr(idx), _lib.ptr(score), _lib.ptr(flags), _lib.ptr(ws),
+                                             ws.numel(), s)
+            else:
+                ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_f16_workspace(F, N, k))
+                lib.fr_gallery_topk_f16(_lib.ptr(Q), _lib.ptr(G16), _lib.ptr(G), F, N, DIM, k, row_offset, _lib.ptr(gmax),
+                                        _lib.ptr(idx), _lib.ptr(score), _lib.ptr(flags), _lib.ptr(ws), ws.numel(), cp,
+                                        seg_len, s)
+            return idx, score
         ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_workspace(F, N, k))
         if view is not None:
             lib.fr_gallery_topk_view_f32(_lib.ptr(Q), _lib.ptr(G), _lib.ptr(view), F, N, DIM, k, _lib.ptr(idx),
                                          _lib.ptr(score), _lib.ptr(ws), ws.numel(), s)
             return idx, score
-        cp = _lib.ptr(counts) if counts is not None else None
-        if counts is not None:
-            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
         lib.fr_gallery_topk_f32(_lib.ptr(Q), _lib.ptr(G), F, N, DIM, k, row_offset, _lib.ptr(idx), _lib.ptr(score),
                                 _lib.ptr(ws), ws.numel(), cp, seg_len, s)
     return idx, score
@@ -215,7 +257,10 @@ class DeviceGallery:
     ``scan``: "f32" (default), "f16" or "f8", spelt and meant as ``GalleryMatcher``'s.  With "f16" / "f8" the gallery
     keeps a coarse shadow slab ``S`` beside ``G`` (f16, or fp8 e4m3 x 256: 1 KB / 0.5 KB more per slot) that every
     ``upsert`` writes in the same launch as the f32 rows, and views match by the one-pass coarse scan through the slot
-    list with the exact f32 re-rank: the ids are those of the f32 scan.  For large galleries / many queries.
+    list with the exact f32 re-rank: the ids are those of the f32 scan.  For large galleries / many queries.  With "f16" a view of
+    at least ``coarse_topk_min_rows`` rows also answers top-K from the coarse slab, certified per query to be the exact
+    f32 top-K (``GalleryMatcher.match_topk_device``); ``gmax`` is the largest row norm ever written to the slab (it
+    never shrinks on ``remove``).
     """
 
     def __init__(self, device="cuda:0", capacity=1024, scan="f32"):
@@ -231,6 +276,8 @@ class DeviceGallery:
         self._free = []                  # freed slots, reused LIFO
         self._next = 0                   # first never-used slot
         self.generation = 0              # bumps on every membership change (views check it)
+        self.coarse_topk_min_rows = COARSE_TOPK_MIN_ROWS
+        self.gmax = torch.zeros(1, dtype=torch.float32, device=self.device) if scan == "f16" else None
 
     def __len__(self):
         return len(self.slot_of)
@@ -292,6 +339,9 @@ class DeviceGallery:
                 self.lib.fr_gallery_update_rows_shadow(_lib.ptr(self.G), _lib.ptr(self.S), _SHADOW_KIND[self.scan],
                                                        _lib.ptr(slots), _lib.ptr(rows), len(ids), DIM,
                                                        1 if normalise else 0, _lib.stream_ptr())
+                if self.gmax is not None:                # the norms of the rows as stored, on the stream that wrote them
+                    self.lib.fr_gallery_gmax_update(_lib.ptr(self.G), _lib.ptr(slots), len(ids), DIM, _lib.ptr(self.gmax),
+                                                    _lib.stream_ptr())
 
     def remove(self, ids):
         n = 0
@@ -358,12 +408,19 @@ class GalleryView:
         return idx, score
 
     def match_topk_device(self, Q, k, renormalise=True):
-        """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``.  Always the exact f32 scan over the
-        f32 rows, whatever ``scan`` the gallery was built with (there is no coarse top-K)."""
+        """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``.  The bits of the exact f32 scan
+        over the f32 rows, whatever ``scan`` the gallery was built with: a view of at least
+        ``gallery.coarse_topk_min_rows`` rows of a scan="f16" gallery gets them from the certified coarse pass through
+        the slot list, every other view from the exact scan (``last_topk`` tells which)."""
         k = _check_k(k)
         if self.generation != self.gallery.generation:
             raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
-        return _topk_device(self, Q, k, renormalise, self.slots, self.gallery.G, len(self.ids))
+        g, coarse = self.gallery, None
+        if g.scan == "f16" and len(self.ids) >= g.coarse_topk_min_rows:
+            coarse = (g.S, g.gmax, g.capacity)
+        return _topk_device(self, Q, k, renormalise, self.slots, g.G, len(self.ids), coarse=coarse)
+
+    last_topk = property(lambda self: last_topk())
 
     decide_device = GalleryMatcher.decide_device
     match = GalleryMatcher.match

@@ -134,6 +134,37 @@ size_t fr_gallery_match_view_f8_workspace(int F, int64_t Nview);
 int fr_gallery_match_view_f8(const float* Q, const void* S8, const float* G32, const int64_t* view, int F,
                              int64_t Nview, int64_t capacity, int D, int64_t* out_idx, float* out_score,
                              void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* Certified coarse top-K: fr_gallery_topk_f32 / _view_f32's result, bit for bit, from ONE pass over the f16 rows on the
+ * matrix cores wherever that pass provably suffices, from the exact scan for every other query - decided per query on
+ * the device.  The coarse pass keeps, per query, candidate groups of 4 consecutive rows and a bound on the coarse score
+ * of every row it did not keep; the re-rank re-scores the rows of the best groups with the exact scan's own f32 dot
+ * product (same bits), and certifies a query iff its K-th exact score exceeds every unseen row's coarse bound by more
+ * than eps = 1.125 * 2^-10 * |q| * Gmax + 2^-20 * (|q| + Gmax) + 2^-40, a proven bound of |coarse - exact| (DESIGN.md
+ * 4.6b).  flags (device int32 [F]): 0 = certified, 1 = answered by the exact scan (also: any query with a non-finite
+ * element or one beyond the f16 range).  Queries that are flagged cost an exact scan; when none is, the exact launch
+ * finds no work.
+ * gmax: device float [1], an upper bound of the largest row norm in G32 / the slab; fr_gallery_gmax_update raises it
+ * to cover rows G[slots[0..n)] (slots NULL: rows 0..n) and sets it to +inf when a row holds a non-finite element or
+ * one that overflows f16 (|x| > 65504) - then nothing certifies.  It never shrinks: start it at 0, call the update on
+ * the stream that wrote the rows.
+ * Contract, arguments and limits otherwise as fr_gallery_topk_f32 / fr_gallery_topk_view_f32 and
+ * fr_gallery_match_f16 / _view_f16 (G16 / S16: fr_f32_to_f16 of the f32 rows), and N <= 2^28 rows.
+ * fr_gallery_topk_view_masked_f32: fr_gallery_topk_view_f32 for the queries f with mask[f] > 0 (device int32 [F]; NULL:
+ * all); the others cost no scan work and report (-1, -1.0f). */
+size_t fr_gallery_topk_f16_workspace(int F, int64_t N, int K);
+int fr_gallery_topk_f16(const float* Q, const void* G16, const float* G32, int F, int64_t N, int D, int K,
+                        int64_t row_offset, const float* gmax, int64_t* out_idx, float* out_score, int32_t* flags,
+                        void* workspace, size_t workspace_bytes, const int32_t* seg_counts, int seg_len,
+                        fr_stream_t stream);
+size_t fr_gallery_topk_view_f16_workspace(int F, int64_t Nview, int K);
+int fr_gallery_topk_view_f16(const float* Q, const void* S16, const float* G32, const int64_t* view, int F,
+                             int64_t Nview, int64_t capacity, int D, int K, const float* gmax, int64_t* out_idx,
+                             float* out_score, int32_t* flags, void* workspace, size_t workspace_bytes,
+                             fr_stream_t stream);
+int fr_gallery_topk_view_masked_f32(const float* Q, const float* G, const int64_t* view, int F, int64_t Nview, int D,
+                                    int K, int64_t* out_idx, float* out_score, void* workspace,
+                                    size_t workspace_bytes, const int32_t* mask, fr_stream_t stream);
+int fr_gallery_gmax_update(const float* G, const int64_t* slots, int64_t n, int D, float* gmax, fr_stream_t stream);
 /* f32 -> fp8 e4m3 row conversion (x * FR_F8_SCALE, round to nearest even, n % 4 == 0) */
 int fr_f32_to_f8(const float* x, void* out, int64_t n, fr_stream_t stream);
 /* f32 -> f16 row conversion for building the device-resident gallery (infrenceServer.py:271) */
