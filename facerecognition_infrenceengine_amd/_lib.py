@@ -164,6 +164,12 @@ SIGNATURES = {
     "fr_crop_resize_norm": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "fr_stage_select": (_I, [_P, _P, _I, _P, _I, _I, _F, _P, _P, _P, _I, _P, _P, _P]),
     "fr_detect_sequence": (_I, [C.POINTER(Call), _I]),
+    "fr_det_conv_weight_halves": (_Z, [_I, _I, _I]),
+    "fr_det_conv_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fr_det_input_f16": (_I, [_P, _P, _I, _I, _I, _P]),
+    "fr_det_pool_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fr_det_upsample_add_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "fr_scrfd_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _P]),
 }
 
 _NOCHECK = ("fr_version", "fr_device_count")

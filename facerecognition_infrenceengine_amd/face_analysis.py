@@ -53,8 +53,13 @@ class FaceAnalysis:
     and ``mtcnn_{pnet,rnet,onet}.pt`` state dicts (public PyTorch naming, see weights.py).  A recognition network
     shipped as ONNX - the ``w600k_r50.onnx`` of the reference's own buffalo_l pack - is read too (onnx_import.py: the
     first ``*.onnx`` of the directory whose graph is an ArcFace IResNet; ``arch`` then follows the file).  The pack's
-    detector is SCRFD, not MTCNN: without ``mtcnn_*.pt`` files the detector falls back to synthetic weights.  When the
-    directory is absent the engine falls back to SEEDED SYNTHETIC weights and says so loudly:
+    detector (``det_10g.onnx``, SCRFD) is read too when the directory holds no ``mtcnn_*.pt`` files: the first ``*.onnx``
+    that ``onnx_import.scrfd_plan_from_onnx`` accepts becomes a ``scrfd.SCRFDHIP`` detector on a 640 x 640 canvas unless
+    ``prepare`` is given another ``det_size``; with neither, MTCNN runs on synthetic weights.  The detector keywords of the
+    constructor (``minsize``, ``factor``, ``thresholds``, ``cap_scale``, ``keep_scale``, ``cap_p``, ``cap_r``, ``cap_o``) are
+    MTCNN's.  Under a SCRFD detector ``cap_p`` is its ``cap`` (candidates kept per level and frame in front of NMS, at most
+    1365: 3 * cap <= 4096, a larger value raises ValueError) and ``cap_o`` its ``cap_out`` (faces per frame); the others have
+    no counterpart and are ignored with a warning - the score threshold is ``prepare(det_thresh=...)``.  When the directory is absent the engine falls back to SEEDED SYNTHETIC weights and says so loudly:
     the pipeline is then numerically exact w.r.t. its oracle but recognises nothing.
     ``providers`` is accepted for signature compatibility and ignored (HIP only).
     """
@@ -68,6 +73,7 @@ class FaceAnalysis:
                                                   "cap_p", "cap_r", "cap_o") if k in kwargs}
         self.synthetic = None
         self.det_size = None
+        self._scrfd_graph = None              # the pack's SCRFD detector graph, when _load_states found one and no mtcnn_*.pt
 
     def _load_states(self):
         d = _model_dir(self.name, self.root)
@@ -79,17 +85,20 @@ class FaceAnalysis:
             ps = [os.path.join(d, f"mtcnn_{n}{ext}") for n in ("pnet", "rnet", "onet")]
             if det is None and all(os.path.exists(q) for q in ps):
                 det = tuple(weights.load_state(q) for q in ps)
+        parsed = {}                                        # file name -> graph (or None: the recognition network's), read once
         if rec is None and os.path.isdir(d):              # insightface packs ship the recognition network as ONNX
-            from .onnx_import import iresnet_state_from_onnx
+            from .onnx_import import iresnet_state_from_onnx, read_onnx
             skipped = []
             for fn in sorted(os.listdir(d)):
                 if fn.endswith(".onnx"):
                     try:
-                        st, arch = iresnet_state_from_onnx(os.path.join(d, fn))
+                        parsed[fn] = read_onnx(os.path.join(d, fn))
+                        st, arch = iresnet_state_from_onnx(parsed[fn])
                     except Exception as e:                 # the pack's detector / landmark / attribute models, or a
                         skipped.append(f"{fn}: {type(e).__name__}: {e}")      # graph this reader cannot map
                         continue
                     rec, self.arch = {k: torch.from_numpy(v) for k, v in st.items()}, arch
+                    parsed[fn] = None
                     break
             for why in skipped:
                 logging.getLogger(__name__).info("model pack '%s': skipped %s", self.name, why)
@@ -98,12 +107,47 @@ class FaceAnalysis:
                 # recognition weights here would silently recognise nobody
                 raise _lib.FrError(f"model pack '{self.name}' under {d}: none of its .onnx files is a readable ArcFace "
                                    "IResNet (" + "; ".join(skipped) + ")")
+        self._scrfd_graph = self._find_scrfd(d, parsed) if det is None and os.path.isdir(d) else None
+        if self._scrfd_graph is not None:
+            # rec is never None here: a directory that holds .onnx files of which none is an ArcFace IResNet raised above,
+            # and one without .onnx files holds no SCRFD graph
+            self.synthetic = False
+            return (rec, None)
         self.synthetic = rec is None or det is None
         if self.synthetic:
             missing = " and ".join(w for w, x in (("recognition", rec), ("MTCNN detector", det)) if x is None)
             warnings.warn(f"model pack '{self.name}' under {d}: no {missing} weights found: using SEEDED SYNTHETIC "
                           f"weights for them (numerically exact pipeline, meaningless identities)")
         return (rec or weights.synth_iresnet_state(self.arch), det or weights.synth_mtcnn_states())
+
+    def _find_scrfd(self, d, parsed):
+        """The graph of the first ``*.onnx`` under d that is a SCRFD detector with keypoints, or None; the others are
+        skipped with their reason at INFO.  ``parsed``: the graphs _load_states has read already (None: the file it took as
+        the recognition network, which is not looked at again)."""
+        from .onnx_import import read_onnx, scrfd_plan_from_onnx
+        for fn in sorted(os.listdir(d)):
+            if fn.endswith(".onnx") and parsed.get(fn, fn) is not None:
+                try:
+                    g = parsed.get(fn) or read_onnx(os.path.join(d, fn))
+                    scrfd_plan_from_onnx(g, (640, 640))
+                    return g
+                except Exception as e:
+                    logging.getLogger(__name__).info("model pack '%s': %s is no SCRFD detector: %s: %s", self.name, fn,
+                                                     type(e).__name__, e)
+        return None
+
+    def _make_detector(self, det_kwargs, det_thresh=None, share=None):
+        from .mtcnn import MTCNNHIP
+        if self._scrfd_graph is None:
+            return MTCNNHIP(*self._det_states, device=self.device, **det_kwargs)
+        from .scrfd import SCRFDHIP
+        # the detector keywords are MTCNN's; two have a SCRFD meaning (class docstring), the others none
+        kw = {new: det_kwargs[old] for old, new in (("cap_p", "cap"), ("cap_o", "cap_out")) if old in det_kwargs}
+        ignored = sorted(k for k in det_kwargs if k not in ("cap_p", "cap_o"))
+        if ignored:
+            warnings.warn(f"model pack '{self.name}': its detector is SCRFD, which ignores the MTCNN keyword(s) {', '.join(ignored)} "
+                          "(the score threshold is prepare(det_thresh=...))")
+        return SCRFDHIP(self._scrfd_graph, device=self.device, det_thresh=0.5 if det_thresh is None else det_thresh, share=share, **kw)
 
     def prepare(self, ctx_id=0, det_thresh=None, det_size=None):
         """``ctx_id`` = HIP device ordinal (infrenceServer.py:416).
@@ -115,16 +159,24 @@ class FaceAnalysis:
         ``minsize`` and the pyramid then apply to CANVAS pixels: a 20-pixel minimum face on the 640 x 360 image of a 1080p
         frame is 60 pixels in the frame.  Detector cost no longer grows with the camera's resolution, and frames of
         differing sizes go through one call (``get_batch`` / ``detect_embed_*`` take a list of them).
-        ``det_size=None`` (default): MTCNN walks the full pyramid of the full frame, and a batch is frames of one size."""
+        ``det_size=None`` (default): MTCNN walks the full pyramid of the full frame, and a batch is frames of one size.
+
+        A pack whose detector is a SCRFD ONNX file (no ``mtcnn_*.pt``): ``det_size=None`` means (640, 640), insightface's
+        default, both sides multiples of 32; ``det_thresh`` (default 0.5) is the score threshold.  MTCNN takes its
+        thresholds from the constructor and ignores ``det_thresh``, as before."""
         from .iresnet import IResNetHIP
-        from .mtcnn import MTCNNHIP
         _lib.require_gpu()
         self.det_size = check_det_size(det_size)
         self.device = torch.device(f"cuda:{max(int(ctx_id), 0)}")
         rec, det = self._load_states()
         self._det_states = det
+        if self._scrfd_graph is not None:
+            self.det_size = self.det_size or (640, 640)
+            if self.det_size[0] % 32 or self.det_size[1] % 32:
+                raise ValueError(f"det_size {self.det_size}: the SCRFD detector needs both sides in multiples of 32")
+        self._det_thresh = det_thresh
         self.rec = IResNetHIP(rec, self.arch, self.device)
-        self.det = MTCNNHIP(*det, device=self.device, **self.det_kwargs)
+        self.det = self._make_detector(self.det_kwargs, det_thresh)
         self.lib = _lib.load()
         self._use_graphs, self._graphs = False, {}
         return self
@@ -155,7 +207,6 @@ class FaceAnalysis:
         """A second engine on the same device that SHARES this one's embed network (weights resident once) and
         has its own detector with other capacities / thresholds (e.g. ``cap_o=1`` for single-face frames).  It keeps this
         engine's ``det_size`` unless one is given (``None``: no detection canvas)."""
-        from .mtcnn import MTCNNHIP
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         other = FaceAnalysis(self.name, self.root, providers=self.providers, arch=self.arch)
@@ -163,7 +214,13 @@ class FaceAnalysis:
         other._det_states = self._det_states
         other.det_size = self.det_size if isinstance(det_size, str) and det_size == "same" else check_det_size(det_size)
         other.det_kwargs = {**self.det_kwargs, **det_kwargs}
-        other.det = MTCNNHIP(*self._det_states, device=self.device, **other.det_kwargs)
+        other._scrfd_graph, other._det_thresh = self._scrfd_graph, getattr(self, "_det_thresh", None)
+        if self._scrfd_graph is not None:
+            if other.det_size is None or other.det_size[0] % 32 or other.det_size[1] % 32:
+                raise ValueError(f"det_size {other.det_size}: the SCRFD detector needs a canvas with both sides in multiples of 32")
+            other.det = other._make_detector(other.det_kwargs, other._det_thresh, share=self.det)      # packed weights resident once
+        else:
+            other.det = other._make_detector(other.det_kwargs)
         other._use_graphs, other._graphs = False, {}
         other._shares_rec = self._shares_rec = True          # neither engine may free the shared network's plans
         return other
@@ -239,6 +296,9 @@ class FaceAnalysis:
                 raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
             boxes, scores, kps, counts = self.det.detect_batch(frames)
             return boxes, scores, kps.contiguous() if contiguous_kps else kps, counts
+        if self._scrfd_graph is not None:               # SCRFD divides by det_scale in its decode, in front of NMS (frame pixels)
+            with torch.cuda.device(self.device):
+                return self.det.detect_batch(self._canvas(src), src.det_scale)
         with torch.cuda.device(self.device):
             boxes, scores, kps, counts = self.det.detect_batch(self._canvas(src))
             boxes, kps = boxes.contiguous(), kps.contiguous()

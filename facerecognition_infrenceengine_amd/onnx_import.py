@@ -341,3 +341,342 @@ def iresnet_state_from_onnx(path_or_graph):
     if b is not None:
         take_bn(b, "features")
     return st, arch
+
+
+# --------------------------------------------------------------------------- SCRFD graph -> device plan
+
+class ScrfdPlan:
+    """What ``scrfd_plan_from_onnx`` returns for one canvas size.
+
+    steps    device steps in execution order, dicts with ``op`` in
+             ``input``  (out)                                       the canvas as tensor 0
+             ``conv``   (x, out, w, b, wkey, k, stride, pad, relu, res, f32)   w [Cout,Cin,k,k] / b [Cout] float64, BN / Mul folded
+             ``pool``   (x, out, kind, k, stride, pad)              kind 0 max, 1 average
+             ``upadd``  (coarse, lateral, out, up)                  lateral + nearest x up of coarse
+    shapes   tensor id -> (C, H, W), the channel count unpadded
+    levels   three dicts (stride, score, bbox, kps: tensor ids of f32 head maps read flat as [H*W*A, 1 | 4 | 10]), strides 8, 16, 32
+    outputs  the nine graph output names in graph order -> (level index, kind)
+    """
+
+    def __init__(self, canvas_hw, steps, shapes, levels, num_anchors, outputs):
+        self.canvas_hw, self.steps, self.shapes, self.levels = tuple(canvas_hw), steps, shapes, levels
+        self.num_anchors, self.outputs = num_anchors, outputs
+        self.macs2 = sum(2 * shapes[s["out"]][1] * shapes[s["out"]][2] * int(np.prod(s["w"].shape))
+                         for s in steps if s["op"] == "conv")
+
+
+_CAST = {1: np.float32, 6: np.int32, 7: np.int64, 11: np.float64}
+_NEAREST_OK = {("asymmetric", "floor"), ("asymmetric", "round_prefer_floor"), ("half_pixel", "round_prefer_floor"),
+               ("pytorch_half_pixel", "round_prefer_floor")}
+
+
+def _text(v, default):
+    return default if v is None else (bytes(v).decode() if not isinstance(v, str) else v)
+
+
+def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
+    """Map a SCRFD detector graph (insightface's ``det_*.onnx``: conv backbone, FPN, three strides of score / bbox / kps
+    heads) onto device steps by following the data flow.  ``canvas_hw`` = (height, width), multiples of 32: shape
+    arithmetic of dynamic-shape exports is evaluated on the host for it.  Raises ValueError naming the node and op it cannot
+    map; a graph is mapped whole or not at all."""
+    g = path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph)
+    ch, cw = int(canvas_hw[0]), int(canvas_hw[1])
+    if ch <= 0 or cw <= 0 or ch % 32 or cw % 32:
+        raise ValueError(f"canvas {ch} x {cw}: sides must be positive multiples of 32")
+    if len(g.inputs) != 1:
+        raise ValueError(f"expected one graph input, found {g.inputs}")
+    consumers = {}
+    for n in g.nodes:
+        for t in n.inputs:
+            if t:
+                consumers.setdefault(t, []).append(n)
+    host = dict(g.initializers)          # tensor name -> numpy value known on the host
+    dev = {g.inputs[0]: 0}               # tensor name -> device tensor id
+    shapes = {0: (3, ch, cw)}
+    steps = [{"op": "input", "out": 0}]
+    producer = {}                        # tensor id -> its conv step (only while more may be folded into it)
+    resized = {}                         # tensor name -> (source tensor id, factor): a Resize waiting for its Add
+    nhwc, flat, sigm = {}, {}, {}        # tail views: name -> tensor id / (tensor id, K) / (tensor id, K)
+
+    def who(n):
+        return f"node {n.name or (n.outputs[0] if n.outputs else '?')!r} ({n.op})"
+
+    def new(shape):
+        tid = len(shapes)
+        shapes[tid] = shape
+        return tid
+
+    def sole(n, t):
+        return len(consumers.get(t, [])) == 1 and consumers[t][0] is n
+
+    def open_conv(n, t):
+        """the conv step that produced device tensor name t, when n is its only reader"""
+        st = producer.get(dev.get(t))
+        return st if st is not None and sole(n, t) else None
+
+    def sym(n, key, k):
+        p = list(n.attrs.get(key, [0, 0, 0, 0]))
+        if len(p) != 4 or len(set(p)) != 1:
+            raise ValueError(f"{who(n)}: pads {p} are not symmetric")
+        return int(p[0])
+
+    def square(n, key, default=None):
+        v = n.attrs.get(key, default)
+        if v is None or len(v) != 2 or v[0] != v[1]:
+            raise ValueError(f"{who(n)}: {key} {v} is not square")
+        return int(v[0])
+
+    def host_eval(n):
+        a = [host[t] if t else None for t in n.inputs]
+        op = n.op
+        if op == "Gather":
+            return np.take(a[0], np.asarray(a[1]).astype(np.int64), axis=int(n.attrs.get("axis", 0)))
+        if op == "Slice":
+            data = np.asarray(a[0])
+            if len(a) > 1:
+                starts, ends = a[1], a[2]
+                axes = a[3] if len(a) > 3 and a[3] is not None else np.arange(len(starts))
+                stp = a[4] if len(a) > 4 and a[4] is not None else np.ones(len(starts), np.int64)
+            else:
+                starts, ends = n.attrs["starts"], n.attrs["ends"]
+                axes, stp = n.attrs.get("axes", list(range(len(starts)))), [1] * len(starts)
+            sl = [slice(None)] * data.ndim
+            for s, e, ax, sp in zip(np.ravel(starts), np.ravel(ends), np.ravel(axes), np.ravel(stp)):
+                sl[int(ax)] = slice(int(s), int(min(e, 2 ** 62)), int(sp))
+            return data[tuple(sl)]
+        if op == "Concat":
+            return np.concatenate([np.atleast_1d(x) for x in a], axis=int(n.attrs.get("axis", 0)))
+        if op in ("Unsqueeze", "Squeeze"):
+            axes = n.attrs.get("axes")
+            if axes is None and len(a) > 1:
+                axes = [int(x) for x in np.ravel(a[1])]
+            x = np.asarray(a[0])
+            if op == "Squeeze":
+                return np.squeeze(x, axis=tuple(axes) if axes else None)
+            for ax in sorted(axes):
+                x = np.expand_dims(x, ax)
+            return x
+        if op == "Cast":
+            to = n.attrs.get("to")
+            if to not in _CAST:
+                raise ValueError(f"{who(n)}: cast to ONNX data type {to} not supported")
+            return np.asarray(a[0]).astype(_CAST[to])
+        if op in ("Mul", "Add", "Sub"):
+            return {"Mul": np.multiply, "Add": np.add, "Sub": np.subtract}[op](a[0], a[1])
+        if op == "Div":
+            x, y = np.asarray(a[0]), np.asarray(a[1])
+            return x // y if x.dtype.kind in "iu" and y.dtype.kind in "iu" else x / y
+        if op in ("Floor", "Ceil"):
+            return (np.floor if op == "Floor" else np.ceil)(a[0])
+        if op == "Identity":
+            return a[0]
+        raise ValueError(f"{who(n)}: op {n.op} is not supported (on constant inputs)")
+
+    for n in g.nodes:
+        ins = [t for t in n.inputs if t]
+        if not n.outputs:
+            raise ValueError(f"{who(n)}: node without outputs")
+        out = n.outputs[0]
+        if n.op == "Shape" and ins and ins[0] in dev:
+            c, h, w = shapes[dev[ins[0]]]
+            host[out] = np.array([1, c, h, w], dtype=np.int64)
+            continue
+        if ins and all(t in host for t in ins):
+            host[out] = host_eval(n)
+            continue
+        if n.op == "Conv":
+            if ins[0] not in dev or ins[1] not in host:
+                raise ValueError(f"{who(n)}: conv input / weight is not a feature map / an initialiser")
+            w = np.asarray(host[ins[1]], dtype=np.float64)
+            c, h, wd = shapes[dev[ins[0]]]
+            if n.attrs.get("group", 1) != 1:
+                raise ValueError(f"{who(n)}: grouped conv (group {n.attrs['group']}) is not supported")
+            k = square(n, "kernel_shape", list(w.shape[2:]))
+            s = square(n, "strides", [1, 1])
+            p = sym(n, "pads", k)
+            if w.ndim != 4 or w.shape[1] != c or w.shape[2] != k or w.shape[3] != k or k not in (1, 3) or s not in (1, 2) \
+                    or p >= k or list(n.attrs.get("dilations", [1, 1])) != [1, 1]:
+                raise ValueError(f"{who(n)}: conv weight {w.shape} kernel {k} stride {s} pad {p} on {c} channels is not a "
+                                 "1x1 / 3x3, stride 1 / 2, undilated conv of its input")
+            b = np.asarray(host[ins[2]], dtype=np.float64).reshape(-1) if len(ins) > 2 else np.zeros(w.shape[0])
+            if len(ins) > 2 and ins[2] not in host:
+                raise ValueError(f"{who(n)}: conv bias is not an initialiser")
+            tid = new((w.shape[0], (h + 2 * p - k) // s + 1, (wd + 2 * p - k) // s + 1))
+            st = {"op": "conv", "x": dev[ins[0]], "out": tid, "w": w, "b": b, "wkey": (ins[1], ins[2] if len(ins) > 2 else None),
+                  "k": k, "stride": s, "pad": p, "relu": False, "res": None, "f32": False}
+            steps.append(st)
+            producer[tid] = st
+            dev[out] = tid
+        elif n.op == "BatchNormalization":
+            st = open_conv(n, ins[0])
+            if st is None or st["relu"] or st["res"] is not None:
+                raise ValueError(f"{who(n)}: BatchNormalization that does not directly follow a Conv")
+            sc, bi, mu, var = (np.asarray(host[t], dtype=np.float64).reshape(-1) for t in ins[1:5])
+            f = sc / np.sqrt(var + float(n.attrs.get("epsilon", 1e-5)))
+            st["w"], st["b"] = st["w"] * f[:, None, None, None], (st["b"] - mu) * f + bi
+            st["wkey"] += ("bn",) + tuple(ins[1:5])
+            dev[out] = st["out"]
+        elif n.op == "Mul":
+            c = [t for t in ins if t in host]
+            d = [t for t in ins if t in dev]
+            st = open_conv(n, d[0]) if len(d) == 1 and len(c) == 1 else None
+            if st is None or np.size(host[c[0]]) != 1 or st["relu"] or st["res"] is not None:
+                raise ValueError(f"{who(n)}: Mul that is not a constant scalar scale of a Conv output")
+            f = float(np.ravel(host[c[0]])[0])
+            st["w"], st["b"] = st["w"] * f, st["b"] * f
+            st["wkey"] += ("mul", c[0], f)
+            dev[out] = st["out"]
+        elif n.op == "Relu":
+            st = open_conv(n, ins[0]) if ins[0] in dev else None
+            if st is None or st["relu"]:
+                raise ValueError(f"{who(n)}: Relu that does not follow a Conv or a Conv + Add")
+            st["relu"] = True
+            dev[out] = st["out"]
+        elif n.op == "Add":
+            if len(ins) != 2:
+                raise ValueError(f"{who(n)}: Add of {len(ins)} tensors")
+            rs = [t for t in ins if t in resized]
+            if rs:
+                other = [t for t in ins if t not in resized]
+                if len(rs) != 1 or len(other) != 1 or other[0] not in dev or not sole(n, rs[0]):
+                    raise ValueError(f"{who(n)}: Add of a Resize output with something that is not a feature map")
+                src, up = resized[rs[0]]
+                lat = dev[other[0]]
+                if shapes[lat] != (shapes[src][0], shapes[src][1] * up, shapes[src][2] * up):
+                    raise ValueError(f"{who(n)}: Add of a {shapes[lat]} map with a x{up} resize of a {shapes[src]} map")
+                tid = new(shapes[lat])
+                steps.append({"op": "upadd", "coarse": src, "lateral": lat, "out": tid, "up": up})
+                producer.pop(lat, None)
+                dev[out] = tid
+                continue
+            if not all(t in dev for t in ins):
+                raise ValueError(f"{who(n)}: Add of something that is not a feature map")
+            a, b = dev[ins[0]], dev[ins[1]]
+            if shapes[a] != shapes[b]:
+                raise ValueError(f"{who(n)}: Add of maps of shapes {shapes[a]} and {shapes[b]}")
+            # the conv that runs LAST takes the other map as its residual (relu(acc + bias + residual))
+            made = {s["out"]: i for i, s in enumerate(steps)}
+            cand = [(made[st["out"]], st, o) for t, o in ((ins[0], b), (ins[1], a))
+                    for st in [open_conv(n, t)] if st is not None and not st["relu"] and st["res"] is None
+                    and made[st["out"]] > made[o]]
+            if cand and a != b:
+                _, st, o = max(cand, key=lambda c: c[0])
+                st["res"] = o
+                producer.pop(o, None)
+                dev[out] = st["out"]
+            else:
+                tid = new(shapes[a])
+                steps.append({"op": "upadd", "coarse": a, "lateral": b, "out": tid, "up": 1})
+                producer.pop(a, None), producer.pop(b, None)
+                dev[out] = tid
+        elif n.op in ("MaxPool", "AveragePool"):
+            if ins[0] not in dev:
+                raise ValueError(f"{who(n)}: pool of something that is not a feature map")
+            c, h, wd = shapes[dev[ins[0]]]
+            k, s = square(n, "kernel_shape"), square(n, "strides", [1, 1])
+            p = sym(n, "pads", k)
+            ceil = int(n.attrs.get("ceil_mode", 0))
+            cip = int(n.attrs.get("count_include_pad", 0))
+            if k > 3 or s > 2 or p >= k or list(n.attrs.get("dilations", [1, 1])) != [1, 1] or n.attrs.get("storage_order", 0):
+                raise ValueError(f"{who(n)}: pool kernel {k} stride {s} pad {p} is not implemented (kernel <= 3, stride <= 2)")
+
+            def osz(x):
+                o = -((x + 2 * p - k) // -s) + 1 if ceil else (x + 2 * p - k) // s + 1
+                return o - 1 if ceil and (o - 1) * s >= x + p else o
+            ho, wo = osz(h), osz(wd)
+            over = p > 0 or (ho - 1) * s + k > h or (wo - 1) * s + k > wd
+            if n.op == "AveragePool" and cip and over:
+                raise ValueError(f"{who(n)}: AveragePool with count_include_pad over padded or overhanging windows is not implemented")
+            tid = new((c, ho, wo))
+            steps.append({"op": "pool", "x": dev[ins[0]], "out": tid, "kind": 0 if n.op == "MaxPool" else 1, "k": k, "stride": s,
+                          "pad": p})
+            producer.pop(dev[ins[0]], None)
+            dev[out] = tid
+        elif n.op in ("Resize", "Upsample"):
+            if ins[0] not in dev:
+                raise ValueError(f"{who(n)}: resize of something that is not a feature map")
+            c, h, wd = shapes[dev[ins[0]]]
+            mode = _text(n.attrs.get("mode"), "nearest")
+            ctm = _text(n.attrs.get("coordinate_transformation_mode"), "half_pixel" if n.op == "Resize" else "asymmetric")
+            nm = _text(n.attrs.get("nearest_mode"), "round_prefer_floor" if n.op == "Resize" else "floor")
+            if mode != "nearest" or (ctm, nm) not in _NEAREST_OK:
+                raise ValueError(f"{who(n)}: resize mode {mode} / {ctm} / {nm} is not a nearest-neighbour copy")
+            rest = [t for t in n.inputs[1:]]
+            if any(t and t not in host for t in rest):
+                raise ValueError(f"{who(n)}: resize scales / sizes do not follow from the input size")
+            vals = [np.ravel(host[t]) for t in rest if t and np.size(host[t])]
+            if n.op == "Resize" and len(n.inputs) > 3 and n.inputs[3]:
+                tgt = [int(v) for v in np.ravel(host[n.inputs[3]])]
+                ok = len(tgt) == 4 and tgt[2] == 2 * h and tgt[3] == 2 * wd and tgt[1] == c
+            else:
+                sc = vals[-1] if vals else np.ravel(n.attrs.get("scales", []))
+                ok = len(sc) == 4 and float(sc[0]) == 1 and float(sc[1]) == 1 and float(sc[2]) == 2 and float(sc[3]) == 2
+            if not ok:
+                raise ValueError(f"{who(n)}: resize is not a x2 nearest-neighbour upsample of its {h} x {wd} input")
+            resized[out] = (dev[ins[0]], 2)
+            producer.pop(dev[ins[0]], None)
+        elif n.op == "Transpose":
+            if ins[0] not in dev or list(n.attrs.get("perm", [])) != [0, 2, 3, 1] or not sole(n, ins[0]):
+                raise ValueError(f"{who(n)}: Transpose that is not the (0, 2, 3, 1) of a head map")
+            nhwc[out] = dev[ins[0]]
+        elif n.op == "Reshape":
+            if ins[0] not in nhwc or len(ins) < 2 or ins[1] not in host:
+                raise ValueError(f"{who(n)}: Reshape that does not flatten a transposed head map to a constant last dimension")
+            tgt = [int(v) for v in np.ravel(host[ins[1]])]
+            tid = nhwc[ins[0]]
+            c, h, wd = shapes[tid]
+            if (len(tgt) < 2 or tgt[-1] <= 0 or c % tgt[-1] or tgt[-2] not in (-1, c * h * wd // tgt[-1])
+                    or any(v > 0 and v != 1 for v in tgt[:-2])):
+                raise ValueError(f"{who(n)}: Reshape target {tgt} does not flatten a {shapes[tid]} head map")
+            flat[out] = (tid, tgt[-1])
+        elif n.op == "Sigmoid":
+            if ins[0] not in flat:
+                raise ValueError(f"{who(n)}: Sigmoid that is not on a flattened head map")
+            sigm[out] = flat[ins[0]]
+        else:
+            raise ValueError(f"{who(n)}: op {n.op} is not supported")
+
+    produced = [t for n in g.nodes for t in n.outputs]
+    outs = [t for t in produced if t not in consumers and t not in host]
+    if len(outs) != 9:
+        kinds = "" if len(outs) != 6 else " (a detector without keypoint outputs: alignment needs them)"
+        raise ValueError(f"expected 9 graph outputs (3 strides x score, bbox, kps), found {len(outs)}{kinds}: not a SCRFD detector with keypoints")
+    by_stride = {}
+    for t in outs:
+        if t in sigm:
+            tid, kk, sg = sigm[t] + (True,)
+        elif t in flat:
+            tid, kk, sg = flat[t] + (False,)
+        else:
+            raise ValueError(f"graph output {t!r} is not a flattened head map")
+        st = producer.get(tid)
+        c, h, w = shapes[tid]
+        if st is None or st["relu"] or st["res"] is not None or ch % h or cw % w or ch // h != cw // w:
+            raise ValueError(f"graph output {t!r} does not come straight out of a head conv")
+        by_stride.setdefault(ch // h, []).append((t, tid, c, kk, sg, st))
+    if sorted(by_stride) != [8, 16, 32] or any(len(v) != 3 for v in by_stride.values()):
+        raise ValueError(f"head maps at strides {sorted(by_stride)} with {[len(v) for v in by_stride.values()]} outputs each: "
+                         "expected score, bbox and kps at strides 8, 16, 32")
+    levels, outputs, A = [], {}, None
+    for li, s in enumerate((8, 16, 32)):
+        ent = sorted(by_stride[s], key=lambda e: e[2])
+        a = ent[0][2]
+        A = a if A is None else A
+        if a != A or [e[2] for e in ent] != [a, 4 * a, 10 * a] or [e[3] for e in ent] != [1, 4, 10]:
+            raise ValueError(f"stride {s}: head channels {[e[2] for e in ent]} flattened to {[e[3] for e in ent]} are not "
+                             f"(A, 4A, 10A) to (1, 4, 10) with A = {A}")
+        if not ent[0][4]:
+            raise ValueError(f"stride {s}: score output {ent[0][0]!r} does not come out of a Sigmoid")
+        if ent[1][4] or ent[2][4]:
+            raise ValueError(f"stride {s}: a Sigmoid on a bbox / kps output")
+        for e, kind in zip(ent, ("score", "bbox", "kps")):
+            e[5]["f32"] = True
+            outputs[e[0]] = (li, kind)
+        levels.append({"stride": s, "score": ent[0][1], "bbox": ent[1][1], "kps": ent[2][1]})
+    outputs = {t: outputs[t] for t in outs}
+    used = {s[k] for s in steps for k in ("x", "res", "coarse", "lateral") if s.get(k) is not None}
+    used |= {lv[k] for lv in levels for k in ("score", "bbox", "kps")}
+    for s in steps:
+        if s["out"] not in used:
+            raise ValueError(f"a {s['op']} step's result (tensor {s['out']}, shape {shapes[s['out']]}) feeds nothing: not a SCRFD detector")
+    return ScrfdPlan((ch, cw), steps, shapes, levels, A, outputs)

@@ -34,7 +34,10 @@ typedef void* fr_stream_t;
  * x2 / C2, fr_conv_f8_args y8_sub, fr_pnet23_split_f16 all_heads; 103: the fr_gallery_topk_* / fr_match_reduce_shards_topk
  * entries; 104: fr_pnet_level gained x1s / hs / ws / f16, the fr_pnet_pyramid_* entries;
  * 105: fr_frame_ref, fr_letterbox_u8, fr_detections_unscale, the fr_warp_affine_5pt*_refs entries;
- * 106: fr_gallery_match_view_f16 / _f8 with their _workspace functions, fr_gallery_update_rows_shadow).  fr_version() returns the value the library was built
+ * 106: fr_gallery_match_view_f16 / _f8 with their _workspace functions, fr_gallery_update_rows_shadow).  The SCRFD detector's
+ * entries (fr_det_conv_f16, fr_det_conv_weight_halves, fr_det_input_f16, fr_det_pool_f16, fr_det_upsample_add_f16, fr_scrfd_decode)
+ * were ADDED under 106: no existing signature or struct changed shape, and a binding written against them finds a library
+ * without them by the missing symbol.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -595,6 +598,50 @@ int fr_letterbox_u8(const fr_frame_ref* refs, int nframes, uint8_t* canvas, int 
  * [nframes,cap,5,2] of the slots j < counts[f] is divided (IEEE f32) by det_scale[f]; other slots are left untouched. */
 int fr_detections_unscale(float* boxes, float* kps, const int32_t* counts, const float* det_scale, int nframes, int cap,
                           fr_stream_t stream);
+
+/* ---------------------------------------------------------------- SCRFD detector ----
+ * The detector of insightface's buffalo_l pack (det_10g.onnx; FaceAnalysis(name="buffalo_l"), infrenceServer.py:412-416) as
+ * layer kernels; the host walks a plan read from the ONNX graph (onnx_import.scrfd_plan_from_onnx, scrfd.py).  Activations are
+ * f16 NHWC with the channel count padded to a multiple of 8; padded channels hold exact zeros.
+ *
+ * fr_det_conv_f16: y = [relu]( conv(x, w) + bias [+ residual] ), 1x1 or 3x3, stride 1 or 2, zero padding `pad` on every side,
+ * f16 operands on the matrix cores, f32 accumulation and epilogue (bias, then residual, then ReLU).
+ *   x         f16 [N,H,W,Cin], Cin a multiple of 8
+ *   w         f16, fr_det_conv_weight_halves(Cin, cout_packed, K) elements: [ceil(G / 4)][cout_packed][4][8] where G = K*K*Cin/8
+ *             and element [s][co][q][j] is weight (co, tap t, channel 8*c + j) of group g = 4 s + q = t * (Cin / 8) + c, tap
+ *             t = ky * K + kx; groups >= G and output channels past the layer's own are zero.  cout_packed: a multiple of 16.
+ *   bias      f32 [cout_packed] (zero past the layer's own channels)
+ *   residual  optional f16 [N,Ho,Wo,ldo] (f16 output only)
+ *   y         out_f32 == 0: f16 [N,Ho,Wo,ldo], channels [0, cout_store) written, cout_store and ldo multiples of 8;
+ *             out_f32 != 0: f32 [N,Ho,Wo,ldo], channels [0, cout_store) written, any cout_store <= ldo (the head maps)
+ *   tile      0: chosen from the shape; else 10 * MT + NT with MT in {1, 2, 4} (x16 pixels per wave), NT in {2, 4} (x16 channels) */
+size_t fr_det_conv_weight_halves(int Cin, int cout_packed, int K);
+int fr_det_conv_f16(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H, int W,
+                    int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo, int cout_store, int ldo,
+                    int relu, int out_f32, int tile, fr_stream_t stream);
+/* canvas u8 [N,H,W,3] BGR -> y f16 [N,H,W,8]: channels 0..2 = (R, G, B) as (v - 127.5) / 128 (exact in f16), 3..7 = 0
+ * (insightface's SCRFD blob: input_mean = 127.5, input_std = 128, swapRB). */
+int fr_det_input_f16(const uint8_t* canvas, void* y, int N, int H, int W, fr_stream_t stream);
+/* x f16 [N,H,W,C] -> y f16 [N,Ho,Wo,C], C a multiple of 8.  kind 0: max, 1: average; window k <= 3, stride <= 2, `pad` rows /
+ * columns in front; Ho, Wo from the host (floor or ceil mode): every window must hold an in-bounds tap.  Taps outside the
+ * input are skipped and the average divides by the in-bounds count (ONNX count_include_pad = 0; with no window over padding
+ * or the edge, which is all the importer admits of count_include_pad = 1, the two agree).  Exact: the f16 rounding of the
+ * true value. */
+int fr_det_pool_f16(const void* x, void* y, int N, int H, int W, int C, int Ho, int Wo, int kind, int k, int stride,
+                    int pad, fr_stream_t stream);
+/* y = lateral + nearest-neighbour x`up` of coarse (up = 2: the FPN top-down step; 1: a plain sum).  lateral, y f16 [N,H,W,C];
+ * coarse f16 [N,H/up,W/up,C]; C a multiple of 8.  One f16 rounding of the exact sum. */
+int fr_det_upsample_add_f16(const void* coarse, const void* lateral, void* y, int N, int H, int W, int C, int up,
+                            fr_stream_t stream);
+/* One level of SCRFD head maps -> candidates.  score f32 [nframes,Hl*Wl*A] (LOGITS), bbox f32 [nframes,Hl*Wl*A,4], kps f32
+ * [nframes,Hl*Wl*A,10], anchors of a cell consecutive, cells row-major.  Keeps anchors with logit >= logit_thr in that order,
+ * the first `cap`; anchor centre (x * stride, y * stride); box = (cx - d0 s, cy - d1 s, cx + d2 s, cy + d3 s), keypoint i =
+ * (cx + k[2i] s, cy + k[2i+1] s), all divided by det_scale[frame] (f32 [nframes]); score = 1 / (1 + expf(-logit)).  Each
+ * operation is one IEEE f32 rounding.  Writes segment `level` (0..2) of boxes f32 [nframes,3,cap,4], scores f32 [nframes,3,cap],
+ * aux f32 [nframes,3,cap,10] and counts i32 [nframes*3]: the lists fr_sort_nms takes with nseg = 3, seg_cap = cap. */
+int fr_scrfd_decode(const float* score, const float* bbox, const float* kps, int nframes, int Hl, int Wl, int A, int stride,
+                    int level, float logit_thr, const float* det_scale, int cap, float* boxes, float* scores, float* aux,
+                    int32_t* counts, fr_stream_t stream);
 
 /* A recorded run of detector calls replayed by ONE C call (an eager single-frame get() is bound by the interpreter: ~50
  * ctypes calls per frame; FaceAnalysis.get, infrenceServer.py:528).  `fn` names the entry point, `a` carries its arguments
