@@ -166,6 +166,8 @@ SIGNATURES = {
     "fr_detect_sequence": (_I, [C.POINTER(Call), _I]),
     "fr_det_conv_weight_halves": (_Z, [_I, _I, _I]),
     "fr_det_conv_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fr_det_conv_act_f16": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "fr_dw_conv_f16": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fr_det_input_f16": (_I, [_P, _P, _I, _I, _I, _P]),
     "fr_det_pool_f16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "fr_det_upsample_add_f16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),

@@ -3,6 +3,7 @@
 // blocks end in relu(conv + bias + identity): neither fits fr_conv_nhwc_f16 (64-channel granule, prelu-then-residual).
 //
 //   fr_det_conv_f16          1x1 / 3x3, stride 1 / 2, zero padding: implicit GEMM on the f16 16x16x32 MFMA
+//   fr_det_conv_act_f16      the same kernel with a PReLU epilogue (the recognition plans of mbf.py)
 //   fr_det_input_f16         u8 BGR canvas -> f16 RGB (x - 127.5) / 128, 8 channels
 //   fr_det_pool_f16          max / average pool
 //   fr_det_upsample_add_f16  lateral + nearest x2 (or x1) of the coarser map
@@ -11,7 +12,7 @@
 namespace {
 
 struct DetConvP {
-    const half_t* x; const half_t* w; const float* bias; const half_t* res; void* y;
+    const half_t* x; const half_t* w; const float* bias; const float* slope; const half_t* res; void* y;
     int H, W, Cin, Ho, Wo, KW, stride, pad;
     int G, CG, ksteps;              // 8-channel groups of the K axis (taps * Cin / 8), groups per tap, K steps of 4 groups
     int ntiles, CoutW;              // 16-channel output tiles, packed output channels (ntiles * 16)
@@ -24,7 +25,9 @@ struct DetConvP {
 // step may straddle taps and only the last step of a layer carries zero groups (Cin = 8 at the stem: 9 groups, 3 steps).
 // The weights are the MFMA's A operand and the pixels its B operand: a lane then holds 4 CONSECUTIVE output channels of one
 // pixel, stored as one 8-byte word.
-template <int MT, int NT>
+// PRELU: the epilogue's activation is v < 0 ? v * slope[channel] : v instead of the optional ReLU (a separate instantiation, so
+// the detector's kernels are the code they were).
+template <int MT, int NT, bool PRELU>
 __global__ __launch_bounds__(256) void det_conv(DetConvP p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, q = lane >> 4;
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(256) void det_conv(DetConvP p) {
         g += 4; cg += 4;
         while (cg >= p.CG) { cg -= p.CG; ++tap; }
     }
-    // epilogue: + bias, + residual, ReLU, in that order; acc[mt][nt][i] = channel tile*16 + 4q + i of pixel m0 + 16 mt + r
+    // epilogue: + bias, + residual, ReLU / PReLU, in that order; acc[mt][nt][i] = channel tile*16 + 4q + i of pixel m0 + 16 mt + r
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         const int64_t m = m0 + mt * 16 + r;
@@ -93,6 +96,9 @@ __global__ __launch_bounds__(256) void det_conv(DetConvP p) {
             const int c0 = tile * 16 + q * 4;
             if (c0 >= p.cout_store) continue;
             const float4v b = *reinterpret_cast<const float4v*>(p.bias + c0);
+            float4v sl = float4v{0.f, 0.f, 0.f, 0.f};
+            if constexpr (PRELU) sl = *reinterpret_cast<const float4v*>(p.slope + c0);
+            auto act = [&](float v, int i) { return PRELU ? (v < 0.f ? v * sl[i] : v) : (p.relu ? fmaxf(v, 0.f) : v); };
             float v[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = acc[mt][nt][i] + b[i];
@@ -100,7 +106,7 @@ __global__ __launch_bounds__(256) void det_conv(DetConvP p) {
                 float* y = static_cast<float*>(p.y) + m * p.ldo;
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    if (c0 + i < p.cout_store) y[c0 + i] = p.relu ? fmaxf(v[i], 0.f) : v[i];
+                    if (c0 + i < p.cout_store) y[c0 + i] = act(v[i], i);
             } else {                                                 // cout_store and ldo are multiples of 8 here
                 if (p.res) {
                     const half4 rr = *reinterpret_cast<const half4*>(p.res + m * p.ldo + c0);
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(256) void det_conv(DetConvP p) {
                 }
                 half4 o;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) o[i] = (half_t)(p.relu ? fmaxf(v[i], 0.f) : v[i]);
+                for (int i = 0; i < 4; ++i) o[i] = (half_t)act(v[i], i);
                 *reinterpret_cast<half4*>(static_cast<half_t*>(p.y) + m * p.ldo + c0) = o;
             }
         }
@@ -187,32 +193,26 @@ __global__ __launch_bounds__(256) void det_upsample_add(const half_t* __restrict
 template <int MT, int NT>
 void launch_conv(const DetConvP& p, hipStream_t s) {
     const dim3 grid((unsigned)fr_cdiv(p.M, (int64_t)MT * 64), (unsigned)fr_cdiv(p.ntiles, NT));
-    det_conv<MT, NT><<<grid, 256, 0, s>>>(p);
+    if (p.slope) det_conv<MT, NT, true><<<grid, 256, 0, s>>>(p);
+    else det_conv<MT, NT, false><<<grid, 256, 0, s>>>(p);
 }
 
-}  // namespace
-
-extern "C" size_t fr_det_conv_weight_halves(int Cin, int cout_packed, int K) {
-    if (Cin <= 0 || cout_packed <= 0 || K <= 0) return 0;
-    const int G = K * K * (Cin / 8);
-    return (size_t)((G + 3) / 4) * (size_t)cout_packed * 32;
-}
-
-extern "C" int fr_det_conv_f16(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H, int W,
-                               int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo, int cout_store, int ldo,
-                               int relu, int out_f32, int tile, fr_stream_t stream) {
-    FR_REQUIRE(x && w && bias && y, "fr_det_conv_f16: null pointer");
-    FR_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 8 == 0, "fr_det_conv_f16: Cin %d must be a positive multiple of 8", Cin);
-    FR_REQUIRE(cout_packed > 0 && cout_packed % 16 == 0, "fr_det_conv_f16: packed Cout %d must be a multiple of 16", cout_packed);
+// what: the entry point's name in front of its messages.  slope != nullptr selects the PReLU epilogue.
+int conv_entry(const char* what, const void* x, const void* w, const float* bias, const float* slope, const void* residual, void* y,
+               int N, int H, int W, int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo, int cout_store, int ldo,
+               int relu, int out_f32, int tile, fr_stream_t stream) {
+    FR_REQUIRE(x && w && bias && y, "%s: null pointer", what);
+    FR_REQUIRE(N > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 8 == 0, "%s: Cin %d must be a positive multiple of 8", what, Cin);
+    FR_REQUIRE(cout_packed > 0 && cout_packed % 16 == 0, "%s: packed Cout %d must be a multiple of 16", what, cout_packed);
     FR_REQUIRE((K == 1 || K == 3) && (stride == 1 || stride == 2) && pad >= 0 && pad < K,
-               "fr_det_conv_f16: kernel %d stride %d pad %d not supported (1x1 / 3x3, stride 1 / 2, pad < kernel)", K, stride, pad);
+               "%s: kernel %d stride %d pad %d not supported (1x1 / 3x3, stride 1 / 2, pad < kernel)", what, K, stride, pad);
     FR_REQUIRE(H + 2 * pad >= K && W + 2 * pad >= K && Ho == (H + 2 * pad - K) / stride + 1 && Wo == (W + 2 * pad - K) / stride + 1,
-               "fr_det_conv_f16: output %d x %d does not follow from input %d x %d", Ho, Wo, H, W);
-    FR_REQUIRE(cout_store > 0 && cout_store <= cout_packed && cout_store <= ldo, "fr_det_conv_f16: bad cout_store %d / ldo %d", cout_store, ldo);
+               "%s: output %d x %d does not follow from input %d x %d", what, Ho, Wo, H, W);
+    FR_REQUIRE(cout_store > 0 && cout_store <= cout_packed && cout_store <= ldo, "%s: bad cout_store %d / ldo %d", what, cout_store, ldo);
     FR_REQUIRE(out_f32 ? residual == nullptr : (cout_store % 8 == 0 && ldo % 8 == 0),
-               "fr_det_conv_f16: f16 output needs cout_store and ldo in multiples of 8; f32 output takes no residual");
+               "%s: f16 output needs cout_store and ldo in multiples of 8; f32 output takes no residual", what);
     DetConvP p;
-    p.x = static_cast<const half_t*>(x); p.w = static_cast<const half_t*>(w); p.bias = bias;
+    p.x = static_cast<const half_t*>(x); p.w = static_cast<const half_t*>(w); p.bias = bias; p.slope = slope;
     p.res = static_cast<const half_t*>(residual); p.y = y;
     p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.KW = K; p.stride = stride; p.pad = pad;
     p.CG = Cin / 8; p.G = K * K * p.CG; p.ksteps = (p.G + 3) / 4;
@@ -233,10 +233,34 @@ extern "C" int fr_det_conv_f16(const void* x, const void* w, const float* bias, 
         case 42: launch_conv<4, 2>(p, s); break;
         case 22: launch_conv<2, 2>(p, s); break;
         case 12: launch_conv<1, 2>(p, s); break;
-        default: FR_REQUIRE(false, "fr_det_conv_f16: unknown tile shape %d (0, 44, 24, 14, 42, 22, 12)", tile);
+        default: FR_REQUIRE(false, "%s: unknown tile shape %d (0, 44, 24, 14, 42, 22, 12)", what, tile);
     }
     FR_CHECK_LAUNCH("det_conv");
     return FR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t fr_det_conv_weight_halves(int Cin, int cout_packed, int K) {
+    if (Cin <= 0 || cout_packed <= 0 || K <= 0) return 0;
+    const int G = K * K * (Cin / 8);
+    return (size_t)((G + 3) / 4) * (size_t)cout_packed * 32;
+}
+
+extern "C" int fr_det_conv_f16(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H, int W,
+                               int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo, int cout_store, int ldo,
+                               int relu, int out_f32, int tile, fr_stream_t stream) {
+    return conv_entry("fr_det_conv_f16", x, w, bias, nullptr, residual, y, N, H, W, Cin, cout_packed, K, stride, pad, Ho, Wo, cout_store,
+                      ldo, relu, out_f32, tile, stream);
+}
+
+extern "C" int fr_det_conv_act_f16(const void* x, const void* w, const float* bias, const float* slope, const void* residual, void* y,
+                                   int N, int H, int W, int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo,
+                                   int cout_store, int ldo, int act, int out_f32, int tile, fr_stream_t stream) {
+    FR_REQUIRE(act >= 0 && act <= 2, "fr_det_conv_act_f16: act %d is none of 0 (none), 1 (ReLU), 2 (PReLU)", act);
+    FR_REQUIRE(act != 2 || slope, "fr_det_conv_act_f16: act 2 (PReLU) needs the slope vector");
+    return conv_entry("fr_det_conv_act_f16", x, w, bias, act == 2 ? slope : nullptr, residual, y, N, H, W, Cin, cout_packed, K, stride, pad,
+                      Ho, Wo, cout_store, ldo, act == 1, out_f32, tile, stream);
 }
 
 extern "C" int fr_det_input_f16(const uint8_t* canvas, void* y, int N, int H, int W, fr_stream_t stream) {

@@ -52,7 +52,9 @@ class FaceAnalysis:
     ``name`` selects a model directory ``<root>/models/<name>/`` holding ``arcface_<arch>.pt|.safetensors``
     and ``mtcnn_{pnet,rnet,onet}.pt`` state dicts (public PyTorch naming, see weights.py).  A recognition network
     shipped as ONNX - the ``w600k_r50.onnx`` of the reference's own buffalo_l pack - is read too (onnx_import.py: the
-    first ``*.onnx`` of the directory whose graph is an ArcFace IResNet; ``arch`` then follows the file).  The pack's
+    first ``*.onnx`` of the directory whose graph is an ArcFace IResNet; ``arch`` then follows the file), and so is a
+    MobileFaceNet-style one built from depthwise convs (the ``w600k_mbf.onnx`` of buffalo_s / buffalo_sc: ``arch`` becomes
+    ``"mbf"`` and ``mbf.PlanRecogniserHIP`` runs the plan ``onnx_import.recognition_plan_from_onnx`` reads; f16 only).  The pack's
     detector (``det_10g.onnx``, SCRFD) is read too when the directory holds no ``mtcnn_*.pt`` files: the first ``*.onnx``
     that ``onnx_import.scrfd_plan_from_onnx`` accepts becomes a ``scrfd.SCRFDHIP`` detector on a 640 x 640 canvas unless
     ``prepare`` is given another ``det_size``; with neither, MTCNN runs on synthetic weights.  The detector keywords of the
@@ -87,17 +89,23 @@ class FaceAnalysis:
                 det = tuple(weights.load_state(q) for q in ps)
         parsed = {}                                        # file name -> graph (or None: the recognition network's), read once
         if rec is None and os.path.isdir(d):              # insightface packs ship the recognition network as ONNX
-            from .onnx_import import iresnet_state_from_onnx, read_onnx
+            from .onnx_import import iresnet_state_from_onnx, read_onnx, recognition_plan_from_onnx
             skipped = []
             for fn in sorted(os.listdir(d)):
                 if fn.endswith(".onnx"):
                     try:
                         parsed[fn] = read_onnx(os.path.join(d, fn))
                         st, arch = iresnet_state_from_onnx(parsed[fn])
-                    except Exception as e:                 # the pack's detector / landmark / attribute models, or a
-                        skipped.append(f"{fn}: {type(e).__name__}: {e}")      # graph this reader cannot map
-                        continue
-                    rec, self.arch = {k: torch.from_numpy(v) for k, v in st.items()}, arch
+                        rec, self.arch = {k: torch.from_numpy(v) for k, v in st.items()}, arch
+                    except Exception as e:                 # no IResNet: a MobileFaceNet-style recogniser (buffalo_s / _sc)?
+                        try:
+                            if fn not in parsed:
+                                raise
+                            rec, self.arch = recognition_plan_from_onnx(parsed[fn]), "mbf"
+                        except Exception as e2:            # the pack's detector / landmark / attribute models, or a
+                            why = f"{fn}: {type(e).__name__}: {e}"            # graph this reader cannot map
+                            skipped.append(why if e2 is e else f"{why}; as a depthwise recogniser: {type(e2).__name__}: {e2}")
+                            continue
                     parsed[fn] = None
                     break
             for why in skipped:
@@ -106,7 +114,7 @@ class FaceAnalysis:
                 # the directory HOLDS .onnx files but none maps onto an ArcFace IResNet: falling back to synthetic
                 # recognition weights here would silently recognise nobody
                 raise _lib.FrError(f"model pack '{self.name}' under {d}: none of its .onnx files is a readable ArcFace "
-                                   "IResNet (" + "; ".join(skipped) + ")")
+                                   "IResNet or depthwise (MobileFaceNet-style) recogniser (" + "; ".join(skipped) + ")")
         self._scrfd_graph = self._find_scrfd(d, parsed) if det is None and os.path.isdir(d) else None
         if self._scrfd_graph is not None:
             # rec is never None here: a directory that holds .onnx files of which none is an ArcFace IResNet raised above,
@@ -118,7 +126,7 @@ class FaceAnalysis:
             missing = " and ".join(w for w, x in (("recognition", rec), ("MTCNN detector", det)) if x is None)
             warnings.warn(f"model pack '{self.name}' under {d}: no {missing} weights found: using SEEDED SYNTHETIC "
                           f"weights for them (numerically exact pipeline, meaningless identities)")
-        return (rec or weights.synth_iresnet_state(self.arch), det or weights.synth_mtcnn_states())
+        return (rec if rec is not None else weights.synth_iresnet_state(self.arch), det or weights.synth_mtcnn_states())
 
     def _find_scrfd(self, d, parsed):
         """The graph of the first ``*.onnx`` under d that is a SCRFD detector with keypoints, or None; the others are
@@ -175,7 +183,11 @@ class FaceAnalysis:
             if self.det_size[0] % 32 or self.det_size[1] % 32:
                 raise ValueError(f"det_size {self.det_size}: the SCRFD detector needs both sides in multiples of 32")
         self._det_thresh = det_thresh
-        self.rec = IResNetHIP(rec, self.arch, self.device)
+        if self.arch == "mbf":                          # _load_states read a recognition PLAN (onnx_import.RecognitionPlan)
+            from .mbf import PlanRecogniserHIP
+            self.rec = PlanRecogniserHIP(rec, self.device)
+        else:
+            self.rec = IResNetHIP(rec, self.arch, self.device)
         self.det = self._make_detector(self.det_kwargs, det_thresh)
         self.lib = _lib.load()
         self._use_graphs, self._graphs = False, {}
@@ -188,6 +200,9 @@ class FaceAnalysis:
         activation scales).  Returns the number of convs switched."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
+        if self.arch == "mbf":
+            raise _lib.FrError(f"model pack '{self.name}': its recogniser is a depthwise (MobileFaceNet-style) network; the fp8 path "
+                               "exists for IResNet only")
         frames = self._to_device(frames)
         with self._lock, torch.cuda.device(self.device):
             frames, src = self._source(frames)

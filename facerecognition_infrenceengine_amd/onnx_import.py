@@ -159,10 +159,32 @@ def _node(buf):
 
 
 class OnnxGraph:
-    """nodes (file order = topological), initialisers by name, graph input names that are not initialisers."""
+    """nodes (file order = topological), initialisers by name, graph input names that are not initialisers; ``outputs``: the
+    declared graph output names (None when the file was not read here); ``value_shapes``: name -> declared shape of a graph
+    input / output as a list (None for a symbolic dimension), only for those whose ValueInfo carries one."""
 
-    def __init__(self, nodes, initializers, inputs):
+    def __init__(self, nodes, initializers, inputs, outputs=None, value_shapes=None):
         self.nodes, self.initializers, self.inputs = nodes, initializers, inputs
+        self.outputs, self.value_shapes = outputs, value_shapes or {}
+
+
+def _value_info(buf):
+    """ValueInfoProto -> (name, shape or None): type (2) . tensor_type (1) . shape (2) . dim (1) . dim_value (1)"""
+    name, shape = "", None
+    for f, _, v in _fields(buf):
+        if f == 1:
+            name = bytes(v).decode()
+        elif f == 2:
+            for g, _, tt in _fields(v):
+                if g == 1:
+                    for h, _, sh in _fields(tt):
+                        if h == 2:
+                            shape = []
+                            for d, _, dim in _fields(sh):
+                                if d == 1:
+                                    val = [x for e, wt, x in _fields(dim) if e == 1 and wt == 0]
+                                    shape.append(_signed(val[0]) if val else None)
+    return name, shape
 
 
 def read_onnx(path):
@@ -174,22 +196,23 @@ def read_onnx(path):
             graph = v
     if graph is None:
         raise ValueError(f"{path}: no GraphProto (field 7) in the ModelProto")
-    nodes, inits, inputs = [], {}, []
+    nodes, inits, inputs, outputs, vshapes = [], {}, [], [], {}
     for f, wt, v in _fields(graph):
         if f == 1:
             nodes.append(_node(v))
         elif f == 5:
             name, a = _tensor(v)
             inits[name] = a
-        elif f == 11:                                   # ValueInfoProto: field 1 = name
-            for g, _, w in _fields(v):
-                if g == 1:
-                    inputs.append(bytes(w).decode())
+        elif f in (11, 12):                             # graph inputs / outputs (ValueInfoProto)
+            name, shape = _value_info(v)
+            (inputs if f == 11 else outputs).append(name)
+            if shape is not None:
+                vshapes[name] = shape
     # Constant nodes are initialisers in all but name
     for n in nodes:
         if n.op == "Constant" and "value" in n.attrs and n.outputs:
             inits[n.outputs[0]] = n.attrs["value"]
-    return OnnxGraph([n for n in nodes if n.op != "Constant"], inits, [i for i in inputs if i not in inits])
+    return OnnxGraph([n for n in nodes if n.op != "Constant"], inits, [i for i in inputs if i not in inits], outputs, vshapes)
 
 
 # --------------------------------------------------------------------------- IResNet graph -> state dict
@@ -351,6 +374,7 @@ class ScrfdPlan:
     steps    device steps in execution order, dicts with ``op`` in
              ``input``  (out)                                       the canvas as tensor 0
              ``conv``   (x, out, w, b, wkey, k, stride, pad, relu, res, f32)   w [Cout,Cin,k,k] / b [Cout] float64, BN / Mul folded
+             ``dwconv`` (the same keys; res None, f32 False)        depthwise 3x3, pad 1: w [C,1,3,3]
              ``pool``   (x, out, kind, k, stride, pad)              kind 0 max, 1 average
              ``upadd``  (coarse, lateral, out, up)                  lateral + nearest x up of coarse
     shapes   tensor id -> (C, H, W), the channel count unpadded
@@ -362,7 +386,7 @@ class ScrfdPlan:
         self.canvas_hw, self.steps, self.shapes, self.levels = tuple(canvas_hw), steps, shapes, levels
         self.num_anchors, self.outputs = num_anchors, outputs
         self.macs2 = sum(2 * shapes[s["out"]][1] * shapes[s["out"]][2] * int(np.prod(s["w"].shape))
-                         for s in steps if s["op"] == "conv")
+                         for s in steps if s["op"] in ("conv", "dwconv"))
 
 
 _CAST = {1: np.float32, 6: np.int32, 7: np.int64, 11: np.float64}
@@ -489,12 +513,17 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
                 raise ValueError(f"{who(n)}: conv input / weight is not a feature map / an initialiser")
             w = np.asarray(host[ins[1]], dtype=np.float64)
             c, h, wd = shapes[dev[ins[0]]]
-            if n.attrs.get("group", 1) != 1:
+            grp = n.attrs.get("group", 1)
+            # the one grouped form there is a kernel for: depthwise 3x3, pad 1 (the small SCRFDs' separable convs)
+            dw = grp != 1 and w.ndim == 4 and grp == c == w.shape[0] and w.shape[1] == 1 and list(w.shape[2:]) == [3, 3] \
+                and list(n.attrs.get("kernel_shape", [3, 3])) == [3, 3] and list(n.attrs.get("pads", [0] * 4)) == [1] * 4 \
+                and list(n.attrs.get("strides", [1, 1])) in ([1, 1], [2, 2]) and list(n.attrs.get("dilations", [1, 1])) == [1, 1]
+            if grp != 1 and not dw:
                 raise ValueError(f"{who(n)}: grouped conv (group {n.attrs['group']}) is not supported")
             k = square(n, "kernel_shape", list(w.shape[2:]))
             s = square(n, "strides", [1, 1])
             p = sym(n, "pads", k)
-            if w.ndim != 4 or w.shape[1] != c or w.shape[2] != k or w.shape[3] != k or k not in (1, 3) or s not in (1, 2) \
+            if w.ndim != 4 or w.shape[1] != (1 if dw else c) or w.shape[2] != k or w.shape[3] != k or k not in (1, 3) or s not in (1, 2) \
                     or p >= k or list(n.attrs.get("dilations", [1, 1])) != [1, 1]:
                 raise ValueError(f"{who(n)}: conv weight {w.shape} kernel {k} stride {s} pad {p} on {c} channels is not a "
                                  "1x1 / 3x3, stride 1 / 2, undilated conv of its input")
@@ -502,8 +531,8 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             if len(ins) > 2 and ins[2] not in host:
                 raise ValueError(f"{who(n)}: conv bias is not an initialiser")
             tid = new((w.shape[0], (h + 2 * p - k) // s + 1, (wd + 2 * p - k) // s + 1))
-            st = {"op": "conv", "x": dev[ins[0]], "out": tid, "w": w, "b": b, "wkey": (ins[1], ins[2] if len(ins) > 2 else None),
-                  "k": k, "stride": s, "pad": p, "relu": False, "res": None, "f32": False}
+            st = {"op": "dwconv" if dw else "conv", "x": dev[ins[0]], "out": tid, "w": w, "b": b,
+                  "wkey": (ins[1], ins[2] if len(ins) > 2 else None), "k": k, "stride": s, "pad": p, "relu": False, "res": None, "f32": False}
             steps.append(st)
             producer[tid] = st
             dev[out] = tid
@@ -557,7 +586,7 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             # the conv that runs LAST takes the other map as its residual (relu(acc + bias + residual))
             made = {s["out"]: i for i, s in enumerate(steps)}
             cand = [(made[st["out"]], st, o) for t, o in ((ins[0], b), (ins[1], a))
-                    for st in [open_conv(n, t)] if st is not None and not st["relu"] and st["res"] is None
+                    for st in [open_conv(n, t)] if st is not None and st["op"] == "conv" and not st["relu"] and st["res"] is None
                     and made[st["out"]] > made[o]]
             if cand and a != b:
                 _, st, o = max(cand, key=lambda c: c[0])
@@ -651,7 +680,7 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             raise ValueError(f"graph output {t!r} is not a flattened head map")
         st = producer.get(tid)
         c, h, w = shapes[tid]
-        if st is None or st["relu"] or st["res"] is not None or ch % h or cw % w or ch // h != cw // w:
+        if st is None or st["op"] != "conv" or st["relu"] or st["res"] is not None or ch % h or cw % w or ch // h != cw // w:
             raise ValueError(f"graph output {t!r} does not come straight out of a head conv")
         by_stride.setdefault(ch // h, []).append((t, tid, c, kk, sg, st))
     if sorted(by_stride) != [8, 16, 32] or any(len(v) != 3 for v in by_stride.values()):
@@ -680,3 +709,217 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
         if s["out"] not in used:
             raise ValueError(f"a {s['op']} step's result (tensor {s['out']}, shape {shapes[s['out']]}) feeds nothing: not a SCRFD detector")
     return ScrfdPlan((ch, cw), steps, shapes, levels, A, outputs)
+
+
+# --------------------------------------------------------------------------- recognition graph -> device plan
+
+class RecognitionPlan:
+    """What ``recognition_plan_from_onnx`` returns: a recognition network as device steps on a 112 x 112 aligned crop.
+
+    steps    in execution order, dicts with ``op`` in
+             ``input``   (out)                                       the crop as tensor 0, (3, 112, 112)
+             ``conv``    (x, out, w, b, k, stride, pad, act, slope, res, f32)   w [Cout,Cin,k,k] / b [Cout] float64, BN folded;
+                         act 0 none / 1 ReLU (never produced here) / 2 PReLU with ``slope`` [Cout]; ``res``: tensor id added
+                         in front of the activation; ``f32``: the output is the embedding (the fully connected layer, k 1 on a 1 x 1 map)
+             ``dwconv``  (the same keys; res None, f32 False)         depthwise: w [C,1,k,k]
+    shapes   tensor id -> (C, H, W)
+    output   tensor id of the embedding, shape (dim, 1, 1)
+    macs2    2 x multiply-accumulates per face
+    """
+
+    def __init__(self, steps, shapes, output):
+        self.steps, self.shapes, self.output = steps, shapes, output
+        self.dim = shapes[output][0]
+        self.macs2 = sum(2 * shapes[s["out"]][1] * shapes[s["out"]][2] * int(np.prod(s["w"].shape))
+                         for s in steps if s["op"] in ("conv", "dwconv"))
+
+
+def recognition_plan_from_onnx(path_or_graph):
+    """Map a recognition graph built from convs, depthwise convs, PReLU and residual adds - insightface's MobileFaceNet
+    (``w600k_mbf.onnx``) is the shape this is written for - onto device steps by following the data flow: widths and block
+    counts are the graph's own.  One input [*,3,112,112], one output [*,512].  Raises ValueError naming the node and op it
+    cannot map; a graph is mapped whole or not at all."""
+    g = path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph)
+    if len(g.inputs) != 1:
+        raise ValueError(f"expected one graph input, found {g.inputs}")
+    ishape = g.value_shapes.get(g.inputs[0])
+    if ishape is not None and (len(ishape) != 4 or list(ishape[1:]) != [3, 112, 112]):
+        raise ValueError(f"graph input {g.inputs[0]!r} of shape {ishape}: expected [*, 3, 112, 112]")
+    consumers = {}
+    for n in g.nodes:
+        for t in n.inputs:
+            if t:
+                consumers.setdefault(t, []).append(n)
+    host = g.initializers
+    dev = {g.inputs[0]: 0}
+    shapes = {0: (3, 112, 112)}
+    steps = [{"op": "input", "out": 0}]
+    producer = {}                        # tensor id -> its conv / dwconv step while more may be folded into it
+    flat = {}                            # tensor name -> tensor id of the 1 x 1 map it flattens
+    made_by = {}                         # tensor name -> node
+
+    def who(n):
+        return f"node {n.name or (n.outputs[0] if n.outputs else '?')!r} ({n.op})"
+
+    def sole(n, t):
+        return len(consumers.get(t, [])) == 1 and consumers[t][0] is n
+
+    def open_step(n, t):
+        st = producer.get(dev.get(t))
+        return st if st is not None and sole(n, t) else None
+
+    def const(n, t, what):
+        if t not in host:
+            raise ValueError(f"{who(n)}: {what} is not an initialiser")
+        return np.asarray(host[t], dtype=np.float64)
+
+    def add_step(op, x, w, b, k, s, p, hw, f32=False):
+        tid = len(shapes)
+        shapes[tid] = (w.shape[0],) + hw
+        st = {"op": op, "x": x, "out": tid, "w": w, "b": b, "k": k, "stride": s, "pad": p, "act": 0, "slope": None, "res": None,
+              "f32": f32}
+        steps.append(st)
+        producer[tid] = st
+        return st
+
+    for n in g.nodes:
+        ins = [t for t in n.inputs if t]
+        if not n.outputs or not ins:
+            raise ValueError(f"{who(n)}: node without inputs or outputs")
+        out = n.outputs[0]
+        for t in n.outputs:
+            made_by[t] = n
+        if n.op == "Conv":
+            if ins[0] not in dev or len(ins) < 2:
+                raise ValueError(f"{who(n)}: conv input is not a feature map")
+            w = const(n, ins[1], "conv weight")
+            c, h, wd = shapes[dev[ins[0]]]
+            grp = n.attrs.get("group", 1)
+            ks = list(n.attrs.get("kernel_shape", list(w.shape[2:])))
+            st_, pd, dl = list(n.attrs.get("strides", [1, 1])), list(n.attrs.get("pads", [0, 0, 0, 0])), list(n.attrs.get("dilations", [1, 1]))
+            if dl != [1, 1]:
+                raise ValueError(f"{who(n)}: dilations {dl} are not supported")
+            if len(pd) != 4 or len(set(pd)) != 1:
+                raise ValueError(f"{who(n)}: pads {pd} are not symmetric")
+            if w.ndim != 4 or len(ks) != 2 or ks[0] != ks[1] or list(w.shape[2:]) != ks or len(st_) != 2 or st_[0] != st_[1]:
+                raise ValueError(f"{who(n)}: conv weight {w.shape} kernel {ks} strides {st_} is not a square 2-d conv")
+            k, s, p = int(ks[0]), int(st_[0]), int(pd[0])
+            if grp == 1:
+                if w.shape[1] != c or k not in (1, 3) or s not in (1, 2) or p != k // 2:
+                    raise ValueError(f"{who(n)}: conv weight {w.shape} kernel {k} stride {s} pad {p} on {c} channels is not a "
+                                     "1x1 / 3x3, stride 1 / 2, pad k/2 conv of its input")
+                op = "conv"
+            else:
+                if not (grp == c == w.shape[0] and w.shape[1] == 1):
+                    raise ValueError(f"{who(n)}: grouped conv (group {grp} on {c} channels, weight {w.shape}) is not depthwise: not supported")
+                if not ((k == 3 and p == 1 and s in (1, 2)) or (k == h == wd and p == 0 and k % 2 == 1 and k <= 7 and s in (1, 2))):
+                    raise ValueError(f"{who(n)}: depthwise conv kernel {k} stride {s} pad {p} on a {h} x {wd} map is neither 3x3 / pad 1 / "
+                                     "stride 1 | 2 nor the global form (kernel = map size <= 7, pad 0)")
+                op = "dwconv"
+            b = const(n, ins[2], "conv bias").reshape(-1) if len(ins) > 2 else np.zeros(w.shape[0])
+            if b.shape != (w.shape[0],):
+                raise ValueError(f"{who(n)}: conv bias of shape {b.shape} on {w.shape[0]} channels")
+            dev[out] = add_step(op, dev[ins[0]], w, b, k, s, p, ((h + 2 * p - k) // s + 1, (wd + 2 * p - k) // s + 1))["out"]
+        elif n.op == "BatchNormalization":
+            st = open_step(n, ins[0]) if ins[0] in dev else None
+            if st is None or st["act"] or st["res"] is not None or len(ins) != 5:
+                raise ValueError(f"{who(n)}: BatchNormalization that does not directly follow a Conv or the fully connected layer")
+            sc, bi, mu, var = (const(n, t, "BatchNormalization parameter").reshape(-1) for t in ins[1:5])
+            if any(a.shape != (st["w"].shape[0],) for a in (sc, bi, mu, var)):
+                raise ValueError(f"{who(n)}: BatchNormalization parameters of {sc.shape[0]} channels on {st['w'].shape[0]}")
+            f = sc / np.sqrt(var + float(n.attrs.get("epsilon", 1e-5)))
+            st["w"], st["b"] = st["w"] * f[:, None, None, None], (st["b"] - mu) * f + bi
+            dev[out] = st["out"]
+        elif n.op == "PRelu":
+            st = open_step(n, ins[0]) if ins[0] in dev else None
+            if st is None or st["act"] or st["f32"] or len(ins) != 2:
+                raise ValueError(f"{who(n)}: PRelu that does not follow a Conv or a Conv + Add")
+            sl = const(n, ins[1], "PRelu slope")
+            C = st["w"].shape[0]
+            if sl.shape not in ((C,), (C, 1, 1), (1, C, 1, 1)):
+                raise ValueError(f"{who(n)}: PRelu slope of shape {sl.shape} on {C} channels (expected [C], [C,1,1] or [1,C,1,1])")
+            if st["op"] == "dwconv" and st["res"] is not None:
+                raise ValueError(f"{who(n)}: PRelu behind a residual add onto a depthwise conv")
+            st["act"], st["slope"] = 2, sl.reshape(-1)
+            dev[out] = st["out"]
+        elif n.op == "Add":
+            if len(ins) != 2:
+                raise ValueError(f"{who(n)}: Add of {len(ins)} tensors")
+            hs, ds = [t for t in ins if t in host], [t for t in ins if t in dev]
+            if len(hs) == 1 and len(ds) == 1:                          # MatMul + Add: the fully connected layer's bias
+                st = open_step(n, ds[0])
+                bv = np.asarray(host[hs[0]], dtype=np.float64).reshape(-1)
+                if st is None or not st["f32"] or st.get("gemm") != "MatMul" or bv.shape != st["b"].shape:
+                    raise ValueError(f"{who(n)}: Add of a constant that is not the bias of a MatMul")
+                st["b"], st["gemm"] = st["b"] + bv, "MatMul+Add"
+                dev[out] = st["out"]
+                continue
+            if len(ds) != 2:
+                raise ValueError(f"{who(n)}: Add of something that is not a feature map")
+            a, b = dev[ins[0]], dev[ins[1]]
+            if shapes[a] != shapes[b] or a == b:
+                raise ValueError(f"{who(n)}: Add of maps of shapes {shapes[a]} and {shapes[b]}" + (" (one map with itself)" if a == b else ""))
+            # the conv that runs LAST takes the other map as its residual, in front of its activation
+            made = {s["out"]: i for i, s in enumerate(steps)}
+            cand = [(made[st["out"]], st, o) for t, o in ((ins[0], b), (ins[1], a))
+                    for st in [open_step(n, t)] if st is not None and st["op"] == "conv" and not st["act"] and st["res"] is None
+                    and not st["f32"] and made[st["out"]] > made[o]]
+            if not cand:
+                raise ValueError(f"{who(n)}: Add whose later input does not come straight out of a linear 1x1 / 3x3 conv (no residual to fuse)")
+            _, st, o = max(cand, key=lambda c: c[0])
+            st["res"] = o
+            producer.pop(o, None)
+            dev[out] = st["out"]
+        elif n.op in ("Flatten", "Reshape"):
+            tid = dev.get(ins[0])
+            if tid is None or shapes[tid][1:] != (1, 1):
+                raise ValueError(f"{who(n)}: {n.op} of something that is not a 1 x 1 map")
+            if n.op == "Flatten" and n.attrs.get("axis", 1) != 1:
+                raise ValueError(f"{who(n)}: Flatten along axis {n.attrs['axis']}")
+            if n.op == "Reshape":
+                tgt = [int(v) for v in np.ravel(const(n, ins[1], "Reshape target"))] if len(ins) > 1 else []
+                if len(tgt) != 2 or tgt[1] not in (-1, shapes[tid][0]) or tgt[0] not in (-1, 0, 1) or tgt == [-1, -1]:
+                    raise ValueError(f"{who(n)}: Reshape target {tgt} does not flatten a {shapes[tid]} map to [N, {shapes[tid][0]}]")
+            producer.pop(tid, None)
+            flat[out] = tid
+        elif n.op in ("Gemm", "MatMul"):
+            tid = flat.get(ins[0])
+            if tid is None or len(ins) < 2:
+                raise ValueError(f"{who(n)}: {n.op} that does not read a flattened 1 x 1 map")
+            w = const(n, ins[1], "fully connected weight")
+            if n.op == "Gemm":
+                if n.attrs.get("alpha", 1.0) != 1.0 or n.attrs.get("beta", 1.0) != 1.0 or n.attrs.get("transA", 0):
+                    raise ValueError(f"{who(n)}: Gemm with alpha / beta / transA other than 1 / 1 / 0")
+                if not n.attrs.get("transB", 0):
+                    w = w.T
+            else:
+                w = w.T
+            c = shapes[tid][0]
+            if w.ndim != 2 or w.shape[1] != c:
+                raise ValueError(f"{who(n)}: fully connected weight {w.shape} on {c} features")
+            b = const(n, ins[2], "Gemm bias").reshape(-1) if n.op == "Gemm" and len(ins) > 2 else np.zeros(w.shape[0])
+            if b.shape != (w.shape[0],):
+                raise ValueError(f"{who(n)}: Gemm bias of shape {b.shape} on {w.shape[0]} outputs")
+            st = add_step("conv", tid, np.ascontiguousarray(w)[:, :, None, None], b, 1, 1, 0, (1, 1), f32=True)
+            st["gemm"] = n.op
+            dev[out] = st["out"]
+        else:
+            raise ValueError(f"{who(n)}: op {n.op} is not supported")
+
+    produced = [t for n in g.nodes for t in n.outputs]
+    outs = list(g.outputs) if g.outputs else [t for t in produced if t not in consumers]
+    if len(outs) != 1:
+        desc = ", ".join(f"{t!r} of {who(made_by[t])}" if t in made_by else repr(t) for t in outs)
+        raise ValueError(f"expected one graph output (the embedding), found {len(outs)}: {desc}")
+    tid = dev.get(outs[0])
+    st = producer.get(tid)
+    if st is None or not st["f32"] or st["res"] is not None:
+        raise ValueError(f"graph output {outs[0]!r} does not come out of the fully connected layer")
+    oshape = g.value_shapes.get(outs[0])
+    if shapes[tid][0] != 512 or (oshape is not None and (len(oshape) != 2 or oshape[1] != 512)):
+        raise ValueError(f"graph output {outs[0]!r}: embedding of {shapes[tid][0]} dimensions (declared {oshape}), expected [*, 512]")
+    used = {s[k] for s in steps for k in ("x", "res") if s.get(k) is not None} | {tid}
+    for s in steps:
+        if s["out"] not in used:
+            raise ValueError(f"a {s['op']} step's result (tensor {s['out']}, shape {shapes[s['out']]}) feeds nothing: not a recognition network")
+    return RecognitionPlan(steps, shapes, tid)

@@ -44,6 +44,23 @@ def pack_conv(w, b):
     return packed, bias, cin_p, cout_w
 
 
+def pack_dw(w, b, slope=None):
+    """w [C,1,k,k], b [C], slope [C] or None -> (f16 [k*k][Cp] tap-major as fr_dw_conv_f16 reads it, f32 bias [Cp], f32 slope
+    [Cp] or None, Cp = C padded to 8 with zeros)"""
+    w = np.asarray(w, dtype=np.float64)
+    c, _, k, _ = w.shape
+    cp = _ceil(c, 8)
+    wp = np.zeros((k * k, cp), dtype=np.float64)
+    wp[:, :c] = w.reshape(c, k * k).T
+    bias = np.zeros(cp, dtype=np.float32)
+    bias[:c] = np.asarray(b, dtype=np.float64).reshape(-1)
+    sl = None
+    if slope is not None:
+        sl = np.zeros(cp, dtype=np.float32)
+        sl[:c] = np.asarray(slope, dtype=np.float64).reshape(-1)
+    return wp.astype(np.float16), bias, sl, cp
+
+
 class _Arena:
     """The activation buffers of one plan at one batch size, and the launch list that fills them."""
 
@@ -86,6 +103,12 @@ class _Arena:
                 self.calls.append((lib.fr_det_conv_f16, (_lib.ptr(self.buf[s["x"]]), _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(res), _lib.ptr(out),
                                                          N, hi, wi, cin_p, cout_w, s["k"], s["stride"], s["pad"], h, w, cs, ldo,
                                                          int(s["relu"]), int(s["f32"]), 0)))
+            elif s["op"] == "dwconv":
+                ci, hi, wi = plan.shapes[s["x"]]
+                wt, bias, cp = det.packed[s["wkey"]]
+                assert cp == _ceil(ci, 8) == _ceil(c, 8)
+                self.calls.append((lib.fr_dw_conv_f16, (_lib.ptr(self.buf[s["x"]]), _lib.ptr(wt), _lib.ptr(bias), None, _lib.ptr(out), N, hi, wi,
+                                                        cp, s["k"], s["stride"], s["pad"], h, w, int(s["relu"]))))
             elif s["op"] == "pool":
                 ci, hi, wi = plan.shapes[s["x"]]
                 self.calls.append((lib.fr_det_pool_f16, (_lib.ptr(self.buf[s["x"]]), _lib.ptr(out), N, hi, wi, _ceil(ci, 8), h, w, s["kind"],
@@ -147,6 +170,9 @@ class SCRFDHIP:
                     if s["op"] == "conv" and s["wkey"] not in self.packed:
                         wt, bias, cin_p, cout_w = pack_conv(s["w"], s["b"])
                         self.packed[s["wkey"]] = (torch.from_numpy(wt).to(self.device), torch.from_numpy(bias).to(self.device), cin_p, cout_w)
+                    elif s["op"] == "dwconv" and s["wkey"] not in self.packed:
+                        wt, bias, _, cp = pack_dw(s["w"], s["b"])
+                        self.packed[s["wkey"]] = (torch.from_numpy(wt).to(self.device), torch.from_numpy(bias).to(self.device), cp)
                 self._plans[key] = p
             return p
 

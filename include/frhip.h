@@ -37,7 +37,8 @@ typedef void* fr_stream_t;
  * 106: fr_gallery_match_view_f16 / _f8 with their _workspace functions, fr_gallery_update_rows_shadow).  The SCRFD detector's
  * entries (fr_det_conv_f16, fr_det_conv_weight_halves, fr_det_input_f16, fr_det_pool_f16, fr_det_upsample_add_f16, fr_scrfd_decode)
  * were ADDED under 106: no existing signature or struct changed shape, and a binding written against them finds a library
- * without them by the missing symbol.  fr_version() returns the value the library was built
+ * without them by the missing symbol.  The same holds for fr_dw_conv_f16 and fr_det_conv_act_f16 (depthwise layers and the
+ * PReLU epilogue of the plan recogniser, mbf.py), added under 106 later.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -619,6 +620,31 @@ size_t fr_det_conv_weight_halves(int Cin, int cout_packed, int K);
 int fr_det_conv_f16(const void* x, const void* w, const float* bias, const void* residual, void* y, int N, int H, int W,
                     int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo, int cout_store, int ldo,
                     int relu, int out_f32, int tile, fr_stream_t stream);
+/* fr_det_conv_act_f16: fr_det_conv_f16 with a choice of activation - y = act( conv(x, w) + bias [+ residual] ), the epilogue in
+ * that order.  Operands, packing, outputs and `tile` as above.  The layers of a MobileFaceNet recogniser that are no depthwise
+ * convs: the 3x3 stride-2 stem on the 8-channel aligned crop and the 1x1 expand convs (PReLU), the 1x1 project convs (linear,
+ * with the block's input as residual) and the final fully connected layer as a 1x1 conv on a 1x1 map (out_f32).
+ *   act       0: none, 1: ReLU (the bits of fr_det_conv_f16 with relu = 1), 2: PReLU v < 0 ? v * slope[channel] : v
+ *   slope     f32 [cout_packed], read only when act == 2 (values past the layer's own channels are never stored) */
+int fr_det_conv_act_f16(const void* x, const void* w, const float* bias, const float* slope, const void* residual, void* y,
+                        int N, int H, int W, int Cin, int cout_packed, int K, int stride, int pad, int Ho, int Wo,
+                        int cout_store, int ldo, int act, int out_f32, int tile, fr_stream_t stream);
+/* Depthwise convolution: y[n,oy,ox,c] = act( sum over the in-bounds taps (ky, kx) of x[n, oy*stride - pad + ky, ox*stride - pad
+ * + kx, c] * w[ky*K + kx][c] + bias[c] ).  The layer MobileFaceNet (w600k_mbf.onnx) and the small SCRFD detectors (det_500m.onnx)
+ * are built from; memory-bound, no matrix-core work.
+ *   x         f16 [N,H,W,C], C a multiple of 8 (fr_det_conv_f16's activation layout; padded channels hold zeros)
+ *   w         f16 [K*K][C], tap-major: the 8 channels a lane owns are one 16-byte load per tap
+ *   bias      f32 [C]
+ *   slope     f32 [C], read only when act == 2
+ *   y         f16 [N,Ho,Wo,C]; Ho = (H + 2 pad - K) / stride + 1 and Wo likewise, computed by the host and checked here
+ *   K         odd, <= 7; stride 1 or 2; pad 0 .. K / 2, zero padding: taps outside the input are skipped
+ *   act       0: none, 1: ReLU, 2: PReLU
+ * f32 accumulation over the taps in (ky, kx) order (a product of two f16 is exact in f32), + bias, activation, ONE rounding to
+ * f16.  An element's bits depend on neither N, the image's position in the batch nor the launch's tiling.  K == H == W with pad 0
+ * (one output pixel per image and channel: MobileFaceNet's 7x7 tail) walks the taps from global memory; every other shape
+ * stages the input rows of a band of output rows in LDS, so each input element is fetched about once. */
+int fr_dw_conv_f16(const void* x, const void* w, const float* bias, const float* slope, void* y, int N, int H, int W, int C, int K,
+                   int stride, int pad, int Ho, int Wo, int act, fr_stream_t stream);
 /* canvas u8 [N,H,W,3] BGR -> y f16 [N,H,W,8]: channels 0..2 = (R, G, B) as (v - 127.5) / 128 (exact in f16), 3..7 = 0
  * (insightface's SCRFD blob: input_mean = 127.5, input_std = 128, swapRB). */
 int fr_det_input_f16(const uint8_t* canvas, void* y, int N, int H, int W, fr_stream_t stream);
