@@ -394,9 +394,7 @@ __global__ __launch_bounds__(256) void gallery_first_above(const float* __restri
     for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < N; r += (int64_t)gridDim.x * 4) {
         const float4* g = reinterpret_cast<const float4*>(G + r * GD + lane * 8);
         const float4 g0 = g[0], g1 = g[1];
-        float s = qv[0] * g0.x + qv[1] * g0.y + qv[2] * g0.z + qv[3] * g0.w + qv[4] * g1.x + qv[5] * g1.y +
-                  qv[6] * g1.z + qv[7] * g1.w;
-        s = wave_sum(s);
+        const float s = row_dot_wave8(qv, g0, g1);
         const bool pass = inclusive ? (s >= thr) : (s > thr);
         if (pass) {
             unsigned long long key = ((unsigned long long)r << 32) | __float_as_uint(s);

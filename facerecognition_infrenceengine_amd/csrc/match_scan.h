@@ -41,6 +41,16 @@ __device__ __forceinline__ void stage_query_group(const float* __restrict__ Q, i
     }
 }
 
+// dot of one 512-float row with a query spread over a wave, lane l holding elements 8l .. 8l+7 of both (qv: the query's
+// eight, g0 / g1: the row's): eight terms left to right, then wave_sum.  The one arithmetic form of the first-hit
+// consumers (gallery_first_above in match.hip, unknown_assign_batch in unknown_assign.hip): the library is built with
+// -ffp-contract=off, so both get the same bits for the same row and query.
+__device__ __forceinline__ float row_dot_wave8(const float (&qv)[8], const float4 g0, const float4 g1) {
+    float s = qv[0] * g0.x + qv[1] * g0.y + qv[2] * g0.z + qv[3] * g0.w + qv[4] * g1.x + qv[5] * g1.y +
+              qv[6] * g1.z + qv[7] * g1.w;
+    return wave_sum(s);
+}
+
 // One tile on v_mfma_f32_32x32x2_f32 (an exact k-ordered fmaf chain): A = 32 gallery rows, B = 32 queries.
 // gp = this lane's gallery row + 4 * h, qp = this lane's staged query + 4 * h (h = lane >> 5); a row past the
 // end (ok == false) contributes zeros.  acc[reg] = score(tile row (reg & 3) + 8 * (reg >> 2) + 4 * h, query lane & 31).

@@ -6,7 +6,6 @@ mean -> duplicate check -> pickled float32[512] row) and /root/reference/peopleC
 the reference's duplicate check becomes one `fr_gallery_first_above_f32` scan of the device gallery.
 """
 import pickle
-from collections import deque
 
 import numpy as np
 import torch
@@ -103,39 +102,76 @@ def first_above(lib, matcher, embedding, thr, inclusive):
 
 class UnknownClusters:
     """peopleCount.py:52-91 + :432-449 on the device: cluster means live in one [C,512] matrix (NOT unit rows,
-    exactly as the reference keeps them); assignment = first cluster with dot(avg, e) >= threshold."""
+    exactly as the reference keeps them); assignment = first cluster with dot(avg, e) >= threshold.
+
+    All of the state is on the device - the means, the ``depth``-deep rings they are the mean of, and the counters
+    (include/frhip.h fr_unknown_assign_batch_f32) - and a whole batch of faces is assigned, in the reference's
+    sequential order, by ONE launch with no host synchronisation (``assign_batch``)."""
+
+    STATE_N, STATE_OVERFLOW, STATE_HEADER = 0, 1, 4         # include/frhip.h FR_UNKNOWN_*
 
     def __init__(self, device="cuda:0", threshold=0.65, depth=10, capacity=1024):
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device)
-        self.threshold, self.depth = threshold, depth
-        self.avg = torch.zeros((capacity, DIM), dtype=torch.float32, device=self.device)
-        self.hist = []                  # per cluster: deque of device rows (maxlen = depth)
-        self.counts = []
+        self.threshold, self.depth, self.capacity = threshold, int(depth), int(capacity)
+        if self.depth < 1 or self.capacity < 1:
+            raise ValueError("UnknownClusters needs depth >= 1 and capacity >= 1")
+        self.avg = torch.zeros((self.capacity, DIM), dtype=torch.float32, device=self.device)
+        self._hist = torch.zeros((self.capacity, self.depth, DIM), dtype=torch.float32, device=self.device)
+        self._state = torch.zeros(self.STATE_HEADER + 3 * self.capacity, dtype=torch.int32, device=self.device)
+
+    def assign_batch(self, E, take=None):
+        """Rows of ``E`` (device or host float32 [F,512]) in order; ``take``: optional device int32 / bool [F], rows whose
+        entry is 0 are skipped.  Returns three device int32 [F] tensors: the cluster index of each row (-1: not taken,
+        -2: refused because all ``capacity`` clusters exist - see ``overflowed``), 1 where the row created its cluster,
+        and the cluster's detection count after the row.  One launch on the current stream, no host synchronisation."""
+        if not torch.is_tensor(E):
+            E = torch.from_numpy(np.ascontiguousarray(np.asarray(E, np.float32)))
+        E = E.to(self.device, torch.float32).reshape(-1, DIM).contiguous()
+        F = E.shape[0]
+        if take is not None:
+            take = torch.as_tensor(take).to(self.device, torch.int32).reshape(-1).contiguous()
+            if take.shape[0] != F:
+                raise ValueError(f"take has {take.shape[0]} entries for {F} rows")
+        cluster, is_new, count = (torch.empty(F, dtype=torch.int32, device=self.device) for _ in range(3))
+        with torch.cuda.device(self.device):
+            self.lib.fr_unknown_assign_batch_f32(_lib.ptr(E), _lib.ptr(take), F, DIM, float(self.threshold),
+                                                 _lib.ptr(self.avg), _lib.ptr(self._hist), _lib.ptr(self._state),
+                                                 self.capacity, self.depth, _lib.ptr(cluster), _lib.ptr(is_new),
+                                                 _lib.ptr(count), _lib.stream_ptr())
+        return cluster, is_new, count
 
     def assign(self, embedding):
-        e = torch.from_numpy(np.asarray(embedding, np.float32).reshape(1, DIM)).to(self.device)
-        n = len(self.hist)
-        hit = -1
-        if n:
-            idx = torch.empty(1, dtype=torch.int64, device=self.device)
-            score = torch.empty(1, dtype=torch.float32, device=self.device)
-            ws = torch.empty(8, dtype=torch.uint8, device=self.device)
-            with torch.cuda.device(self.device):
-                self.lib.fr_gallery_first_above_f32(_lib.ptr(e), _lib.ptr(self.avg), 1, n, DIM, float(self.threshold), 1,
-                                                    0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), 8, _lib.stream_ptr())
-            hit = int(idx.item())
-        if hit < 0:
-            if n == self.avg.shape[0]:
-                raise RuntimeError("UnknownClusters capacity exceeded")
-            self.hist.append(deque([e], maxlen=self.depth))
-            self.counts.append(1)
-            self.avg[n] = e[0]              # first embedding is the mean as is (peopleCount.py:66)
-            return n
-        self.hist[hit].append(e)
-        self.counts[hit] += 1
-        rows = torch.cat(list(self.hist[hit])).contiguous()
-        with torch.cuda.device(self.device):
-            self.lib.fr_mean_rows_f32(_lib.ptr(rows), rows.shape[0], DIM, _lib.ptr(self.avg[hit]), _lib.stream_ptr())
+        """One embedding -> its cluster index (``assign_batch`` of one row and one read-back)."""
+        hit = int(self.assign_batch(np.asarray(embedding, np.float32).reshape(1, DIM))[0].item())
+        if hit == -2:
+            raise RuntimeError("UnknownClusters capacity exceeded")
         return hit
+
+    @property
+    def overflowed(self):
+        """Rows refused so far because the bank was full (sticky)."""
+        return int(self._state[self.STATE_OVERFLOW].item())
+
+    def _counters(self):
+        s = self._state.cpu().numpy()
+        n = int(s[self.STATE_N])
+        return n, s[self.STATE_HEADER:self.STATE_HEADER + 3 * n].reshape(n, 3)
+
+    @property
+    def counts(self):
+        """detection_count per cluster (a copy from the device)."""
+        return [int(c) for c in self._counters()[1][:, 2]]
+
+    @property
+    def hist(self):
+        """Per cluster, the rows of its ring oldest first (a copy from the device): a list of float32 [K,512] arrays."""
+        n, c = self._counters()
+        rows = self._hist[:n].cpu().numpy()
+        out = []
+        for k in range(n):
+            length, head = int(c[k, 0]), int(c[k, 1])
+            start = head if length == self.depth else 0
+            out.append(rows[k, [(start + j) % self.depth for j in range(length)]])
+        return out

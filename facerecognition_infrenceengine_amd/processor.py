@@ -320,43 +320,13 @@ class FaceRecognitionProcessor:
         copy stream -> detect -> align -> embed -> company view scan -> decision), one host synchronisation at the
         end.  Returns a list (per frame) of lists of the dicts ``recognize`` returns, or None when the company has
         no gallery (the reference returns the frame untouched then, infrenceServer.py:523-525)."""
-        import torch
-        from .ingest import FrameIngest, RaggedIngest
         if self.face_detector is None:
             self.initialize_detector()
-        det = self.face_detector
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
         if len(matcher) == 0:
             logger.warning("No embeddings found for company %s", company_id)
             return None
-        arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
-        n, (h, w) = len(arr), arr[0].shape[:2]
-        det_size = getattr(det, "det_size", None)
-        if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr) or \
-                (det_size is None and any(a.shape != (h, w, 3) for a in arr)):
-            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
-        stages = self.__dict__.setdefault("_stages", {})
-        key = (n, h, w) if det_size is None else (tuple(a.shape[:2] for a in arr), det_size)
-        if key not in stages:
-            while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
-                stages.pop(next(iter(stages)))
-            stages[key] = [FrameIngest(n, h, w, det.device, depth=2) if det_size is None else
-                           RaggedIngest(key[0], det_size, det.device, depth=2), 0]
-        ring, turn = stages[key]
-        stages[key][1] = turn + 1
-        with det._lock, torch.cuda.device(det.device):
-            if det_size is None:
-                host = ring.host_buffer(turn)
-                for i, a in enumerate(arr):
-                    host[i] = a
-                dev, ready = ring.upload(turn)
-                r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True)      # results go to the host anyway
-            else:                                         # one arena, one copy, one engine pass whatever the frames' sizes
-                for i, a in enumerate(arr):
-                    ring.host_frame(turn, i)[...] = a
-                dev, table, ready = ring.upload(turn)
-                r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, table=table, det_scale=ring.det_scale)
-            ring.release(turn)
+        n, r = _detect_embed_batch(self, self.face_detector, frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
                                                      r["normed_embedding"])
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
@@ -415,10 +385,16 @@ class CameraProcessor:
     """Counting path, peopleCount.py:822-896: whole gallery, 0.45 recognised / < 0.35 unknown,
     the [0.35, 0.45) band is dropped."""
 
-    def __init__(self, embedding_manager, manager, face_detector=None):
+    def __init__(self, embedding_manager, manager, face_detector=None, unknown_clusters=None):
+        """``unknown_clusters`` (``process_batch`` only): an ``enrol.UnknownClusters`` bank that clusters the unknown faces
+        of every camera on the device, or a dict camera_id -> bank for cameras of different campuses (cameras that map
+        to the same bank object share it; a camera without an entry is not clustered)."""
         self.embedding_manager, self.manager, self.face_detector = embedding_manager, manager, face_detector
         self.recognition_threshold = 0.45
         self.unknown_threshold = 0.35
+        self.unknown_clusters = unknown_clusters
+        self._cluster_lock = threading.Lock()     # a bank's launches are queued in the order its batches arrive
+        self._bank_masks = {}                     # bank layout of a batch -> device frame masks (uploaded once)
 
     def initialize_detector(self):
         if self.face_detector is None:
@@ -457,6 +433,123 @@ class CameraProcessor:
             logger.error("Error in face detection: %s", e)
         return stats
 
+    def _banks(self, camera_ids, device):
+        """[(bank, device bool [n] mask of its frames, or None when every frame is its)] in batch order."""
+        import torch
+        uc = self.unknown_clusters
+        if uc is None:
+            return []
+        if not isinstance(uc, dict):
+            return [(uc, None)]
+        banks, layout = [], []
+        for cam in camera_ids:
+            b = uc.get(cam)
+            k = next((i for i, x in enumerate(banks) if x is b), None) if b is not None else -1
+            if k is None:
+                banks.append(b)
+                k = len(banks) - 1
+            layout.append(k)
+        if len(banks) == 1 and all(k == 0 for k in layout):
+            return [(banks[0], None)]
+        key = tuple(layout)
+        masks = self._bank_masks.get(key)
+        if masks is None:                         # a new camera layout: the one upload (and wait) this path ever makes
+            while len(self._bank_masks) >= 8:
+                self._bank_masks.pop(next(iter(self._bank_masks)))
+            masks = self._bank_masks[key] = [torch.tensor([k == i for k in layout], dtype=torch.bool).to(device)
+                                             for i in range(len(banks))]
+        return list(zip(banks, masks))
+
+    def process_batch(self, frames, camera_ids):
+        """Batch form of ``process_frame``: ``frames`` = list of BGR uint8 frames (of one size, or of any sizes when the
+        engine has a ``det_size``), ``camera_ids`` = their cameras.  ONE pass of the slot pipeline over the batch,
+        whole-gallery scan, the 0.45 / 0.35 decision and - with ``unknown_clusters`` - the clustering of the unknown
+        faces (re-normalised rows, one ``assign_batch`` per bank, batch order) all stay on the device; then ONE group
+        of device-to-host copies.  The manager then gets, frame by frame and face by face, the calls ``process_frame``
+        would make (one ``timestamp`` for the whole batch).  With clusters, a manager that defines
+        ``process_unknown_cluster(camera_id, timestamp, cluster, is_new, detection_count, bbox)`` gets that call for
+        a clustered face instead of ``process_unknown_detection`` (no embedding travels to the host); a face its bank
+        refused (capacity) goes to ``process_unknown_detection``.  Returns one stats dict per frame, with clusters plus
+        ``"unknown_clusters": [(cluster, is_new, detection_count), ...]``.  Errors are logged and swallowed as
+        ``process_frame``'s are; only ``len(camera_ids) != len(frames)`` raises (ValueError), before anything runs."""
+        import torch
+        from . import _lib
+        if self.face_detector is None:
+            self.initialize_detector()
+        n = len(frames)
+        if len(camera_ids) != n:                  # the caller's mistake, and the one error that raises (gallery or not)
+            raise ValueError(f"{n} frames but {len(camera_ids)} camera ids")
+        clustered = self.unknown_clusters is not None
+        stats = [dict({"faces": 0, "recognized": 0, "unknown": 0}, **({"unknown_clusters": []} if clustered else {}))
+                 for _ in range(n)]
+        matcher, metadata = self.embedding_manager.get_matcher_for_company(None)
+        if len(matcher) == 0 or n == 0:
+            return stats
+        timestamp = datetime.utcnow()
+        try:
+            det = self.face_detector
+            n, r = _detect_embed_batch(self, det, frames)
+            E = r["normed_embedding"]
+            matcher, metadata, idx, score = _match_fresh(self.embedding_manager, None, matcher, metadata, E)
+            dec = matcher.decide_device(idx, score, self.recognition_threshold, self.unknown_threshold)
+            cap = r["bbox"].shape[1]
+            S = n * cap
+            banks = self._banks(camera_ids, det.device)
+            use_cb = bool(banks) and hasattr(self.manager, "process_unknown_cluster")
+            ints = [idx, dec.to(torch.int64)]
+            qn = None
+            if banks:
+                with self._cluster_lock, torch.cuda.device(det.device):
+                    qn = torch.empty_like(E)                                          # peopleCount.py:863
+                    _lib.load().fr_l2norm_rows_f32(_lib.ptr(E), _lib.ptr(qn), S, 512, _lib.stream_ptr())
+                    unknown = (torch.arange(cap, device=det.device)[None, :] < r["counts"][:, None]) & (dec.view(n, cap) == 0)
+                    trip = None
+                    for bank, mask in banks:
+                        take = (unknown if mask is None else unknown & mask[:, None]).reshape(-1)
+                        t = torch.stack(bank.assign_batch(qn, take))                  # [3,S]: cluster, is_new, count
+                        trip = t if trip is None else torch.where(take[None, :], t, trip)   # a slot belongs to one bank
+                ints.append(trip.reshape(-1).to(torch.int64))
+            # ---- the one group of device -> host copies
+            counts = r["counts"].cpu().numpy()
+            ints = torch.cat(ints).cpu().numpy()
+            flt = torch.cat([score.reshape(S, 1), r["bbox"].reshape(S, 4)], dim=1).cpu().numpy()
+            idx_h, dec_h = ints[:S], ints[S:2 * S]
+            trip_h = ints[2 * S:].reshape(3, S) if banks else None
+            score_h, bb = flt[:, 0], flt[:, 1:].astype(int)                           # :531 truncation
+            q = None
+            unbanked = isinstance(self.unknown_clusters, dict) and any(self.unknown_clusters.get(c) is None for c in camera_ids)
+            if not use_cb or unbanked:                                                # the embeddings travel as well
+                e = (E if qn is None else qn).cpu().numpy()
+                q = e / np.linalg.norm(e, axis=1, keepdims=True) if qn is None else e
+            refused = 0
+            for f in range(n):
+                st, cam = stats[f], camera_ids[f]
+                st["faces"] = int(counts[f])
+                for s in range(f * cap, f * cap + int(counts[f])):
+                    if dec_h[s] == 1:
+                        pid = matcher.ids[idx_h[s]]
+                        self.manager.process_detection(pid, metadata[pid], cam, timestamp, float(score_h[s]))
+                        st["recognized"] += 1
+                    elif dec_h[s] == 0:
+                        cl = int(trip_h[0, s]) if trip_h is not None else -1
+                        if cl != -1:
+                            st["unknown_clusters"].append((cl, int(trip_h[1, s]), int(trip_h[2, s])))
+                        if cl >= 0 and use_cb:
+                            self.manager.process_unknown_cluster(cam, timestamp, cl, int(trip_h[1, s]), int(trip_h[2, s]),
+                                                                 bb[s].tolist())
+                        else:
+                            if cl == -2:
+                                refused += 1
+                            if q is None:                 # only a refused row needs its embedding here: a second, rare copy
+                                q = qn.cpu().numpy()
+                            self.manager.process_unknown_detection(cam, timestamp, q[s], bb[s].tolist())
+                        st["unknown"] += 1
+            if refused:
+                logger.warning("Unknown-person clusters full: %d faces of this batch were not clustered", refused)
+        except Exception as e:
+            logger.error("Error in face detection: %s", e)
+        return stats
+
 
 def _detect_embed(detector, frame):
     """detect -> align -> embed of one frame under the engine's lock: one engine may be shared by threads
@@ -467,6 +560,44 @@ def _detect_embed(detector, frame):
         return detector.detect_embed_device(dev)
     with lock:
         return detector.detect_embed_device(dev)
+
+
+def _detect_embed_batch(owner, det, frames):
+    """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
+    ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape) -> copy stream ->
+    ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
+    engine has a ``det_size``.  Returns (number of frames, the slot results: device tensors)."""
+    import torch
+    from .ingest import FrameIngest, RaggedIngest
+    arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
+    n, (h, w) = len(arr), arr[0].shape[:2]
+    det_size = getattr(det, "det_size", None)
+    if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr) or \
+            (det_size is None and any(a.shape != (h, w, 3) for a in arr)):
+        raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
+    stages = owner.__dict__.setdefault("_stages", {})
+    key = (n, h, w) if det_size is None else (tuple(a.shape[:2] for a in arr), det_size)
+    if key not in stages:
+        while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
+            stages.pop(next(iter(stages)))
+        stages[key] = [FrameIngest(n, h, w, det.device, depth=2) if det_size is None else
+                       RaggedIngest(key[0], det_size, det.device, depth=2), 0]
+    ring, turn = stages[key]
+    stages[key][1] = turn + 1
+    with det._lock, torch.cuda.device(det.device):
+        if det_size is None:
+            host = ring.host_buffer(turn)
+            for i, a in enumerate(arr):
+                host[i] = a
+            dev, ready = ring.upload(turn)
+            r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True)      # results go to the host anyway
+        else:                                         # one arena, one copy, one engine pass whatever the frames' sizes
+            for i, a in enumerate(arr):
+                ring.host_frame(turn, i)[...] = a
+            dev, table, ready = ring.upload(turn)
+            r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, table=table, det_scale=ring.det_scale)
+        ring.release(turn)
+    return n, r
 
 
 def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):

@@ -216,6 +216,27 @@ int fr_cosine_matrix_f32(const float* A, const float* B, int F, int N, int D, fl
                          fr_stream_t stream);
 /* out = mean of K rows, summed in row order (np.mean(.., axis=0): trainingServer.py:355, peopleCount.py:79) */
 int fr_mean_rows_f32(const float* x, int K, int D, float* out, fr_stream_t stream);
+/* Unknown-person clustering of a whole batch in ONE launch (peopleCount.py:441-449 + UnknownPerson.update :68-75), the
+ * rows of E [F][512] in order, row f taken when take == NULL or take[f] != 0:
+ *   hit  = lowest c < n with dot(avg[c], E[f]) >= thr (f32, inclusive; the dot of fr_gallery_first_above_f32, same bits):
+ *          E[f] is pushed into cluster c's ring (depth rows, the oldest is overwritten once full), its detection_count
+ *          goes up by one and avg[c] = (oldest + ... + newest) / (float)K, summed in that order (np.mean of the deque);
+ *   miss = cluster n is created: avg[n] = E[f] as is, ring = that one row, detection_count 1, n += 1;
+ *   miss with n == capacity: nothing changes, out_cluster[f] = -2 and the sticky overflow counter goes up by one.
+ * out_cluster[f]: the cluster index (-1: row not taken, -2: refused at capacity); out_new[f]: 1 when the row created its
+ * cluster; out_count[f]: the cluster's detection_count after the row (0 for -1 / -2).
+ * State, all caller-owned device memory that only this entry writes: avg f32 [capacity][512], hist f32 [capacity][depth][512],
+ * state int32 [FR_UNKNOWN_STATE_INTS(capacity)] - zero it once to start empty: [FR_UNKNOWN_N] live clusters,
+ * [FR_UNKNOWN_OVERFLOW] refused rows, then per cluster c at FR_UNKNOWN_HEADER + 3 c: ring length, ring head (the slot the
+ * next push writes), detection_count.  One workgroup walks the batch (the row-to-row dependency is real); no allocation,
+ * no synchronisation.  Added under ABI 106: no existing signature changed. */
+#define FR_UNKNOWN_N 0
+#define FR_UNKNOWN_OVERFLOW 1
+#define FR_UNKNOWN_HEADER 4
+#define FR_UNKNOWN_STATE_INTS(capacity) (FR_UNKNOWN_HEADER + 3 * (capacity))
+int fr_unknown_assign_batch_f32(const float* E, const int32_t* take, int F, int D, float thr, float* avg, float* hist,
+                                int32_t* state, int capacity, int depth, int32_t* out_cluster, int32_t* out_new,
+                                int32_t* out_count, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- embed ----
  * a-4  ArcFace IResNet conv stack (inside FaceAnalysis.get, infrenceServer.py:528).
