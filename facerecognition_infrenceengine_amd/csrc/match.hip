@@ -161,14 +161,7 @@ __global__ void gallery_update_rows(float* __restrict__ G, void* __restrict__ sh
     const float* p = rows + (int64_t)i * GD;
     float4 v0 = *reinterpret_cast<const float4*>(p + lane * 4);
     float4 v1 = *reinterpret_cast<const float4*>(p + 256 + lane * 4);
-    if (normalise) {
-        float ss = v0.x * v0.x + v0.y * v0.y + v0.z * v0.z + v0.w * v0.w;
-        ss += v1.x * v1.x + v1.y * v1.y + v1.z * v1.z + v1.w * v1.w;
-        ss = wave_sum(ss);
-        const float nrm = sqrtf(ss);
-        v0.x /= nrm; v0.y /= nrm; v0.z /= nrm; v0.w /= nrm;
-        v1.x /= nrm; v1.y /= nrm; v1.z /= nrm; v1.w /= nrm;
-    }
+    if (normalise) unit_row_wave4(v0, v1);          // match_scan.h: shared with the enrolment batch
     const int64_t slot = slots[i];
     float* o = G + slot * GD;
     *reinterpret_cast<float4*>(o + lane * 4) = v0;
@@ -441,13 +434,8 @@ __global__ void cosine_matrix(const float* __restrict__ A, const float* __restri
     const int lane = threadIdx.x & 63;
     if (pair >= F * N) return;
     const int f = pair / N, n = pair - f * N;
-    float ab = 0.f, aa = 0.f, bb = 0.f;
-    for (int c = lane; c < D; c += 64) {
-        const float a = A[(int64_t)f * D + c], b = B[(int64_t)n * D + c];
-        ab += a * b; aa += a * a; bb += b * b;
-    }
-    ab = wave_sum(ab); aa = wave_sum(aa); bb = wave_sum(bb);
-    if (lane == 0) out[pair] = ab / (sqrtf(aa) * sqrtf(bb));
+    const float c = cosine_rows_wave(A + (int64_t)f * D, B + (int64_t)n * D, D, lane);     // match_scan.h
+    if (lane == 0) out[pair] = c;
 }
 
 extern "C" int fr_cosine_matrix_f32(const float* A, const float* B, int F, int N, int D, float* out,

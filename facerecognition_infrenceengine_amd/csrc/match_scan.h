@@ -1,6 +1,7 @@
 // What the exact f32 gallery scans (match.hip: top-1, match_topk.hip: top-K) have in common: the geometry of a
 // scan block, the padding test of a query group, the order of two candidates, the staging of a query group and
-// the dot products of one 32-row gallery tile.
+// the dot products of one 32-row gallery tile - and the per-row arithmetic (first-hit dot, cosine, unit row) that the
+// first-hit consumers and the enrolment batch (enrol_batch.hip) share with the entries of match.hip.
 #pragma once
 #include "common.h"
 
@@ -42,13 +43,39 @@ __device__ __forceinline__ void stage_query_group(const float* __restrict__ Q, i
 }
 
 // dot of one 512-float row with a query spread over a wave, lane l holding elements 8l .. 8l+7 of both (qv: the query's
-// eight, g0 / g1: the row's): eight terms left to right, then wave_sum.  The one arithmetic form of the first-hit
+// eight, g0 / g1: the row's): eight terms left to right (row_dot_lane8: one lane's share), then wave_sum.  The one arithmetic form of the first-hit
 // consumers (gallery_first_above in match.hip, unknown_assign_batch in unknown_assign.hip): the library is built with
 // -ffp-contract=off, so both get the same bits for the same row and query.
+__device__ __forceinline__ float row_dot_lane8(const float (&qv)[8], const float4 g0, const float4 g1) {
+    return qv[0] * g0.x + qv[1] * g0.y + qv[2] * g0.z + qv[3] * g0.w + qv[4] * g1.x + qv[5] * g1.y +
+           qv[6] * g1.z + qv[7] * g1.w;
+}
 __device__ __forceinline__ float row_dot_wave8(const float (&qv)[8], const float4 g0, const float4 g1) {
-    float s = qv[0] * g0.x + qv[1] * g0.y + qv[2] * g0.z + qv[3] * g0.w + qv[4] * g1.x + qv[5] * g1.y +
-              qv[6] * g1.z + qv[7] * g1.w;
-    return wave_sum(s);
+    return wave_sum(row_dot_lane8(qv, g0, g1));
+}
+
+// cosine of two D-float rows by one wave, lane l taking elements l, l + 64, ...: the arithmetic of fr_cosine_matrix_f32
+// (match.hip) and of the pose-consistency test of fr_enrol_batch_f32 (enrol_batch.hip); every lane returns the value.
+__device__ __forceinline__ float cosine_rows_wave(const float* a, const float* b, int D, int lane) {
+    float ab = 0.f, aa = 0.f, bb = 0.f;
+    for (int c = lane; c < D; c += 64) {
+        const float x = a[c], y = b[c];
+        ab += x * y; aa += x * x; bb += y * y;
+    }
+    ab = wave_sum(ab); aa = wave_sum(aa); bb = wave_sum(bb);
+    return ab / (sqrtf(aa) * sqrtf(bb));
+}
+
+// v / ||v|| of one 512-float row held by a wave as v0 = elements 4l .. 4l+3, v1 = elements 256 + 4l .. 256 + 4l+3: the
+// arithmetic of fr_gallery_update_rows_f32(normalise=1), which is also that of fr_l2norm_rows_f32 at D = 512 (its sum
+// starts from 0.f + the first four squares: the same bits).
+__device__ __forceinline__ void unit_row_wave4(float4& v0, float4& v1) {
+    float ss = v0.x * v0.x + v0.y * v0.y + v0.z * v0.z + v0.w * v0.w;
+    ss += v1.x * v1.x + v1.y * v1.y + v1.z * v1.z + v1.w * v1.w;
+    ss = wave_sum(ss);
+    const float nrm = sqrtf(ss);
+    v0.x /= nrm; v0.y /= nrm; v0.z /= nrm; v0.w /= nrm;
+    v1.x /= nrm; v1.y /= nrm; v1.z /= nrm; v1.w /= nrm;
 }
 
 // One tile on v_mfma_f32_32x32x2_f32 (an exact k-ordered fmaf chain): A = 32 gallery rows, B = 32 queries.

@@ -4,6 +4,10 @@ Mirrors /root/reference/trainingServer.py:170-247,328,355-358,393 (largest face 
 mean -> duplicate check -> pickled float32[512] row) and /root/reference/peopleCount.py:52-91,432-449
 (10-deep running mean, first cluster with dot >= 0.65).  The O(N) per-row GridFS read + cosine loop of
 the reference's duplicate check becomes one `fr_gallery_first_above_f32` scan of the device gallery.
+
+``Enroller.enrol`` is the one-job form; ``Enroller.enrol_batch`` / ``enrol_slots`` run a whole batch of jobs with one
+engine pass and one `fr_enrol_batch_f32` call, giving job for job what enrolling them one after the other gives
+(DESIGN.md 4.6d).
 """
 import pickle
 
@@ -11,8 +15,14 @@ import numpy as np
 import torch
 
 from . import _lib
+from .gallery import GalleryView, StaleViewError
 
 DIM = 512
+# include/frhip.h FR_ENROL_* (tests/test_enrol_batch_abi.py compares)
+ENROL_DONE, ENROL_NO_FACE, ENROL_DIFFERENT, ENROL_DUPLICATE = 0, 1, 2, 3
+ENROL_MAX_POSES, ENROL_MAX_JOBS = 8, 256
+STATUS_NAMES = {ENROL_DONE: "done", ENROL_NO_FACE: "no_face", ENROL_DIFFERENT: "different_people",
+                ENROL_DUPLICATE: "duplicate"}
 
 
 def largest_face_index(faces):
@@ -65,8 +75,8 @@ class Enroller:
         return out.cpu().numpy()
 
     def check_duplicate(self, new_embedding, matcher):
-        """trainingServer.py:170-200 against a GalleryMatcher of unit rows: (is_dup, id of the first row with
-        cosine > threshold)."""
+        """trainingServer.py:170-200 against a GalleryMatcher of unit rows, or a company's GalleryView: (is_dup, id of the
+        first row, in the matcher's / the view's order, with cosine > threshold)."""
         idx, score = first_above(self.lib, matcher, new_embedding, self.duplicate_threshold, inclusive=False)
         return (idx >= 0), (matcher.ids[idx] if idx >= 0 else None)
 
@@ -84,9 +94,174 @@ class Enroller:
             return {"status": "duplicate", "duplicate_id": dup_id, "embedding": avg}
         return {"status": "done", "embedding": avg, "blob": pickle.dumps(avg)}       # :393 gallery row format
 
+    # ------------------------------------------------------------------ batches
+    def enrol_slots(self, slots, job_images, gallery):
+        """The whole arithmetic of a batch of jobs on the device, no host synchronisation (include/frhip.h
+        fr_enrol_batch_f32: largest face, pose consistency, mean, duplicate check against ``gallery`` and against the
+        batch's own earlier ``done`` jobs, in job order).
+
+        slots: the dict of one ``FaceAnalysis.detect_embed_slots`` call, or a list of such dicts (their images are numbered
+        on, in list order).  job_images: per job, the list of its image indices, in the reference's position order.
+        gallery: a GalleryMatcher of unit rows or a GalleryView (a stale one raises StaleViewError).
+        Returns device tensors on the current stream: status i32 [J] (ENROL_*), pair i32 [J,2], face i32 [I] (the chosen
+        slot of each image in ``job_images`` order, flattened; -1: no face), avg f32 [J,512], row f32 [J,512], dup_pos
+        i64 [J] (gallery position, len(gallery) + i for the batch's job i, -1), dup_score f32 [J]."""
+        parts = list(slots) if isinstance(slots, (list, tuple)) else [slots]
+        job_images = [list(im) for im in job_images]
+        J = len(job_images)
+        if J > ENROL_MAX_JOBS:
+            raise ValueError(f"at most {ENROL_MAX_JOBS} jobs a batch (got {J})")
+        max_poses = max((len(im) for im in job_images), default=0)
+        if max_poses > ENROL_MAX_POSES:
+            raise ValueError(f"at most {ENROL_MAX_POSES} images a job (got {max_poses})")
+        firsts, row0 = [], 0                       # first row of every image: known from the shapes alone
+        for p in parts:
+            n, cap = p["bbox"].shape[0], p["bbox"].shape[1]
+            firsts += [row0 + k * cap for k in range(n)]
+            row0 += n * cap
+        order = [int(i) for im in job_images for i in im]
+        if any(not 0 <= i < len(firsts) for i in order):
+            raise ValueError("job_images names an image the slots do not hold")
+        G, view, N = _gallery_args(gallery)
+        dev, I = self.device, len(order)
+        job_first = np.cumsum([0] + [len(im) for im in job_images])
+        # one pinned staging block, one asynchronous copy: image order, first rows, job_first
+        host = torch.from_numpy(np.concatenate([order, [firsts[i] for i in order], job_first]).astype(np.int32))
+        status = torch.empty(J, dtype=torch.int32, device=dev)
+        pair = torch.empty((J, 2), dtype=torch.int32, device=dev)
+        face = torch.empty(I, dtype=torch.int32, device=dev)
+        avg = torch.empty((J, DIM), dtype=torch.float32, device=dev)
+        row = torch.empty((J, DIM), dtype=torch.float32, device=dev)
+        dup_pos = torch.empty(J, dtype=torch.int64, device=dev)
+        dup_score = torch.empty(J, dtype=torch.float32, device=dev)
+        out = {"status": status, "pair": pair, "face": face, "avg": avg, "row": row, "dup_pos": dup_pos,
+               "dup_score": dup_score}
+        if J == 0:
+            return out
+        with torch.cuda.device(dev):
+            meta = host.pin_memory().to(dev, non_blocking=True)
+            E = torch.cat([p["normed_embedding"].reshape(-1, DIM) for p in parts]).to(dev, torch.float32).contiguous()
+            bbox = torch.cat([p["bbox"].reshape(-1, 4) for p in parts]).to(dev, torch.float32).contiguous()
+            counts = torch.cat([p["counts"].reshape(-1) for p in parts]).to(dev, torch.int32)
+            img_first, jf = meta[I:2 * I], meta[2 * I:]
+            img_count = counts.index_select(0, meta[:I].to(torch.int64)).contiguous()     # the detector's counts, never read here
+            ws = torch.empty(int(self.lib.fr_enrol_batch_workspace(J, N)), dtype=torch.uint8, device=dev)
+            self.lib.fr_enrol_batch_f32(_lib.ptr(E), _lib.ptr(bbox), E.shape[0], _lib.ptr(img_first), _lib.ptr(img_count),
+                                        I, _lib.ptr(jf), J, max_poses, DIM, _lib.ptr(G), _lib.ptr(view), N,
+                                        float(self.similarity_threshold), float(self.duplicate_threshold),
+                                        _lib.ptr(status), _lib.ptr(pair), _lib.ptr(face), _lib.ptr(avg), _lib.ptr(row),
+                                        _lib.ptr(dup_pos), _lib.ptr(dup_score), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+        return out
+
+    def _engine_pass(self, images):
+        """One ``detect_embed_slots`` call per image shape (one call in all with a ``det_size`` engine), grouped as
+        camera.CameraManager.process_batch groups frames.  images: BGR arrays, None for what did not decode.
+        Returns (slot dicts, image index of every input image)."""
+        mixed = getattr(self.app, "det_size", None) is not None
+        by_shape = {}
+        for k, im in enumerate(images):
+            if im is not None:
+                by_shape.setdefault(None if mixed else tuple(im.shape), []).append(k)
+        parts, index, base = [], [None] * len(images), 0
+        for ks in by_shape.values():
+            frames = [np.ascontiguousarray(images[k]) for k in ks]
+            frames = self.app._to_device(frames if mixed else np.stack(frames))
+            parts.append(self.app.detect_embed_slots(frames))
+            for n, k in enumerate(ks):
+                index[k] = base + n
+            base += len(ks)
+        if any(i is None for i in index) or not parts:          # an image without a face: one slot whose count is 0
+            parts.append({"counts": torch.zeros(1, dtype=torch.int32, device=self.device),
+                          "bbox": torch.zeros((1, 1, 4), dtype=torch.float32, device=self.device),
+                          "normed_embedding": torch.zeros((1, DIM), dtype=torch.float32, device=self.device)})
+            index = [base if i is None else i for i in index]
+        return parts, index
+
+    def enrol_batch(self, jobs, gallery, ids=None, commit=False):
+        """``enrol`` for a list of jobs: job for job what ``enrol(jobs[j], gallery)`` returns when every ``done`` job's row
+        is upserted (normalise=True) behind the gallery before the next job runs - a batch sees its own earlier jobs.
+        jobs: a list of lists of images (BGR arrays, or encoded bytes as ``process_image`` accepts; what does not decode
+        is an image without a face).  gallery: a GalleryMatcher of unit rows or a GalleryView.  ids: optional, one id per
+        job.  One engine pass, one ``enrol_slots``, one group of device-to-host copies.
+
+        Returns an ``EnrolBatchResult``: a list with one dict per job, keyed as ``enrol``'s (status, pair, duplicate_id,
+        embedding, blob); a duplicate of the batch's own job i carries ``duplicate_of_job: i`` and ``duplicate_id =
+        ids[i]`` (None without ``ids``).  commit=True (needs a GalleryView and ``ids``): the ``done`` rows are upserted into
+        ``gallery.gallery`` under their ids in one call, and ``result.view`` is the view of the old ids followed by the
+        done ids in job order - the gallery the next batch is checked against."""
+        jobs = [list(job) for job in jobs]
+        if len(jobs) > ENROL_MAX_JOBS:
+            raise ValueError(f"at most {ENROL_MAX_JOBS} jobs a batch (got {len(jobs)})")
+        if any(len(job) > ENROL_MAX_POSES for job in jobs):
+            raise ValueError(f"at most {ENROL_MAX_POSES} images a job (got {max(len(job) for job in jobs)})")
+        if ids is not None and len(ids) != len(jobs):
+            raise ValueError("ids and jobs disagree")
+        if commit and not (isinstance(gallery, GalleryView) and ids is not None):
+            raise ValueError("commit=True needs a GalleryView and ids")
+        _gallery_args(gallery)                                       # a stale view: before the engine runs
+        result = EnrolBatchResult()
+        if not jobs:
+            result.view = gallery if commit else None
+            return result
+        images = []
+        for job in jobs:
+            for im in job:
+                if isinstance(im, (bytes, bytearray, memoryview)):
+                    from .ingest import decode_image
+                    im = decode_image(im)
+                images.append(im)
+        job_images, k = [], 0
+        with torch.cuda.device(self.device):
+            parts, index = self._engine_pass(images)
+            for job in jobs:
+                job_images.append(index[k:k + len(job)])
+                k += len(job)
+            out = self.enrol_slots(parts, job_images, gallery)
+            names = ("status", "pair", "avg", "dup_pos")
+            host = [torch.empty(out[n].shape, dtype=out[n].dtype).pin_memory() for n in names]
+            for h, n in zip(host, names):
+                h.copy_(out[n], non_blocking=True)
+            torch.cuda.current_stream().synchronize()                # the one synchronisation of the batch
+        status, pair, avg, dup_pos = (h.numpy() for h in host)
+        N = len(gallery.ids) if isinstance(gallery, GalleryView) else gallery.G.shape[0]
+        for j in range(len(jobs)):
+            st = int(status[j])
+            r = {"status": STATUS_NAMES[st]}
+            if st == ENROL_DIFFERENT:
+                r["pair"] = (int(pair[j, 0]), int(pair[j, 1]))
+            elif st in (ENROL_DONE, ENROL_DUPLICATE):
+                r["embedding"] = avg[j].copy()
+                if st == ENROL_DONE:
+                    r["blob"] = pickle.dumps(r["embedding"])        # :393 gallery row format
+                elif dup_pos[j] < N:
+                    r["duplicate_id"] = gallery.ids[int(dup_pos[j])]
+                else:
+                    r["duplicate_of_job"] = int(dup_pos[j]) - N
+                    r["duplicate_id"] = ids[r["duplicate_of_job"]] if ids is not None else None
+            result.append(r)
+        if commit:
+            done = [j for j in range(len(jobs)) if int(status[j]) == ENROL_DONE]
+            if done:
+                rows = out["avg"][torch.tensor(done, device=self.device)]
+                gallery.gallery.upsert([ids[j] for j in done], rows, normalise=True)
+            have = set(gallery.ids)
+            result.view = gallery.gallery.view(list(gallery.ids) + [ids[j] for j in done if ids[j] not in have])
+        return result
+
+
+def _gallery_args(gallery):
+    """(rows, view slots or None, number of positions) of a GalleryMatcher or a GalleryView (which must be current)."""
+    if isinstance(gallery, GalleryView):
+        if gallery.generation != gallery.gallery.generation:
+            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
+        return gallery.gallery.G, gallery.slots, len(gallery.ids)
+    return gallery.G, None, gallery.G.shape[0]
+
 
 def first_above(lib, matcher, embedding, thr, inclusive):
-    """Lowest gallery row whose dot with the L2-normalised query passes the threshold."""
+    """Lowest gallery row whose dot with the L2-normalised query passes the threshold.  ``matcher``: a GalleryMatcher, or
+    a GalleryView (position in the view's order; scanned through its slot list by fr_gallery_first_above_blocked_f32)."""
+    G, view, N = _gallery_args(matcher)
     q = torch.from_numpy(np.asarray(embedding, np.float32).reshape(1, DIM)).to(matcher.device)
     qn = torch.empty_like(q)
     idx = torch.empty(1, dtype=torch.int64, device=matcher.device)
@@ -95,9 +270,20 @@ def first_above(lib, matcher, embedding, thr, inclusive):
     with torch.cuda.device(matcher.device):
         s = _lib.stream_ptr()
         lib.fr_l2norm_rows_f32(_lib.ptr(q), _lib.ptr(qn), 1, DIM, s)
-        lib.fr_gallery_first_above_f32(_lib.ptr(qn), _lib.ptr(matcher.G), 1, matcher.G.shape[0], DIM, float(thr),
-                                       1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), 8, s)
+        if view is None:
+            lib.fr_gallery_first_above_f32(_lib.ptr(qn), _lib.ptr(G), 1, N, DIM, float(thr),
+                                           1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), 8, s)
+        else:
+            lib.fr_gallery_first_above_blocked_f32(_lib.ptr(qn), _lib.ptr(G), _lib.ptr(view), None, 1, N, DIM, float(thr),
+                                                   1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws),
+                                                   8, s)
     return int(idx.item()), float(score.item())
+
+
+class EnrolBatchResult(list):
+    """What ``Enroller.enrol_batch`` returns: the list of per-job dicts; ``view`` is the GalleryView that holds the rows
+    a ``commit=True`` call enrolled (None without a commit)."""
+    view = None
 
 
 class UnknownClusters:

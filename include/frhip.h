@@ -38,7 +38,9 @@ typedef void* fr_stream_t;
  * entries (fr_det_conv_f16, fr_det_conv_weight_halves, fr_det_input_f16, fr_det_pool_f16, fr_det_upsample_add_f16, fr_scrfd_decode)
  * were ADDED under 106: no existing signature or struct changed shape, and a binding written against them finds a library
  * without them by the missing symbol.  The same holds for fr_dw_conv_f16 and fr_det_conv_act_f16 (depthwise layers and the
- * PReLU epilogue of the plan recogniser, mbf.py), added under 106 later.  fr_version() returns the value the library was built
+ * PReLU epilogue of the plan recogniser, mbf.py), added under 106 later, and for fr_unknown_assign_batch_f32,
+ * fr_gallery_first_above_blocked_f32 and fr_enrol_batch_f32 / fr_enrol_batch_workspace (the counting and enrolment paths in
+ * batches), added under 106 after those.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -237,6 +239,56 @@ int fr_mean_rows_f32(const float* x, int K, int D, float* out, fr_stream_t strea
 int fr_unknown_assign_batch_f32(const float* E, const int32_t* take, int F, int D, float thr, float* avg, float* hist,
                                 int32_t* state, int capacity, int depth, int32_t* out_cluster, int32_t* out_new,
                                 int32_t* out_count, fr_stream_t stream);
+
+/* fr_gallery_first_above_f32 for MANY queries: the same result contract (out_idx[f] = the first position whose dot with
+ * Q[f] passes the threshold, + row_offset; -1 / 0.f when none) and, for every (query, gallery) pair the older entry can
+ * express, the same index and the same score bits.  What differs is the traffic: a gallery row is fetched once per block of
+ * 16 queries, not once per query.
+ *   view == NULL: position p is row p of G [N][512].  view != NULL: position p is row view[p] of G (int64 storage slots of a
+ *   slab, read as given and not checked, as fr_gallery_match_view_f32 reads them); out_idx is the VIEW position.
+ *   take == NULL: every query is scanned.  take != NULL (int32 [F]): query f with take[f] == 0 costs no scan work and
+ *   reports -1 / 0.f.
+ * N < 2^31.  workspace: F * 8 bytes.  Added under ABI 106. */
+int fr_gallery_first_above_blocked_f32(const float* Q, const float* G, const int64_t* view, const int32_t* take, int F,
+                                       int64_t N, int D, float thr, int inclusive, int64_t row_offset, int64_t* out_idx,
+                                       float* out_score, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* Enrolment of J jobs in one call (trainingServer.py:170-247, 312-398 for a whole batch): job for job the result of
+ * enrolling the jobs one after the other, every `done` job's row being visible to the duplicate check of the later jobs.
+ * Inputs, all on the device: E f32 [S][512] normed embeddings and bbox f32 [S][4] (x1, y1, x2, y2), one row per face slot;
+ * image i owns rows img_first[i] .. img_first[i] + img_count[i] - 1 (img_count: the face counts as the detector wrote
+ * them; both are clamped so that no row outside [0, S) is read); job j owns images job_first[j] .. job_first[j+1] - 1 of
+ * the I images, in the caller's order (job_first int32 [J+1]).  max_poses: the largest number of images of a job, which
+ * the caller knows on the host.  The gallery: G / view / N as fr_gallery_first_above_blocked_f32, unit rows.
+ * Per job, in job order:
+ *   1. per image, the face = the first slot with the largest area (x2 - x1) * (y2 - y1), f32, each operation rounded
+ *      once, strict '>' in slot order; an image with no face is skipped.  face[i] = that slot, -1 for no face.
+ *   2. K faces found; K == 0: FR_ENROL_NO_FACE.
+ *   3. pairs (a, b), a < b, in lexicographic order over the K found embeddings: the first with cosine < sim_thr (the bits
+ *      of fr_cosine_matrix_f32) -> FR_ENROL_DIFFERENT, pair[j] = (a, b) (indices among the FOUND embeddings).
+ *   4. avg[j] = the K rows summed in order / (float)K (the bits of fr_mean_rows_f32); not re-normalised.
+ *   5. q = avg / ||avg|| (the bits of fr_l2norm_rows_f32, which are the bits fr_gallery_update_rows_f32(normalise=1) stores:
+ *      row[j] is both the job's query and the row it enrols).  The first gallery position p with dot(q, row_p) > dup_thr
+ *      (fr_gallery_first_above_f32's dot and bits) -> FR_ENROL_DUPLICATE, dup_pos[j] = p, dup_score[j] = that dot.
+ *   6. otherwise the first earlier job i < j that ended FR_ENROL_DONE with dot(q, row[i]) > dup_thr -> FR_ENROL_DUPLICATE,
+ *      dup_pos[j] = N + i.  A gallery hit always wins (gallery rows come first); jobs that did not end DONE add no row.
+ *   7. otherwise FR_ENROL_DONE.
+ * Outputs, device: status int32 [J]; pair int32 [J][2] ((-1, -1) unless DIFFERENT); face int32 [I]; avg f32 [J][512]
+ * (zero rows for NO_FACE / DIFFERENT); row f32 [J][512] (the unit row of a DONE / DUPLICATE job, else zero); dup_pos
+ * int64 [J] (-1 unless DUPLICATE); dup_score f32 [J] (0 unless DUPLICATE).
+ * Four launches whatever J, I and N are, no allocation, no synchronisation.  J > FR_ENROL_MAX_JOBS, max_poses >
+ * FR_ENROL_MAX_POSES and D != 512 are refused before any launch; J == 0 returns FR_OK and reads no pointer.
+ * workspace: fr_enrol_batch_workspace(J, N) bytes.  Added under ABI 106. */
+#define FR_ENROL_DONE 0
+#define FR_ENROL_NO_FACE 1
+#define FR_ENROL_DIFFERENT 2
+#define FR_ENROL_DUPLICATE 3
+#define FR_ENROL_MAX_POSES 8
+#define FR_ENROL_MAX_JOBS 256
+size_t fr_enrol_batch_workspace(int J, int64_t N);
+int fr_enrol_batch_f32(const float* E, const float* bbox, int S, const int32_t* img_first, const int32_t* img_count, int I,
+                       const int32_t* job_first, int J, int max_poses, int D, const float* G, const int64_t* view, int64_t N,
+                       float sim_thr, float dup_thr, int32_t* status, int32_t* pair, int32_t* face, float* avg, float* row,
+                       int64_t* dup_pos, float* dup_score, void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- embed ----
  * a-4  ArcFace IResNet conv stack (inside FaceAnalysis.get, infrenceServer.py:528).
