@@ -1,6 +1,7 @@
 """Dev tool: a 64 x 1080p detector batch alone with (a) everything exact (f32 R-/O-Net second layers, every kept P-Net cell
-re-evaluated), (b) + split-precision R-/O-Net conv2 (MTCNNHIP.split_ro), (c) + band-only exact P-Net pass (pnet_band): phase
-times by event marks."""
+re-evaluated), (b) + split-precision R-/O-Net conv2 and tail GEMMs (MTCNNHIP.split_ro) + band-only exact P-Net pass (pnet_band),
+(c) + the first R-/O-Net layer on the f16 matrix cores (split_conv1): phase times by event marks.  (The f32 tail behind a split conv2
+lost this A/B in round 4, profiles/r04_ab_detector_changes.txt, and is gone.)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench, warnings
@@ -10,8 +11,8 @@ app = FaceAnalysis(name="synthetic", arch="r100", cap_o=4).prepare(ctx_id=0)
 frames = bench.synth_frames(64, 1080, 1920, 0, torch.device("cuda:0"))
 app.det.refined_cells = torch.zeros(1, dtype=torch.int32, device="cuda")
 for rep in range(2):
-    for split, band, tail, c1 in ((False, False, False, False), (True, True, False, False), (True, True, True, False), (True, True, True, True)):
-        app.det.split_ro, app.det.pnet_band, app.det.split_tail, app.det.split_conv1 = split, band, tail, c1
+    for split, band, c1 in ((False, False, False), (True, True, False), (True, True, True)):
+        app.det.split_ro, app.det.pnet_band, app.det.split_conv1 = split, band, c1
         for _ in range(3):
             app.det.detect_batch(frames)
         torch.cuda.synchronize()
@@ -33,5 +34,5 @@ for rep in range(2):
         extra = " P-Net cells re-evaluated per batch: %d" % (int(app.det.refined_cells[0]) // 10)
         if split:
             extra += "; exact-pass crops (R, O): %s" % [int(app.det._ro_lists[k][0]) for k in (0, 1)]
-        print("split_ro", split, "pnet_band", band, "split_tail", tail, "split_conv1", c1, "detect ms %.3f" % (e0.elapsed_time(e1) / 10), {k: round(v, 3) for k, v in acc.items()},
+        print("split_ro", split, "pnet_band", band, "split_conv1", c1, "detect ms %.3f" % (e0.elapsed_time(e1) / 10), {k: round(v, 3) for k, v in acc.items()},
               "faces", int(out[3].sum()), extra, flush=True)
