@@ -82,7 +82,13 @@ int fr_gallery_update_rows_f32(float* G, const int64_t* slots, const float* rows
  * rows per query, which are then re-scored EXACTLY in f32 against G32 (may be NULL: scores then come from the
  * coarse scan) and picked by max score / lowest row - the rule of infrenceServer.py:535-542.
  * G16: f16 [N,512] (fr_f32_to_f16 of the unit rows); G8: OCP fp8 e4m3 [N,512] scaled by FR_F8_SCALE
- * (fr_f32_to_f8).  seg_counts / seg_len: see fr_gallery_match_f32. */
+ * (fr_f32_to_f8).  seg_counts / seg_len: see fr_gallery_match_f32.
+ * With G32 == NULL nothing is re-scored and the result is the coarse scan's own: out_score[f] is the coarse maximum -
+ * the largest dot product of the stored operands (the f16 roundings of query and rows; fp8: the e4m3 codes of
+ * 256 x query and 256 x row, saturated at +-448, the sum divided by 256^2), accumulated in f32 on the matrix cores -
+ * and out_idx[f] is the first row of the first group of 4 consecutive rows (rows 4g .. 4g + 3) that attains it, plus
+ * row_offset: a multiple of 4 plus row_offset, not necessarily the row that scored.  (-1, -1.0f) if no coarse score
+ * exceeds -1.  The view forms have no such mode: they refuse a NULL G32. */
 #define FR_TOPK 4
 #define FR_TOPK8 8
 #define FR_F8_SCALE 256.0f
