@@ -96,6 +96,10 @@ SIGNATURES = {
     "fr_gallery_topk_view_f16_workspace": (_Z, [_I, _L, _I]),
     "fr_gallery_topk_view_f16": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "fr_gallery_topk_view_masked_f32": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _Z, _P, _P]),
+    "fr_gallery_match_grouped_workspace": (_Z, [_I, _L]),
+    "fr_gallery_match_grouped_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _P, _P, _P, _Z, _P, _I, _P]),
+    "fr_gallery_topk_grouped_workspace": (_Z, [_I, _L, _I]),
+    "fr_gallery_topk_grouped_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _I, _I, _P, _P, _P, _Z, _P, _I, _P]),
     "fr_gallery_gmax_update": (_I, [_P, _P, _L, _I, _P, _P]),
     "fr_f32_to_f8": (_I, [_P, _P, _L, _P]),
     "fr_f32_to_f16": (_I, [_P, _P, _L, _P]),

@@ -41,6 +41,8 @@ class CameraManager:
         self.running = False
         self.threads = []
         self.frame_queues, self.result_queue = {}, None
+        self.company_of = {}                   # source -> company id of the start call that added it
+        self._control = threading.Lock()       # start / stop calls, one at a time
         self.stats = {"batches": 0, "frames": 0, "dropped_results": 0, "largest_batch": 0, "dead_sources": []}
 
     # ---- capture side (infrenceServer.py:573-601)
@@ -108,29 +110,42 @@ class CameraManager:
                     time.sleep(0.0005)
         return got
 
-    def process_cameras(self, sources, company_id):
+    def process_cameras(self, sources=None, company_id=None):
+        """The batching loop.  Every turn drains ALL sources running at that moment (``start_cameras`` may add some
+        while the loop runs), each under the company it was started with; ``sources`` / ``company_id``, when given,
+        are registered first."""
         if self.processor is None:
             from .processor import FaceRecognitionProcessor
             self.processor = FaceRecognitionProcessor(self.embedding_manager)
+        for s in sources or ():
+            self.company_of.setdefault(s, company_id)
         while self.running:
-            batch = self.take_batch(sources)
+            batch = self.take_batch([s for s in list(self.frame_queues) if s in self.company_of])
             if not batch:
                 continue
             try:
-                self.process_batch(batch, company_id)
+                self.process_batch(batch, [self.company_of.get(s, company_id) for s, _ in batch])
             except Exception as e:                         # logged and survived, as the reference's loop (:620-621)
                 logger.error("Error processing cameras %s: %s", [s for s, _ in batch], e)
 
     def process_batch(self, batch, company_id):
         """batch: [(source, frame)].  Frames of one size go through the engine together - all of them in ONE call when the
-        processor takes mixed sizes (``accepts_mixed_sizes``: an engine with a ``det_size``); results leave in batch order."""
+        processor takes mixed sizes (``accepts_mixed_sizes``: an engine with a ``det_size``); results leave in batch order.
+        ``company_id``: one id for the whole batch, or a list / tuple aligned with ``batch``.  Frames of several
+        companies still go through the engine together: the processor call gets the per-frame list then, and the plain
+        id whenever all its frames share one."""
+        mixed_ids = isinstance(company_id, (list, tuple))
+        if mixed_ids and len(company_id) != len(batch):
+            raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
         by_shape = {}
         mixed = getattr(self.processor, "accepts_mixed_sizes", False)
         for k, (_, f) in enumerate(batch):
             by_shape.setdefault(None if mixed else tuple(f.shape), []).append(k)
         results = [None] * len(batch)
         for ks in by_shape.values():
-            res = self.processor.recognize_batch([batch[k][1] for k in ks], company_id)
+            ids = [company_id[k] for k in ks] if mixed_ids else [company_id]
+            one = all(c == ids[0] for c in ids[1:])
+            res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids)
             for j, k in enumerate(ks):
                 results[k] = None if res is None else res[j]
         self.stats["batches"] += 1
@@ -150,21 +165,38 @@ class CameraManager:
         ``self.result_queue`` as ``(source, frame)``.  A consumer thread always drains that queue (the reference's
         cv2.imshow loop, :648-667): it calls ``display(source, frame)`` when given, otherwise it keeps the latest
         processed frame per source (``latest_frame(source)``) - so the unchanged ``POST /api/camera/start`` route,
-        which passes no display, neither fills the 10-deep queue nor makes the GPU work for dropped results."""
-        if self.running:
-            return
-        if self.capture_factory is None:
-            raise RuntimeError("CameraManager needs capture_factory=<callable(source) -> capture object>")
-        self.running = True
-        sources = list(sources)
-        self.frame_queues = {s: queue.Queue(maxsize=2) for s in sources}      # :629
-        self.result_queue = queue.Queue(maxsize=10)                            # :630
-        for s in sources:
-            t = threading.Thread(target=self.capture_frames, args=(s, self.frame_queues[s]), daemon=True)
-            t.start(); self.threads.append(t)
-        t = threading.Thread(target=self.process_cameras, args=(sources, company_id), daemon=True)
-        t.start(); self.threads.append(t)
+        which passes no display, neither fills the 10-deep queue nor makes the GPU work for dropped results.
 
+        Called while running, it ADDS the sources that are not running yet, under the given company (the reference's
+        ``start_cameras`` appends processes, each with the ``company_id`` of its request: infrenceServer.py:624-646):
+        a queue and a capture thread each, and the one batching loop serves them from its next turn on, together with
+        the cameras of the other companies.  Sources that already run are left as they are - a repeated identical
+        start is a no-op - and ``display`` is that of the first start."""
+        with self._control:
+            if self.capture_factory is None:
+                raise RuntimeError("CameraManager needs capture_factory=<callable(source) -> capture object>")
+            if self.running:
+                self._add_sources([s for s in sources if s not in self.company_of], company_id)
+                return
+            self.running = True
+            self.frame_queues, self.company_of = {}, {}
+            self.result_queue = queue.Queue(maxsize=10)                        # :630
+            self._add_sources(list(sources), company_id)
+            t = threading.Thread(target=self.process_cameras, daemon=True)
+            t.start(); self.threads.append(t)
+            self._start_consumer(display)
+
+    def _add_sources(self, sources, company_id):
+        for s in sources:
+            if s in self.company_of:
+                continue
+            q = queue.Queue(maxsize=2)                                         # :629
+            self.company_of[s] = company_id
+            self.frame_queues[s] = q
+            t = threading.Thread(target=self.capture_frames, args=(s, q), daemon=True)
+            t.start(); self.threads.append(t)
+
+    def _start_consumer(self, display):
         def keep_latest(source, frame):
             with self._latest_lock:
                 self.latest[source] = frame
@@ -188,8 +220,12 @@ class CameraManager:
             return self.latest.get(source)
 
     def stop_cameras(self):
-        self.running = False
-        for t in self.threads:
-            t.join(timeout=5)
-        self.threads.clear()
+        """Stops every camera of every company."""
+        with self._control:
+            self.running = False
+            for t in self.threads:
+                t.join(timeout=5)
+            self.threads.clear()
+            self.company_of = {}
+            self.frame_queues = {}
         logger.info("All camera threads stopped")

@@ -14,28 +14,14 @@
 
 struct BestPair { float s; int64_t i; };
 
-// VIEW: row r of the scanned gallery is storage slot view[r] of G (a per-company view of one device-resident
-// slab, no copy of the rows); the winner index is the VIEW position, so the order/tie rule is the view's.
+// The scan of the query group staged in qs [QG][QPAD] against rows [0, N) of G, by the whole block (it holds barriers:
+// every thread calls it, after the barrier that ends the staging).  VIEW: row r is storage slot view[r] of G (a
+// per-company view of one device-resident slab, no copy of the rows); the winner index is the VIEW position, so the
+// order/tie rule is the view's.  Threads 0 .. 31 return the block's best pair of query lane tid; qs is overwritten.
 template <bool VIEW>
-__global__ __launch_bounds__(256) void gallery_scan_f32(const float* __restrict__ Q, const float* __restrict__ G,
-                                                        const int64_t* __restrict__ view,
-                                                        int F, int64_t N, float* __restrict__ ws_score,
-                                                        int64_t* __restrict__ ws_idx,
-                                                        const int32_t* __restrict__ seg_counts, int seg_len) {
-    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+__device__ __forceinline__ BestPair scan_group_best(const float* __restrict__ G, const int64_t* __restrict__ view,
+                                                    int64_t N, float* qs) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q0 = blockIdx.y * QG;
-    // query slots beyond their segment's count are padding (sharded match: SURVEY.md 8(e)); a group made of
-    // padding only does no work (the reduce reports (-1, -1) for every padding slot)
-    if (seg_counts && !group_has_valid(seg_counts, seg_len, q0, min(q0 + QG, F))) return;
-    // stage the query group (zero rows beyond F)
-    for (int e = tid; e < QG * (GD / 4); e += 256) {
-        int r = e / (GD / 4), c = e % (GD / 4);
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q0 + r < F) v = *reinterpret_cast<const float4*>(Q + (int64_t)(q0 + r) * GD + c * 4);
-        *reinterpret_cast<float4*>(&qs[r * QPAD + c * 4]) = v;
-    }
-    __syncthreads();
     const int r = lane & 31, h = lane >> 5;
     float best = -INFINITY;
     int64_t besti = -1;
@@ -44,20 +30,8 @@ __global__ __launch_bounds__(256) void gallery_scan_f32(const float* __restrict_
         const int64_t row = t * 32 + r;
         const bool ok = row < N;
         const int64_t slot = VIEW ? (ok ? view[row] : 0) : (ok ? row : 0);
-        const float* gp = G + slot * GD + 4 * h;
-        const float* qp = &qs[r * QPAD + 4 * h];
-        float16v acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int kk = 0; kk < GD / 8; ++kk) {
-            float4 a = *reinterpret_cast<const float4*>(gp + kk * 8);
-            float4 b = *reinterpret_cast<const float4*>(qp + kk * 8);
-            if (!ok) a = make_float4(0.f, 0.f, 0.f, 0.f);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-        }
-        // acc[reg] = score(gallery row t*32 + (reg&3) + 8*(reg>>2) + 4*h, query q0 + r)
+        const float16v acc = scan_tile_f32(G + slot * GD + 4 * h, &qs[r * QPAD + 4 * h], ok);
+        // acc[reg] = score(gallery row t*32 + (reg&3) + 8*(reg>>2) + 4*h, query lane r)
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             int64_t gi = t * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
@@ -77,13 +51,84 @@ __global__ __launch_bounds__(256) void gallery_scan_f32(const float* __restrict_
     if (h == 0) { ls[wave * 32 + r] = best; li[wave * 32 + r] = besti; }
     __syncthreads();
     if (tid < 32) {
-        float bs = ls[tid]; int64_t bi = li[tid];
-        for (int w = 1; w < 4; ++w) if (li[w * 32 + tid] >= 0) take_better(bs, bi, ls[w * 32 + tid], li[w * 32 + tid]);
-        if (q0 + tid < F) {
-            ws_score[(int64_t)blockIdx.x * F + q0 + tid] = bs;
-            ws_idx[(int64_t)blockIdx.x * F + q0 + tid] = bi;
+        best = ls[tid]; besti = li[tid];
+        for (int w = 1; w < 4; ++w) if (li[w * 32 + tid] >= 0) take_better(best, besti, ls[w * 32 + tid], li[w * 32 + tid]);
+    }
+    return BestPair{best, besti};
+}
+
+template <bool VIEW>
+__global__ __launch_bounds__(256) void gallery_scan_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                        const int64_t* __restrict__ view,
+                                                        int F, int64_t N, float* __restrict__ ws_score,
+                                                        int64_t* __restrict__ ws_idx,
+                                                        const int32_t* __restrict__ seg_counts, int seg_len) {
+    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+    const int tid = threadIdx.x;
+    const int q0 = blockIdx.y * QG;
+    // query slots beyond their segment's count are padding (sharded match: SURVEY.md 8(e)); a group made of
+    // padding only does no work (the reduce reports (-1, -1) for every padding slot)
+    if (seg_counts && !group_has_valid(seg_counts, seg_len, q0, min(q0 + QG, F))) return;
+    stage_query_group(Q, F, q0, qs);                  // zero rows beyond F
+    __syncthreads();
+    const BestPair b = scan_group_best<VIEW>(G, view, N, qs);
+    if (tid < 32 && q0 + tid < F) {
+        ws_score[(int64_t)blockIdx.x * F + q0 + tid] = b.s;
+        ws_idx[(int64_t)blockIdx.x * F + q0 + tid] = b.i;
+    }
+}
+
+// GROUPED: block (x, g) scans query group g - the up to QG query slots qmap[g * QG ..] names, gathered from anywhere in
+// Q - through ITS view, views[gtab[2g] .. + gtab[2g + 1]); partial results go to ws [gridDim.x][ngroups * QG], entry
+// g * QG + lane.  Same staging, tile arithmetic and merges as gallery_scan_f32<true>, so a query's score bits and tie
+// rule do not depend on the group or lane it lands in.  A group with an empty view or without a real slot returns at
+// once and writes nothing: gallery_reduce_grouped applies the same two tests and reads nothing of it.  The grid's x is
+// sized by the LONGEST view: a block that finds no tile of its own (shorter) view writes the empty partial without
+// staging anything.
+__global__ __launch_bounds__(256) void gallery_scan_grouped_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                                const int64_t* __restrict__ views,
+                                                                const int64_t* __restrict__ gtab,
+                                                                const int32_t* __restrict__ qmap, int F,
+                                                                float* __restrict__ ws_score, int64_t* __restrict__ ws_idx,
+                                                                const int32_t* __restrict__ seg_counts, int seg_len) {
+    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+    const int tid = threadIdx.x, g = blockIdx.y;
+    const int64_t N = gtab[2 * g + 1];
+    const int32_t* map = qmap + (int64_t)g * QG;
+    if (N <= 0 || !grouped_has_real(map, F, seg_counts, seg_len)) return;
+    const int64_t at = (int64_t)blockIdx.x * gridDim.y * QG + g * QG + tid;
+    if ((int64_t)blockIdx.x * 4 >= (N + 31) / 32) {       // no tile of this view falls to this block
+        if (tid < 32) { ws_score[at] = -INFINITY; ws_idx[at] = -1; }
+        return;
+    }
+    stage_query_group(Q, F, 0, qs, map, seg_counts, seg_len);
+    __syncthreads();
+    const BestPair b = scan_group_best<true>(G, views + gtab[2 * g], N, qs);
+    if (tid < 32) {
+        ws_score[at] = b.s;
+        ws_idx[at] = b.i;
+    }
+}
+
+// one thread per map entry; an entry that names no query slot writes nothing
+__global__ void gallery_reduce_grouped(const float* __restrict__ ws_score, const int64_t* __restrict__ ws_idx, int nblk,
+                                       int ngroups, const int64_t* __restrict__ gtab, const int32_t* __restrict__ qmap,
+                                       int F, int64_t* __restrict__ out_idx, float* __restrict__ out_score,
+                                       const int32_t* __restrict__ seg_counts, int seg_len) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ngroups * QG) return;
+    const int f = qmap[e];
+    if (f < 0 || f >= F) return;
+    float bs = -INFINITY; int64_t bi = -1;
+    if (gtab[2 * (e / QG) + 1] > 0 && (!seg_counts || slot_valid(seg_counts, seg_len, f))) {
+        for (int b = 0; b < nblk; ++b) {
+            int64_t i = ws_idx[(int64_t)b * ngroups * QG + e];
+            if (i >= 0) take_better(bs, bi, ws_score[(int64_t)b * ngroups * QG + e], i);
         }
     }
+    // reference: best_score starts at -1 and only a strictly larger score replaces it
+    if (bi < 0 || !(bs > -1.0f)) { out_idx[f] = -1; out_score[f] = -1.0f; }
+    else { out_idx[f] = bi; out_score[f] = bs; }
 }
 
 __global__ void gallery_reduce(const float* __restrict__ ws_score, const int64_t* __restrict__ ws_idx, int nblk,
@@ -145,6 +190,36 @@ extern "C" int fr_gallery_match_view_f32(const float* Q, const float* G, const i
     // Nview == 0: the scan kernel sees no tiles and the reduce writes (-1, -1)
     return gallery_match_launch("fr_gallery_match_view_f32", Q, G, Nview ? view : nullptr, F, Nview, D, 0, out_idx,
                                 out_score, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+// Grouped view scan: each query through ITS OWN view, one launch pair for a batch that mixes companies.
+extern "C" size_t fr_gallery_match_grouped_workspace(int ngroups, int64_t max_view_len) {
+    return fr_gallery_match_workspace((ngroups > 0 ? ngroups : 0) * QG, max_view_len);
+}
+
+extern "C" int fr_gallery_match_grouped_f32(const float* Q, const float* G, const int64_t* views, const int64_t* gtab,
+                                            const int32_t* qmap, int F, int ngroups, int64_t max_view_len,
+                                            int64_t capacity, int D, int64_t* out_idx, float* out_score,
+                                            void* workspace, size_t workspace_bytes, const int32_t* seg_counts,
+                                            int seg_len, fr_stream_t stream) {
+    const char* who = "fr_gallery_match_grouped_f32";
+    bool empty;
+    const int rc = grouped_args_check(who, Q, G, views, gtab, qmap, F, ngroups, max_view_len, capacity, D, out_idx,
+                                      out_score, workspace, workspace_bytes,
+                                      fr_gallery_match_grouped_workspace(ngroups, max_view_len), seg_counts, seg_len, &empty);
+    if (rc != FR_OK || empty) return rc;
+    const int nblk = scan_blocks(max_view_len), FS = ngroups * QG;
+    float* ws_score = reinterpret_cast<float*>(workspace);
+    size_t off = ((size_t)nblk * FS * sizeof(float) + 255) & ~(size_t)255;
+    int64_t* ws_idx = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + off);
+    hipStream_t s = fr_stream(stream);
+    gallery_scan_grouped_f32<<<dim3(nblk, ngroups), 256, 0, s>>>(Q, G, views, gtab, qmap, F, ws_score, ws_idx,
+                                                                  seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_scan_grouped_f32");
+    gallery_reduce_grouped<<<fr_cdiv(FS, 64), 64, 0, s>>>(ws_score, ws_idx, nblk, ngroups, gtab, qmap, F, out_idx,
+                                                          out_score, seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_reduce_grouped");
+    return FR_OK;
 }
 
 // ---------------------------------------------------------------- in-place gallery row update

@@ -32,12 +32,57 @@ static inline int scan_blocks(int64_t N) {
     return (int)b;
 }
 
-// stage query group [q0, q0 + QG) of Q [F][GD] into qs [QG][QPAD] (zero rows beyond F); 256 threads, no barrier
-__device__ __forceinline__ void stage_query_group(const float* __restrict__ Q, int F, int q0, float* qs) {
+// the query slot that lane r of a grouped scan's group owns (qmap: the group's QG entries), or -1: unmapped, outside
+// [0, F), or padding under seg_counts.  The one test of the grouped scans' staging, early exit and reduce.
+__device__ __forceinline__ int grouped_slot(const int32_t* __restrict__ qmap, int r, int F,
+                                            const int32_t* seg_counts, int seg_len) {
+    const int f = qmap[r];
+    if (f < 0 || f >= F) return -1;
+    if (seg_counts && !slot_valid(seg_counts, seg_len, f)) return -1;
+    return f;
+}
+
+// a grouped scan's group (map: its QG entries) owns at least one real query slot; the same answer in every thread
+__device__ __forceinline__ bool grouped_has_real(const int32_t* __restrict__ map, int F, const int32_t* seg_counts,
+                                                 int seg_len) {
+    for (int r = 0; r < QG; ++r)
+        if (grouped_slot(map, r, F, seg_counts, seg_len) >= 0) return true;
+    return false;
+}
+
+// The argument checks the grouped entries (fr_gallery_match_grouped_f32, fr_gallery_topk_grouped_f32) share, all
+// before any launch.  FR_OK with *empty = true: nothing to do.
+static inline int grouped_args_check(const char* who, const void* Q, const void* G, const void* views, const void* gtab,
+                                     const void* qmap, int F, int ngroups, int64_t max_view_len, int64_t capacity, int D,
+                                     const void* out_idx, const void* out_score, const void* workspace,
+                                     size_t workspace_bytes, size_t need, const int32_t* seg_counts, int seg_len,
+                                     bool* empty) {
+    *empty = true;
+    FR_REQUIRE(!seg_counts || (seg_len > 0 && F % seg_len == 0), "%s: seg_len must divide F", who);
+    FR_REQUIRE(D == GD, "%s: D must be %d (got %d)", who, GD, D);
+    FR_REQUIRE(F >= 0 && ngroups >= 0 && max_view_len >= 0, "%s: negative size", who);
+    FR_REQUIRE(capacity >= 0 && capacity < (1ll << 31), "%s: capacity %lld must be below 2^31 slots", who,
+               (long long)capacity);
+    FR_REQUIRE(max_view_len < (1ll << 31), "%s: max_view_len %lld must be below 2^31 rows", who, (long long)max_view_len);
+    FR_REQUIRE(ngroups <= 65535, "%s: at most 65535 groups (got %d)", who, ngroups);
+    if (F == 0 || ngroups == 0) return FR_OK;
+    FR_REQUIRE(Q && G && views && gtab && qmap && out_idx && out_score, "%s: null pointer", who);
+    FR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+    *empty = false;
+    return FR_OK;
+}
+
+// stage query group [q0, q0 + QG) of Q [F][GD] into qs [QG][QPAD] (zero rows beyond F); 256 threads, no barrier.
+// map (optional, the grouped scans): row r is query slot map[r] instead of q0 + r, gathered from anywhere in Q; rows
+// whose grouped_slot is -1 are staged as zero rows and never read from Q.
+__device__ __forceinline__ void stage_query_group(const float* __restrict__ Q, int F, int q0, float* qs,
+                                                  const int32_t* __restrict__ map = nullptr,
+                                                  const int32_t* seg_counts = nullptr, int seg_len = 0) {
     for (int e = threadIdx.x; e < QG * (GD / 4); e += 256) {
         int r = e / (GD / 4), c = e % (GD / 4);
+        const int f = map ? grouped_slot(map, r, F, seg_counts, seg_len) : q0 + r;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q0 + r < F) v = *reinterpret_cast<const float4*>(Q + (int64_t)(q0 + r) * GD + c * 4);
+        if (map ? f >= 0 : f < F) v = *reinterpret_cast<const float4*>(Q + (int64_t)f * GD + c * 4);
         *reinterpret_cast<float4*>(&qs[r * QPAD + c * 4]) = v;
     }
 }

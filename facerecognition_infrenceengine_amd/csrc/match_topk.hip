@@ -8,20 +8,13 @@
 #include "match_scan.h"
 #include "topk_list.h"
 
-// Same orientation and arithmetic as gallery_scan_f32: a lane owns ONE query and 16 rows of a tile, its list is
-// lane-local inside the scan.  Partial lists go to ws_score / ws_idx [gridDim.x][F][K].
+// Same orientation and arithmetic as scan_group_best (match.hip): a lane owns ONE query and 16 rows of a tile, its list
+// is lane-local inside the scan.  The whole block calls it (barriers inside) after the barrier that ends the staging of
+// qs; VIEW as there.  On return threads 0 .. 31 hold the block's list of query lane tid; qs is overwritten.
 template <bool VIEW, int KP>
-__global__ __launch_bounds__(256) void gallery_scan_topk_f32(const float* __restrict__ Q, const float* __restrict__ G,
-                                                             const int64_t* __restrict__ view, int F, int64_t N, int K,
-                                                             float* __restrict__ ws_score, int64_t* __restrict__ ws_idx,
-                                                             const int32_t* __restrict__ seg_counts, int seg_len) {
-    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+__device__ __forceinline__ TopK<KP> scan_group_topk(const float* __restrict__ G, const int64_t* __restrict__ view,
+                                                    int64_t N, float* qs) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int q0 = blockIdx.y * QG;
-    // a group made of padding only does no work (the reduce reports empty lists for every padding slot)
-    if (seg_counts && !group_has_valid(seg_counts, seg_len, q0, min(q0 + QG, F))) return;
-    stage_query_group(Q, F, q0, qs);
-    __syncthreads();
     const int r = lane & 31, h = lane >> 5;
     TopK<KP> top;
     top.clear();
@@ -50,9 +43,92 @@ __global__ __launch_bounds__(256) void gallery_scan_topk_f32(const float* __rest
             o.load(ls + (w * 32 + tid) * KP, li + (w * 32 + tid) * KP, KP);
             top.merge(o);
         }
-        if (q0 + tid < F) {
-            const int64_t at = ((int64_t)blockIdx.x * F + q0 + tid) * K;
-            top.store(ws_score + at, ws_idx + at, K);
+    }
+    return top;
+}
+
+// Partial lists go to ws_score / ws_idx [gridDim.x][F][K].
+template <bool VIEW, int KP>
+__global__ __launch_bounds__(256) void gallery_scan_topk_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                             const int64_t* __restrict__ view, int F, int64_t N, int K,
+                                                             float* __restrict__ ws_score, int64_t* __restrict__ ws_idx,
+                                                             const int32_t* __restrict__ seg_counts, int seg_len) {
+    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+    const int tid = threadIdx.x;
+    const int q0 = blockIdx.y * QG;
+    // a group made of padding only does no work (the reduce reports empty lists for every padding slot)
+    if (seg_counts && !group_has_valid(seg_counts, seg_len, q0, min(q0 + QG, F))) return;
+    stage_query_group(Q, F, q0, qs);
+    __syncthreads();
+    TopK<KP> top = scan_group_topk<VIEW, KP>(G, view, N, qs);
+    if (tid < 32 && q0 + tid < F) {
+        const int64_t at = ((int64_t)blockIdx.x * F + q0 + tid) * K;
+        top.store(ws_score + at, ws_idx + at, K);
+    }
+}
+
+// GROUPED (see gallery_scan_grouped_f32, match.hip): block (x, g) scans the query slots qmap[g * QG ..] names through
+// view views[gtab[2g] .. + gtab[2g + 1]); partial lists go to ws [gridDim.x][ngroups * QG][K], entry g * QG + lane.
+template <int KP>
+__global__ __launch_bounds__(256) void gallery_scan_topk_grouped_f32(const float* __restrict__ Q, const float* __restrict__ G,
+                                                                     const int64_t* __restrict__ views,
+                                                                     const int64_t* __restrict__ gtab,
+                                                                     const int32_t* __restrict__ qmap, int F,
+                                                                     int K, float* __restrict__ ws_score,
+                                                                     int64_t* __restrict__ ws_idx,
+                                                                     const int32_t* __restrict__ seg_counts, int seg_len) {
+    __shared__ __attribute__((aligned(16))) float qs[QG * QPAD];
+    const int tid = threadIdx.x, g = blockIdx.y;
+    const int64_t N = gtab[2 * g + 1];
+    const int32_t* map = qmap + (int64_t)g * QG;
+    if (N <= 0 || !grouped_has_real(map, F, seg_counts, seg_len)) return;
+    const int64_t at = ((int64_t)blockIdx.x * gridDim.y * QG + g * QG + tid) * K;
+    TopK<KP> top;
+    if ((int64_t)blockIdx.x * 4 >= (N + 31) / 32) {       // no tile of this view falls to this block: empty lists, no staging
+        top.clear();
+        if (tid < 32) top.store(ws_score + at, ws_idx + at, K);
+        return;
+    }
+    stage_query_group(Q, F, 0, qs, map, seg_counts, seg_len);
+    __syncthreads();
+    top = scan_group_topk<true, KP>(G, views + gtab[2 * g], N, qs);
+    if (tid < 32) top.store(ws_score + at, ws_idx + at, K);
+}
+
+// One wave per map entry: gallery_topk_reduce over ws [nblk][ngroups * QG][K], the list written to the query slot the
+// entry names; an entry that names none writes nothing.  Empty view or padding slot: (-1, -1.0) everywhere.
+template <int KP>
+__global__ __launch_bounds__(256) void gallery_topk_reduce_grouped(const float* __restrict__ ws_score,
+                                                                   const int64_t* __restrict__ ws_idx, int nblk,
+                                                                   int ngroups, const int64_t* __restrict__ gtab,
+                                                                   const int32_t* __restrict__ qmap, int F, int K,
+                                                                   int64_t* __restrict__ out_idx,
+                                                                   float* __restrict__ out_score,
+                                                                   const int32_t* __restrict__ seg_counts, int seg_len) {
+    const int e = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (e >= ngroups * QG) return;
+    const int f = qmap[e];
+    if (f < 0 || f >= F) return;
+    TopK<KP> top;
+    top.clear();
+    if (gtab[2 * (e / QG) + 1] > 0 && (!seg_counts || slot_valid(seg_counts, seg_len, f))) {
+        for (int b = lane; b < nblk; b += 64) {
+            TopK<KP> o;
+            const int64_t at = ((int64_t)b * ngroups * QG + e) * K;
+            o.load(ws_score + at, ws_idx + at, K);
+            top.merge(o);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) top.merge(top.shfl_xor(m));
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            if (j < K) {
+                const bool has = top.i[j] >= 0 && top.s[j] > -1.0f;
+                out_idx[(int64_t)f * K + j] = has ? top.i[j] : -1;
+                out_score[(int64_t)f * K + j] = has ? top.s[j] : -1.0f;
+            }
         }
     }
 }
@@ -189,6 +265,51 @@ extern "C" int fr_gallery_topk_view_f32(const float* Q, const float* G, const in
     // Nview == 0: the scan kernel sees no tiles and the reduce writes (-1, -1.0) everywhere
     return gallery_topk_launch("fr_gallery_topk_view_f32", Q, G, Nview ? view : nullptr, F, Nview, D, K, 0, out_idx,
                                out_score, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+extern "C" size_t fr_gallery_topk_grouped_workspace(int ngroups, int64_t max_view_len, int K) {
+    return fr_gallery_topk_workspace((ngroups > 0 ? ngroups : 0) * QG, max_view_len, K);
+}
+
+template <int KP>
+static int gallery_topk_grouped_launch_kp(const float* Q, const float* G, const int64_t* views, const int64_t* gtab,
+                                          const int32_t* qmap, int F, int ngroups, int nblk, int K,
+                                          int64_t* out_idx, float* out_score, float* ws_score, int64_t* ws_idx,
+                                          const int32_t* seg_counts, int seg_len, hipStream_t s) {
+    gallery_scan_topk_grouped_f32<KP><<<dim3(nblk, ngroups), 256, 0, s>>>(Q, G, views, gtab, qmap, F, K, ws_score,
+                                                                           ws_idx, seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_scan_topk_grouped_f32");
+    gallery_topk_reduce_grouped<KP><<<fr_cdiv(ngroups * QG, 4), 256, 0, s>>>(ws_score, ws_idx, nblk, ngroups, gtab, qmap, F, K,
+                                                                              out_idx, out_score, seg_counts, seg_len);
+    FR_CHECK_LAUNCH("gallery_topk_reduce_grouped");
+    return FR_OK;
+}
+
+// Grouped view top-K: each query through ITS OWN view (fr_gallery_match_grouped_f32's tables, match.hip).
+extern "C" int fr_gallery_topk_grouped_f32(const float* Q, const float* G, const int64_t* views, const int64_t* gtab,
+                                           const int32_t* qmap, int F, int ngroups, int64_t max_view_len,
+                                           int64_t capacity, int D, int K, int64_t* out_idx, float* out_score,
+                                           void* workspace, size_t workspace_bytes, const int32_t* seg_counts,
+                                           int seg_len, fr_stream_t stream) {
+    const char* who = "fr_gallery_topk_grouped_f32";
+    FR_REQUIRE(K >= 1 && K <= FR_TOPK_MAX, "%s: K must be 1..%d (got %d)", who, FR_TOPK_MAX, K);
+    bool empty;
+    const int rc = grouped_args_check(who, Q, G, views, gtab, qmap, F, ngroups, max_view_len, capacity, D, out_idx,
+                                      out_score, workspace, workspace_bytes,
+                                      fr_gallery_topk_grouped_workspace(ngroups, max_view_len, K), seg_counts, seg_len,
+                                      &empty);
+    if (rc != FR_OK || empty) return rc;
+    const int nblk = scan_blocks(max_view_len);
+    float* ws_score = reinterpret_cast<float*>(workspace);
+    int64_t* ws_idx = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) +
+                                                 topk_score_bytes(ngroups * QG, max_view_len, K));
+    hipStream_t s = fr_stream(stream);
+    switch (topk_kp(K)) {
+        case 2: return gallery_topk_grouped_launch_kp<2>(Q, G, views, gtab, qmap, F, ngroups, nblk, K, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        case 4: return gallery_topk_grouped_launch_kp<4>(Q, G, views, gtab, qmap, F, ngroups, nblk, K, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        case 8: return gallery_topk_grouped_launch_kp<8>(Q, G, views, gtab, qmap, F, ngroups, nblk, K, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+        default: return gallery_topk_grouped_launch_kp<16>(Q, G, views, gtab, qmap, F, ngroups, nblk, K, out_idx, out_score, ws_score, ws_idx, seg_counts, seg_len, s);
+    }
 }
 
 // fr_gallery_topk_view_f32 for the queries a mask names: query f is scanned iff mask[f] > 0 (the padding rule of the

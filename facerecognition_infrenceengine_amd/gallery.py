@@ -358,6 +358,11 @@ class DeviceGallery:
         """View over the given ids, in the given order (ids not in the gallery are skipped)."""
         return GalleryView(self, [i for i in ids if i in self.slot_of])
 
+    def view_set(self, views):
+        """The given views of THIS gallery, all of its current generation, as one ``GalleryViewSet``: a batch whose
+        queries belong to different views is then matched in one grouped scan."""
+        return GalleryViewSet(views, gallery=self)
+
 
 class GalleryView:
     """Ordered subset of a ``DeviceGallery``: the rows one company's frames are matched against."""
@@ -425,3 +430,152 @@ class GalleryView:
     decide_device = GalleryMatcher.decide_device
     match = GalleryMatcher.match
     match_topk = GalleryMatcher.match_topk
+
+
+GROUP = 32                     # queries per scan group (csrc/match_scan.h QG)
+
+
+def build_group_tables(view_of, F, seg_len, offsets, lengths):
+    """The host side of the grouped scan's tables (include/frhip.h fr_gallery_match_grouped_f32), a pure function.
+
+    ``view_of``: the view index of every query slot (``seg_len`` == 0: F entries) or of every segment of ``seg_len``
+    slots (F / seg_len entries); None or -1: no view - such slots are grouped under an empty view and report
+    (-1, -1.0).  ``offsets`` / ``lengths``: where each view's slot list starts in the concatenated list, and its length.
+    The slots of one view are packed, in slot order, into groups of at most 32; every slot lands in exactly one group
+    and a group never mixes views.  Returns (gtab int64 [ngroups,2], qmap int32 [ngroups*32], max_view_len)."""
+    F, seg_len = int(F), int(seg_len)
+    vo = np.asarray([-1 if v is None else int(v) for v in view_of], np.int64).reshape(-1)
+    if seg_len > 0:
+        if F % seg_len or len(vo) * seg_len != F:
+            raise ValueError(f"view_of needs one entry per segment: F {F} seg_len {seg_len} entries {len(vo)}")
+        vo = np.repeat(vo, seg_len)
+    elif len(vo) != F:
+        raise ValueError(f"view_of needs one entry per query: F {F} entries {len(vo)}")
+    if len(vo) and (vo.min() < -1 or vo.max() >= len(lengths)):
+        raise ValueError(f"view_of names a view outside 0..{len(lengths) - 1}")
+    gtab, qmap, longest = [], [], 0
+    for v in np.unique(vo):
+        slots = np.nonzero(vo == v)[0]
+        off, n = (0, 0) if v < 0 else (int(offsets[v]), int(lengths[v]))
+        for a in range(0, len(slots), GROUP):
+            part = slots[a:a + GROUP]
+            gtab.append((off, n))
+            qmap.append(np.concatenate([part, np.full(GROUP - len(part), -1, np.int64)]))
+        longest = max(longest, n)
+    gtab = np.asarray(gtab, np.int64).reshape(-1, 2)
+    qmap = (np.concatenate(qmap) if qmap else np.zeros(0, np.int64)).astype(np.int32)
+    return gtab, qmap, longest
+
+
+class GalleryViewSet:
+    """Several views of ONE ``DeviceGallery`` generation, matched together: each query of a batch through its own view,
+    in one grouped scan (fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32) - the frames of a camera batch
+    that belong to different companies.  The concatenated slot lists are uploaded once, here.
+
+    The grouped scan is the EXACT f32 scan over the f32 slab, also on a gallery built with scan="f16" / "f8" (there is
+    no grouped coarse scan): the ids are those the coarse view scan promises - the f32 scan's - and the scores are
+    the exact scan's bits; ``last_topk()`` reports "exact"."""
+
+    _CACHE = 64                # (view_of, F, seg_len) table sets kept: a few hundred bytes each
+
+    def __init__(self, views, gallery=None):
+        views = list(views)
+        if gallery is None:
+            if not views:
+                raise ValueError("GalleryViewSet needs a gallery or at least one view")
+            gallery = views[0].gallery
+        if any(v.gallery is not gallery for v in views):
+            raise ValueError("the views of a GalleryViewSet must belong to one gallery")
+        if any(v.generation != gallery.generation for v in views):
+            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
+        self.gallery, self.views, self.generation = gallery, views, gallery.generation
+        self.lib, self.device = gallery.lib, gallery.device
+        self.lengths = [len(v) for v in views]
+        self.offsets = [int(x) for x in np.concatenate([[0], np.cumsum(self.lengths)])[:-1]]
+        slots = [gallery.slot_of[i] for v in views for i in v.ids]
+        self.slots = torch.tensor(slots + [0], dtype=torch.int64).to(self.device)     # never empty: a pointer to pass
+        self._tables, self._tables_lock = {}, threading.Lock()     # one set serves the camera loop and request threads
+
+    def __len__(self):
+        return len(self.views)
+
+    def tables(self, view_of, F, seg_len=0):
+        """(gtab, qmap: device tensors, ngroups, max_view_len) for this assignment of views; built once per
+        (view_of, F, seg_len) and kept - the last ``_CACHE`` assignments, oldest dropped first.  A miss builds the tables
+        on the host and uploads the two small arrays (blocking copies); a hit costs a dict lookup.  A camera set whose
+        cameras all deliver sends one assignment turn after turn; a turn in which some are late sends another, a subset
+        of the same cameras - those settle in the cache too."""
+        key = (tuple(-1 if v is None else int(v) for v in view_of), int(F), int(seg_len))
+        with self._tables_lock:
+            hit = self._tables.get(key)
+            if hit is None:
+                gtab, qmap, longest = build_group_tables(key[0], F, seg_len, self.offsets, self.lengths)
+                while len(self._tables) >= self._CACHE:
+                    self._tables.pop(next(iter(self._tables)))
+                hit = self._tables[key] = (torch.from_numpy(gtab).to(self.device), torch.from_numpy(qmap).to(self.device),
+                                           gtab.shape[0], longest)
+        return hit
+
+    def _prepare(self, Q, view_of, renormalise, counts, seg_len):
+        if self.generation != self.gallery.generation:
+            raise StaleViewError("GalleryViewSet is stale: the gallery's membership changed after the set was made")
+        Q = Q.to(self.device, torch.float32).contiguous().reshape(-1, DIM)
+        F = Q.shape[0]
+        if counts is not None:
+            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
+        tabs = self.tables(view_of, F, seg_len)
+        if renormalise and F:
+            Qn = torch.empty_like(Q)
+            with torch.cuda.device(self.device):
+                self.lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, _lib.stream_ptr())
+            Q = Qn
+        return Q, F, tabs
+
+    def match_device(self, Q, view_of, renormalise=True, counts=None, seg_len=0):
+        """Q: float32 [F,512] device tensor; ``view_of``: a host sequence naming the view (index into ``self.views``;
+        None: no view) of every query, or of every segment of ``seg_len`` slots when ``seg_len`` > 0 (frame -> company).
+        Returns device tensors (idx int64[F], score float32[F]): for every query what ``views[v].match_device`` of an
+        f32 gallery returns for it - idx is the position in ITS view's ``ids`` - bit for bit; (-1, -1.0) for an
+        empty or missing view.  ``counts`` (device int32 [F / seg_len]) marks padding slots as in
+        ``GalleryMatcher.match_device``.  One fr_l2norm_rows_f32 launch (``renormalise``) plus the grouped entry, and
+        nothing is read back from ``counts``; no host synchronisation once the tables of this ``view_of`` are cached
+        (``tables``: the first call with a new assignment uploads them).  Always the exact f32 scan (see the class)."""
+        Q, F, (gtab, qmap, ngroups, longest) = self._prepare(Q, view_of, renormalise, counts, seg_len)
+        idx = torch.empty(F, dtype=torch.int64, device=self.device)
+        score = torch.empty(F, dtype=torch.float32, device=self.device)
+        if F == 0:
+            return idx, score
+        g = self.gallery
+        with torch.cuda.device(self.device):
+            ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_match_grouped_workspace(ngroups, longest))
+            self.lib.fr_gallery_match_grouped_f32(_lib.ptr(Q), _lib.ptr(g.G), _lib.ptr(self.slots), _lib.ptr(gtab),
+                                                  _lib.ptr(qmap), F, ngroups, longest, g.capacity, DIM, _lib.ptr(idx),
+                                                  _lib.ptr(score), _lib.ptr(ws), ws.numel(),
+                                                  _lib.ptr(counts) if counts is not None else None, seg_len,
+                                                  _lib.stream_ptr())
+        return idx, score
+
+    def match_topk_device(self, Q, view_of, k, renormalise=True, counts=None, seg_len=0):
+        """The ``k`` best rows of every query in ITS view: (idx int64[F,k], score float32[F,k]), per query what
+        ``views[v].match_topk_device`` returns, bit for bit; column 0 is ``match_device``.  Arguments as
+        ``match_device``.  Always the exact f32 scan: ``last_topk()`` reports "exact"."""
+        k = _check_k(k)
+        Q, F, (gtab, qmap, ngroups, longest) = self._prepare(Q, view_of, renormalise, counts, seg_len)
+        idx = torch.empty((F, k), dtype=torch.int64, device=self.device)
+        score = torch.empty((F, k), dtype=torch.float32, device=self.device)
+        _TLS.topk = {"path": "exact", "flags": None}
+        if F == 0:
+            return idx, score
+        g = self.gallery
+        with torch.cuda.device(self.device):
+            ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_topk_grouped_workspace(ngroups, longest, k))
+            self.lib.fr_gallery_topk_grouped_f32(_lib.ptr(Q), _lib.ptr(g.G), _lib.ptr(self.slots), _lib.ptr(gtab),
+                                                 _lib.ptr(qmap), F, ngroups, longest, g.capacity, DIM, k, _lib.ptr(idx),
+                                                 _lib.ptr(score), _lib.ptr(ws), ws.numel(),
+                                                 _lib.ptr(counts) if counts is not None else None, seg_len,
+                                                 _lib.stream_ptr())
+        return idx, score
+
+    last_topk = property(lambda self: last_topk())
+
+    decide_device = GalleryMatcher.decide_device

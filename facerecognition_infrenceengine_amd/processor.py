@@ -215,12 +215,42 @@ class EmbeddingManager:
         copied per company, and a sync rewrites only the rows whose documents changed."""
         with self.embeddings_lock:
             self._flush_to_device()
-            hit = self._matchers.get(company_id)
-            if hit is None or hit[0].generation != self._gallery.generation:
-                ids = self._company_rows(company_id) if company_id is not None else list(self.embeddings)
-                hit = (self._gallery.view(ids), {i: self.employee_metadata[i] for i in ids})
-                self._matchers[company_id] = hit
-            return hit
+            return self._matcher_locked(company_id)
+
+    def _matcher_locked(self, company_id):
+        """The cached (view, metadata) of one company, rebuilt when the slab's membership moved on.  Under the lock,
+        after ``_flush_to_device``."""
+        hit = self._matchers.get(company_id)
+        if hit is None or hit[0].generation != self._gallery.generation:
+            ids = self._company_rows(company_id) if company_id is not None else list(self.embeddings)
+            hit = (self._gallery.view(ids), {i: self.employee_metadata[i] for i in ids})
+            self._matchers[company_id] = hit
+        return hit
+
+    def get_matchers_for_companies(self, company_ids):
+        """(view_set, metadatas, index_of) for a batch whose entries belong to the given companies (one id per entry):
+        the views of the DISTINCT companies that have rows, each once, as one ``GalleryViewSet`` over one generation of
+        the slab (one lock, one flush); ``metadatas[v]`` goes with ``view_set.views[v]``, and ``index_of[i]`` names the
+        view of ``company_ids[i]`` - None where that company has no rows.  Views and sets come from the cache
+        ``get_matcher_for_company`` fills (a set per mix of companies, the last 16; a new mix uploads its slot lists)."""
+        with self.embeddings_lock:
+            self._flush_to_device()
+            where, names, views, metadatas = {}, [], [], []
+            for c in company_ids:
+                if c not in where:
+                    view, metadata = self._matcher_locked(c)
+                    where[c] = len(views) if len(view) else None
+                    if len(view):
+                        names.append(c); views.append(view); metadatas.append(metadata)
+            key = ("view_set",) + tuple(names)
+            hit = self._matchers.get(key)
+            if hit is None or hit[0].generation != self._gallery.generation or \
+                    any(a is not b for a, b in zip(hit[0].views, views)):
+                sets = [k for k in self._matchers if isinstance(k, tuple)]
+                for k in sets[:max(len(sets) - 15, 0)]:          # the company mix of a turn varies with the cameras
+                    del self._matchers[k]                        # that deliver: keep the last 16 mixes
+                hit = self._matchers[key] = (self._gallery.view_set(views), metadatas)
+            return hit[0], hit[1], [where[c] for c in company_ids]
 
     def get_stats(self):
         """infrenceServer.py:386-398."""
@@ -265,13 +295,7 @@ class FaceRecognitionProcessor:
         det = r["det_score"].cpu().numpy()
         out = []
         for f in range(len(idx)):
-            if dec[f] == 1:
-                pid = matcher.ids[idx[f]]
-                out.append({"bbox": bbox[f], "person_id": pid, "person_info": metadata[pid],
-                            "det_score": float(det[f]), "recognition_score": score[f]})
-            else:
-                out.append({"bbox": bbox[f], "person_id": None, "person_info": {"name": "Unknown", "type": "unknown"},
-                            "det_score": float(det[f]), "recognition_score": 0})
+            out.append(_face_result(bbox[f], det[f], dec[f], idx[f], score[f], matcher.ids, metadata))
         return out
 
     def identify(self, frame, company_id, k=5, min_score=None):
@@ -296,13 +320,7 @@ class FaceRecognitionProcessor:
         det = r["det_score"].cpu().numpy()
         out = []
         for f in range(len(idx)):
-            cands = []
-            for i, s in zip(idx[f], score[f]):
-                if i < 0 or (min_score is not None and s < min_score):
-                    break                                     # ranked: everything behind is empty or lower
-                pid = matcher.ids[i]
-                cands.append({"person_id": pid, "person_info": metadata[pid], "score": s})
-            out.append({"bbox": bbox[f], "det_score": float(det[f]), "candidates": cands})
+            out.append(_face_candidates(bbox[f], det[f], idx[f], score[f], matcher.ids, metadata, min_score))
         return out
 
     @property
@@ -313,13 +331,102 @@ class FaceRecognitionProcessor:
             self.initialize_detector()
         return getattr(self.face_detector, "det_size", None) is not None
 
+    def _scan_mixed(self, frames, company_ids, k=None):
+        """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
+        ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
+        no company has a gallery (nothing is run), else (n, slot results, view_set, metadatas, index_of, idx, score);
+        device tensors, no synchronisation beyond the engine's own."""
+        from .gallery import StaleViewError
+        company_ids = list(company_ids)
+        if len(company_ids) != len(frames):
+            raise ValueError(f"one company id per frame: {len(frames)} frames, {len(company_ids)} ids")
+        if self.face_detector is None:
+            self.initialize_detector()
+        mgr = self.embedding_manager
+        view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
+        for c in sorted({str(c) for c, v in zip(company_ids, index_of) if v is None}):
+            logger.warning("No embeddings found for company %s", c)
+        if all(v is None for v in index_of):
+            return None
+        n, r = _detect_embed_batch(self, self.face_detector, frames)
+        cap = r["bbox"].shape[1]
+
+        def scan(vs, of):
+            if k is None:
+                return vs.match_device(r["normed_embedding"], of, counts=r["counts"], seg_len=cap)
+            return vs.match_topk_device(r["normed_embedding"], of, k, counts=r["counts"], seg_len=cap)
+        try:
+            idx, score = scan(view_set, index_of)
+        except StaleViewError:                    # a sync moved the slab on meanwhile: the current views, once
+            view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
+            idx, score = scan(view_set, index_of)
+        return n, r, view_set, metadatas, index_of, idx, score
+
+    def _recognize_batch_mixed(self, frames, company_ids):
+        got = self._scan_mixed(frames, company_ids)
+        if got is None:
+            return [None] * len(frames)
+        n, r, view_set, metadatas, index_of, idx, score = got
+        dec = view_set.decide_device(idx, score, self.recognition_threshold)
+        cap = r["bbox"].shape[1]
+        counts = r["counts"].cpu().numpy()                                   # the one synchronisation
+        idx, score, dec = (t.cpu().numpy().reshape(n, cap) for t in (idx, score, dec))
+        bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
+        dscore = r["det_score"].cpu().numpy()
+        out = []
+        for f in range(n):
+            if index_of[f] is None:
+                out.append(None)
+                continue
+            ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
+            out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], ids, metadata)
+                        for j in range(int(counts[f]))])
+        return out
+
+    def identify_batch(self, frames, company_id, k=5, min_score=None):
+        """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
+        list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
+        through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
+        returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
+        whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path."""
+        if not 1 <= int(k) <= 16:
+            raise ValueError(f"k must be 1..16 (got {k})")
+        ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
+        got = self._scan_mixed(frames, ids, k=int(k))
+        if got is None:
+            return [None] * len(frames)
+        n, r, view_set, metadatas, index_of, idx, score = got
+        cap = r["bbox"].shape[1]
+        counts = r["counts"].cpu().numpy()                                   # the one synchronisation
+        idx, score = idx.cpu().numpy().reshape(n, cap, -1), score.cpu().numpy().reshape(n, cap, -1)
+        bbox = r["bbox"].cpu().numpy().astype(int)
+        dscore = r["det_score"].cpu().numpy()
+        out = []
+        for f in range(n):
+            if index_of[f] is None:
+                out.append(None)
+                continue
+            pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
+            out.append([_face_candidates(bbox[f, j], dscore[f, j], idx[f, j], score[f, j], pids, metadata, min_score)
+                        for j in range(int(counts[f]))])
+        return out
+
     def recognize_batch(self, frames, company_id):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
         copy stream -> detect -> align -> embed -> company view scan -> decision), one host synchronisation at the
         end.  Returns a list (per frame) of lists of the dicts ``recognize`` returns, or None when the company has
-        no gallery (the reference returns the frame untouched then, infrenceServer.py:523-525)."""
+        no gallery (the reference returns the frame untouched then, infrenceServer.py:523-525).
+
+        ``company_id`` may also be a list or tuple with one id per frame - cameras of several companies in one batch
+        (the reference runs one process per camera, each with its own company: infrenceServer.py:603-646).  Still ONE
+        engine pass, then one grouped scan in which every frame is matched through its own company's view, one
+        decision launch and the one synchronisation.  The result is then always a list: None stands in for the frames
+        whose company has no gallery, the other frames are served.  The grouped scan is the exact f32 scan, also when
+        the manager was built with scan="f16" / "f8": the same ids, the exact scan's score bits."""
+        if isinstance(company_id, (list, tuple)):
+            return self._recognize_batch_mixed(frames, company_id)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
@@ -337,17 +444,8 @@ class FaceRecognitionProcessor:
         dscore = r["det_score"].cpu().numpy()
         out = []
         for f in range(n):
-            faces = []
-            for j in range(int(counts[f])):
-                if dec[f, j] == 1:
-                    pid = matcher.ids[idx[f, j]]
-                    faces.append({"bbox": bbox[f, j], "person_id": pid, "person_info": metadata[pid],
-                                  "det_score": float(dscore[f, j]), "recognition_score": score[f, j]})
-                else:
-                    faces.append({"bbox": bbox[f, j], "person_id": None,
-                                  "person_info": {"name": "Unknown", "type": "unknown"},
-                                  "det_score": float(dscore[f, j]), "recognition_score": 0})
-            out.append(faces)
+            out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], matcher.ids, metadata)
+                        for j in range(int(counts[f]))])
         return out
 
     def annotate(self, frame, results):
@@ -549,6 +647,27 @@ class CameraProcessor:
         except Exception as e:
             logger.error("Error in face detection: %s", e)
         return stats
+
+
+def _face_result(bbox, det_score, decision, row, score, ids, metadata):
+    """One face of ``recognize`` / ``recognize_batch``: ``row`` is the position in ``ids`` the scan chose, ``decision`` what
+    fr_match_decide made of its score (1: recognised; infrenceServer.py:545-552)."""
+    if decision == 1:
+        pid = ids[row]
+        return {"bbox": bbox, "person_id": pid, "person_info": metadata[pid], "det_score": float(det_score),
+                "recognition_score": score}
+    return {"bbox": bbox, "person_id": None, "person_info": {"name": "Unknown", "type": "unknown"},
+            "det_score": float(det_score), "recognition_score": 0}
+
+
+def _face_candidates(bbox, det_score, rows, scores, ids, metadata, min_score):
+    """One face of ``identify`` / ``identify_batch``: its ranked rows (positions in ``ids``) and scores as candidates."""
+    cands = []
+    for i, s in zip(rows, scores):
+        if i < 0 or (min_score is not None and s < min_score):
+            break                                             # ranked: everything behind is empty or lower
+        cands.append({"person_id": ids[i], "person_info": metadata[ids[i]], "score": s})
+    return {"bbox": bbox, "det_score": float(det_score), "candidates": cands}
 
 
 def _detect_embed(detector, frame):

@@ -40,7 +40,8 @@ typedef void* fr_stream_t;
  * without them by the missing symbol.  The same holds for fr_dw_conv_f16 and fr_det_conv_act_f16 (depthwise layers and the
  * PReLU epilogue of the plan recogniser, mbf.py), added under 106 later, and for fr_unknown_assign_batch_f32,
  * fr_gallery_first_above_blocked_f32 and fr_enrol_batch_f32 / fr_enrol_batch_workspace (the counting and enrolment paths in
- * batches), added under 106 after those.  fr_version() returns the value the library was built
+ * batches), added under 106 after those, and for fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32 with their
+ * _workspace functions (the grouped view scan of mixed-company batches).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -177,6 +178,38 @@ int fr_gallery_topk_view_masked_f32(const float* Q, const float* G, const int64_
                                     int K, int64_t* out_idx, float* out_score, void* workspace,
                                     size_t workspace_bytes, const int32_t* mask, fr_stream_t stream);
 int fr_gallery_gmax_update(const float* G, const int64_t* slots, int64_t n, int D, float* gmax, fr_stream_t stream);
+/* Grouped view scan: every query through ITS OWN view of the slab G [capacity,512], in one launch pair - a batch whose
+ * frames belong to different companies.  The exact f32 scan only: on a slab that also keeps a coarse copy these
+ * entries still read G.
+ *   Q       f32 [F][512]: ALL query slots in slot order, neither permuted nor compacted.
+ *   views   int64 [V]: the slot lists of the distinct views, concatenated (V >= 1 elements allocated).
+ *   gtab    int64 [ngroups][2]: per query group (offset into views, view length).  Several groups may name one view.
+ *   qmap    int32 [ngroups * 32]: the query slot that lane r of group g owns (entry g * 32 + r), or -1.  A slot should
+ *           appear in at most one entry.
+ *   max_view_len: the longest view length in gtab; it sizes the grid and the workspace only - the rows of a longer
+ *           view are still all scanned (the tile loop strides over the grid).
+ *   capacity: slots of G, < 2^31 (refused with FR_E_INVALID beyond, as the coarse view entries refuse it).  Every
+ *           views[] entry must lie in [0, capacity); they, and the offsets and lengths in gtab, are read as given and
+ *           not checked, as fr_gallery_match_view_f32 reads its view.
+ *   seg_counts / seg_len: see fr_gallery_match_f32 (they speak of query SLOTS, f = position in Q).
+ * Result, for every query slot f that some qmap entry names: out_idx[f] = the POSITION IN f's VIEW (not the slab slot)
+ * of the maximum score, lowest position on exact ties, and out_score[f] - bit for bit what fr_gallery_match_view_f32
+ * returns for query f alone against that view (the same k-ordered f32 chains; neither group nor lane matters);
+ * (-1, -1.0f) for a padding slot, an empty view, or when no score exceeds -1.  fr_gallery_topk_grouped_f32: the same for
+ * fr_gallery_topk_view_f32, out_idx / out_score [F][K].  QUERY SLOTS THAT NO qmap ENTRY NAMES ARE NOT WRITTEN.
+ * A group whose view is empty or whose slots are all padding costs no scan work.  ngroups <= 65535.  F == 0 or
+ * ngroups == 0 returns FR_OK without a launch.  workspace: the matching _workspace(ngroups, max_view_len[, K]) bytes
+ * (partial results [blocks][ngroups * 32]). */
+size_t fr_gallery_match_grouped_workspace(int ngroups, int64_t max_view_len);
+int fr_gallery_match_grouped_f32(const float* Q, const float* G, const int64_t* views, const int64_t* gtab,
+                                 const int32_t* qmap, int F, int ngroups, int64_t max_view_len, int64_t capacity, int D,
+                                 int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
+                                 const int32_t* seg_counts, int seg_len, fr_stream_t stream);
+size_t fr_gallery_topk_grouped_workspace(int ngroups, int64_t max_view_len, int K);
+int fr_gallery_topk_grouped_f32(const float* Q, const float* G, const int64_t* views, const int64_t* gtab,
+                                const int32_t* qmap, int F, int ngroups, int64_t max_view_len, int64_t capacity, int D,
+                                int K, int64_t* out_idx /*[F][K]*/, float* out_score /*[F][K]*/, void* workspace,
+                                size_t workspace_bytes, const int32_t* seg_counts, int seg_len, fr_stream_t stream);
 /* f32 -> fp8 e4m3 row conversion (x * FR_F8_SCALE, round to nearest even, n % 4 == 0) */
 int fr_f32_to_f8(const float* x, void* out, int64_t n, fr_stream_t stream);
 /* f32 -> f16 row conversion for building the device-resident gallery (infrenceServer.py:271) */
