@@ -1,8 +1,11 @@
 // Gallery match: re-normalise, linear scan with strict-'>' first-max, decision.
 // Replaces the Python loop at /root/reference/infrenceServer.py:530-552.
 //
-// f32 scan: scores are computed on the f32 MFMA (v_mfma_f32_32x32x2_f32 is an exact
-// k-ordered fmaf chain, so scores are plain IEEE f32 dot products).  Orientation:
+// f32 scan: scores are computed on the f32 MFMA.  v_mfma_f32_32x32x2_f32 is an exact
+// k-ordered fmaf chain - measured on an MI355X (docs/KERNEL_NOTES.md 4.15): two chained,
+// singly rounded fmas per instruction, k slot 0 first, subnormal operands and results kept -
+// so a score is the IEEE f32 fmaf chain over elements 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, ... of
+// the row and the query (scan_tile_f32, match_scan.h), bit for bit.  Orientation:
 // A = 32 gallery rows, B = 32 queries, so a lane owns ONE query (column) and 16 gallery
 // rows (registers): the running (max, first-argmax) is lane-local, no cross-lane work
 // inside the scan.  HBM-bound: N*D*4 bytes per pass per 32-query group.

@@ -123,7 +123,10 @@ __device__ __forceinline__ void unit_row_wave4(float4& v0, float4& v1) {
     v1.x /= nrm; v1.y /= nrm; v1.z /= nrm; v1.w /= nrm;
 }
 
-// One tile on v_mfma_f32_32x32x2_f32 (an exact k-ordered fmaf chain): A = 32 gallery rows, B = 32 queries.
+// One tile on v_mfma_f32_32x32x2_f32: A = 32 gallery rows, B = 32 queries.  The instruction is an exact k-ordered fmaf
+// chain (measured, docs/KERNEL_NOTES.md 4.15: acc = fmaf(a1, b1, fmaf(a0, b0, acc)), one rounding each, subnormals kept), and
+// instruction 4 kk + e takes element 8 kk + e from the h = 0 lanes (k slot 0) and 8 kk + 4 + e from the h = 1 lanes (k slot 1):
+// a score is the fmaf chain over elements 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, ...; tests/test_gpu_scan_pins.py pins its bits.
 // gp = this lane's gallery row + 4 * h, qp = this lane's staged query + 4 * h (h = lane >> 5); a row past the
 // end (ok == false) contributes zeros.  acc[reg] = score(tile row (reg & 3) + 8 * (reg >> 2) + 4 * h, query lane & 31).
 __device__ __forceinline__ float16v scan_tile_f32(const float* __restrict__ gp, const float* qp, bool ok) {

@@ -1,7 +1,8 @@
 // Exact top-K gallery identification: the K best rows per query under the total order (score descending, row
 // ascending) among rows whose score is > -1 - the reference loop's rule (best starts at -1, strict '>', first
-// maximum) extended from 1 to K.  Scores are the same k-ordered f32 MFMA chains as gallery_scan_f32 (match.hip), so
-// column 0 is bit-identical to the top-1 match for every K.
+// maximum) extended from 1 to K.  Scores are the same k-ordered f32 MFMA chains as gallery_scan_f32 (match.hip; what the
+// chain is was measured: scan_tile_f32 in match_scan.h, docs/KERNEL_NOTES.md 4.15), so column 0 is bit-identical to the
+// top-1 match for every K.
 //
 // The candidate list (TopK<KP>: registers only, insert for the scan's step, a bitonic merge for every merge level) is
 // topk_list.h's; the certified re-rank of the coarse scan (scan_gemm.hip) sorts with the same merge.

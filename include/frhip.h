@@ -194,7 +194,8 @@ int fr_gallery_gmax_update(const float* G, const int64_t* slots, int64_t n, int 
  *   seg_counts / seg_len: see fr_gallery_match_f32 (they speak of query SLOTS, f = position in Q).
  * Result, for every query slot f that some qmap entry names: out_idx[f] = the POSITION IN f's VIEW (not the slab slot)
  * of the maximum score, lowest position on exact ties, and out_score[f] - bit for bit what fr_gallery_match_view_f32
- * returns for query f alone against that view (the same k-ordered f32 chains; neither group nor lane matters);
+ * returns for query f alone against that view (the same k-ordered f32 chains - measured to be the fmaf chain over
+ * elements 0, 4, 1, 5, 2, 6, 3, 7, 8, 12, ..., docs/KERNEL_NOTES.md 4.15; neither group nor lane matters);
  * (-1, -1.0f) for a padding slot, an empty view, or when no score exceeds -1.  fr_gallery_topk_grouped_f32: the same for
  * fr_gallery_topk_view_f32, out_idx / out_score [F][K].  QUERY SLOTS THAT NO qmap ENTRY NAMES ARE NOT WRITTEN.
  * A group whose view is empty or whose slots are all padding costs no scan work.  ngroups <= 65535.  F == 0 or
