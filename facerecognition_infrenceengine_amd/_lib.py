@@ -117,6 +117,8 @@ SIGNATURES = {
     "fr_enrol_batch_workspace": (_Z, [_I, _L]),
     "fr_enrol_batch_f32": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _P, _P, _L, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P,
                                 _Z, _P]),
+    "fr_gallery_pairs_workspace": (_Z, [_L, _L]),
+    "fr_gallery_pairs_above_f16": (_I, [_P, _P, _L, _I, _F, _I, _L, _I, _P, _P, _P, _P, _Z, _P]),
     "fr_conv_nhwc_f16": (_I, [C.POINTER(ConvArgs), _P]),
     "fr_conv_sequence": (_I, [C.POINTER(ConvStep), _I, _P]),
     "fr_conv_inblock_f16": (_I, [C.POINTER(ConvArgs), _P]),

@@ -35,6 +35,66 @@ class StaleViewError(_lib.FrError):
     """A GalleryView was used after its gallery's membership changed: fetch a fresh view and retry."""
 
 
+class DuplicateOverflowError(_lib.FrError):
+    """``find_duplicates`` met more candidate pairs than ``max_pairs``: ``needed`` is the ``max_pairs`` that suffices."""
+
+    def __init__(self, msg, needed):
+        super().__init__(msg)
+        self.needed = needed
+
+
+PAIRS_OVERFLOW, PAIRS_NONFINITE = 1, 2      # include/frhip.h FR_PAIRS_OVERFLOW / FR_PAIRS_NONFINITE
+
+
+class DuplicatePairs:
+    """What ``find_duplicates`` found: ``pairs`` int64 [P,2] positions a < b sorted by (a, b), ``scores`` float32 [P] (the
+    dot of the duplicate check, bit for bit), ``ids`` [(id_a, id_b)], ``candidates``: pairs the coarse filter let through."""
+
+    def __init__(self, pairs, scores, ids, candidates):
+        self.pairs, self.scores, self.ids, self.candidates = pairs, scores, ids, candidates
+
+    def __len__(self):
+        return len(self.pairs)
+
+
+def _pairs_device(owner, G, view, N, thr, inclusive, max_pairs, max_ranges=0):
+    """fr_gallery_pairs_above_f16 on the current stream of ``owner.device``: (keys int64 [max_pairs], scores float32
+    [max_pairs], counts int32 [4]), device tensors, no synchronisation."""
+    lib, dev = owner.lib, owner.device
+    max_pairs = int(max_pairs)
+    if max_pairs < 1:
+        raise ValueError("max_pairs must be at least 1")
+    keys = torch.empty(max_pairs, dtype=torch.int64, device=dev)
+    scores = torch.empty(max_pairs, dtype=torch.float32, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws = GalleryMatcher._workspace(owner, lib.fr_gallery_pairs_workspace(N, max_pairs))
+        lib.fr_gallery_pairs_above_f16(_lib.ptr(G), _lib.ptr(view) if view is not None else None, N, DIM, float(thr),
+                                       1 if inclusive else 0, max_pairs, int(max_ranges), _lib.ptr(keys), _lib.ptr(scores),
+                                       _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    return keys, scores, counts
+
+
+def _pairs_host(owner, ids, keys, scores, counts):
+    """One synchronisation to read the counts, then the P pairs found travel and are sorted on the host."""
+    counts_h = torch.empty(4, dtype=torch.int32).pin_memory()
+    with torch.cuda.device(owner.device):
+        counts_h.copy_(counts, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    seen, found, flags = (int(v) for v in counts_h[:3])
+    if flags & PAIRS_NONFINITE:
+        raise ValueError("find_duplicates: a row holds NaN, an infinity or an element beyond the f16 range (+-65504)")
+    if flags & PAIRS_OVERFLOW:
+        raise DuplicateOverflowError(f"find_duplicates: {seen} candidate pairs, max_pairs is {keys.numel()}: retry with "
+                                     f"max_pairs={seen}", seen)
+    k = keys[:found].cpu().numpy()
+    s = scores[:found].cpu().numpy()
+    order = np.argsort(k, kind="stable")                 # a << 32 | b: the order of (a, b)
+    k, s = k[order], s[order]
+    pairs = np.stack([k >> 32, k & 0xFFFFFFFF], axis=1).astype(np.int64).reshape(-1, 2)
+    return DuplicatePairs(pairs, s, [(ids[a], ids[b]) for a, b in pairs], seen)
+
+
 class GalleryMatcher:
     """``G[N,512]`` float32 unit rows on the device + the id table."""
 
@@ -159,6 +219,20 @@ class GalleryMatcher:
         ids = [[self.ids[i] if i >= 0 and (min_score is None or s >= min_score) else None for i, s in zip(ri, rs)]
                for ri, rs in zip(idx_h, score_h)]
         return ids, score_h, idx_h
+
+    def find_duplicates_device(self, thr=0.4, inclusive=False, max_pairs=1 << 20, max_ranges=0):
+        """The audit of ``find_duplicates`` without a synchronisation: device tensors (keys int64 [max_pairs]: a << 32 | b,
+        scores float32 [max_pairs], counts int32 [4]: candidates seen, pairs written, flags (1: more candidates than
+        ``max_pairs``, 2: a non-finite row), row ranges used).  The first counts[1] entries hold the pairs, in no order."""
+        return _pairs_device(self, self.G, None, self.G.shape[0], thr, inclusive, max_pairs, max_ranges)
+
+    def find_duplicates(self, thr=0.4, inclusive=False, max_pairs=1 << 20):
+        """Every pair of rows a < b the enrolment duplicate check would refuse: dot(row a, row b) > ``thr`` (``inclusive``:
+        >=) with the dot of ``first_above`` on the rows as stored, bit for bit - one pass over the pairs on the f16 matrix
+        cores as a filter, the exact dot for every candidate.  Exact, not approximate, for finite rows
+        inside the f16 range; a row outside it raises ValueError.  More than ``max_pairs`` candidates raise
+        ``DuplicateOverflowError`` whose ``needed`` is the ``max_pairs`` to retry with.  Returns ``DuplicatePairs``."""
+        return _pairs_host(self, self.ids, *self.find_duplicates_device(thr, inclusive, max_pairs))
 
     def decide_device(self, idx, score, thr, unknown_thr=None):
         """1 recognised / 0 unknown / 2 dropped (peopleCount.py:876-887 band)."""
@@ -427,6 +501,14 @@ class GalleryView:
 
     last_topk = property(lambda self: last_topk())
 
+    def find_duplicates_device(self, thr=0.4, inclusive=False, max_pairs=1 << 20, max_ranges=0):
+        """As ``GalleryMatcher.find_duplicates_device``; a and b are positions in ``self.ids``.  The f32 rows are read
+        through the slot list whatever ``scan`` the gallery was built with; the coarse slab is not."""
+        if self.generation != self.gallery.generation:
+            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
+        return _pairs_device(self, self.gallery.G, self.slots, len(self.ids), thr, inclusive, max_pairs, max_ranges)
+
+    find_duplicates = GalleryMatcher.find_duplicates
     decide_device = GalleryMatcher.decide_device
     match = GalleryMatcher.match
     match_topk = GalleryMatcher.match_topk

@@ -252,6 +252,24 @@ class EmbeddingManager:
                 hit = self._matchers[key] = (self._gallery.view_set(views), metadatas)
             return hit[0], hit[1], [where[c] for c in company_ids]
 
+    def find_duplicates(self, company_id=None, thr=0.4):
+        """The gallery audit: every pair of rows of the company's view (``None``: the whole gallery, as ``get_all``) the
+        enrolment duplicate check would refuse - dot > ``thr`` on the rows as stored (``GalleryView.find_duplicates``).  The
+        reference checks a new employee against employees and a new visitor against visitors only
+        (trainingServer.py:170-200); a company's view is employees then visitors, so the pair it never checks is found
+        here.  One lock and one flush; the company's cached view.  Returns [{"a", "b", "score", "a_type", "b_type", "a_name",
+        "b_name"}], ordered by the rows' positions in the view."""
+        from .gallery import StaleViewError
+        view, metadata = self.get_matcher_for_company(company_id)
+        try:
+            found = view.find_duplicates(thr=thr)
+        except StaleViewError:                  # a sync on another thread moved the slab on: the current view, once
+            view, metadata = self.get_matcher_for_company(company_id)
+            found = view.find_duplicates(thr=thr)
+        return [{"a": a, "b": b, "score": float(s), "a_type": metadata[a]["type"], "b_type": metadata[b]["type"],
+                 "a_name": metadata[a]["name"], "b_name": metadata[b]["name"]}
+                for (a, b), s in zip(found.ids, found.scores)]
+
     def get_stats(self):
         """infrenceServer.py:386-398."""
         with self.embeddings_lock:

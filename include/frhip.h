@@ -41,7 +41,8 @@ typedef void* fr_stream_t;
  * PReLU epilogue of the plan recogniser, mbf.py), added under 106 later, and for fr_unknown_assign_batch_f32,
  * fr_gallery_first_above_blocked_f32 and fr_enrol_batch_f32 / fr_enrol_batch_workspace (the counting and enrolment paths in
  * batches), added under 106 after those, and for fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32 with their
- * _workspace functions (the grouped view scan of mixed-company batches).  fr_version() returns the value the library was built
+ * _workspace functions (the grouped view scan of mixed-company batches), and for fr_gallery_pairs_above_f16 /
+ * fr_gallery_pairs_workspace (the gallery audit).  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -329,6 +330,28 @@ int fr_enrol_batch_f32(const float* E, const float* bbox, int S, const int32_t* 
                        const int32_t* job_first, int J, int max_poses, int D, const float* G, const int64_t* view, int64_t N,
                        float sim_thr, float dup_thr, int32_t* status, int32_t* pair, int32_t* face, float* avg, float* row,
                        int64_t* dup_pos, float* dup_score, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* Gallery audit: ALL pairs of positions 0 <= a < b < N of a view (position p = row G32[view[p]]; view NULL: row p) with
+ *   s(a, b) = the dot of fr_gallery_first_above_f32 of the two rows as stored (not renormalised, the same bits; symmetric)
+ *   s > thr  (inclusive: s >= thr), in f32
+ * - the pairs the enrolment duplicate check would refuse.  EXACT for every view whose rows are finite and inside the f16
+ * range: an f16 matrix-core pass over the pairs only filters (coarse score >= thr - eps, eps = 1.125 2^-10 Gmax^2 +
+ * 2^-20 2 Gmax + 2^-40 with Gmax the largest row norm of the view: DESIGN.md 4.6f), every candidate is re-scored with
+ * that dot and kept or dropped by it alone.  The coarse slab of a scan="f16" / "f8" gallery is not read.
+ * out_key int64 [capacity]: a << 32 | b; out_score f32 [capacity]: s beside it; both UNORDERED, out_counts[1] entries.
+ * out_counts int32 [4]: [0] candidates the filter saw (it keeps counting past capacity), [1] pairs written, [2] flags,
+ * [3] row ranges the plan used.  FR_PAIRS_OVERFLOW: more candidates than capacity - the pairs written are a subset of the
+ * true set, retry with capacity >= out_counts[0].  FR_PAIRS_NONFINITE: a row of the view holds NaN, an infinity or an
+ * element beyond +-65504 (what fr_gallery_gmax_update reports) - no pair is written.
+ * max_ranges: 0, or an upper bound on the row ranges the scan is cut into (tuning).  N < 2^31, D == 512, 1 <= capacity <
+ * 2^31; N <= 1: zero counts (out_counts may be NULL), no row is read.  workspace: fr_gallery_pairs_workspace(N, capacity)
+ * bytes (Gmax, the candidates, the f16 copy of the view's rows).  Two memsets and four launches whatever N; no allocation,
+ * no synchronisation.  Added under ABI 106. */
+#define FR_PAIRS_OVERFLOW 1
+#define FR_PAIRS_NONFINITE 2
+size_t fr_gallery_pairs_workspace(int64_t N, int64_t capacity);
+int fr_gallery_pairs_above_f16(const float* G32, const int64_t* view, int64_t N, int D, float thr, int inclusive,
+                               int64_t capacity, int max_ranges, int64_t* out_key, float* out_score, int32_t* out_counts,
+                               void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- embed ----
  * a-4  ArcFace IResNet conv stack (inside FaceAnalysis.get, infrenceServer.py:528).
