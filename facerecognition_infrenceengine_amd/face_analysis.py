@@ -526,6 +526,52 @@ class FaceAnalysis:
         faces = self.get_batch(np.asarray(img)[None])[0]
         return faces[:max_num] if max_num else faces
 
+    def get_batch_yuv(self, frames, pixel_format="nv12", matrix="bt601"):
+        """``get_batch`` for YUV 4:2:0 frames, as a video decoder produces them: ``frames`` is a ``uint8 [N, H*3/2, W]`` array
+        or device tensor, or a list of ``[H*3/2, W]`` frames (host arrays or device tensors) - of one size, or under
+        ``det_size`` of any sizes, as ``get_batch`` allows.  ``pixel_format``: ``"nv12"`` / ``"i420"``; ``matrix``: ``"bt601"``
+        (default), ``"bt709"``, ``"jpeg"`` (colour.py).  H and W must be even.  Host frames cross the link as YUV (half of BGR's
+        bytes) and are converted on the device (csrc/yuv_to_bgr.hip); from there on the call IS ``get_batch`` on the
+        converted frames: the same kernels on the same bytes, the same faces bit for bit.  Runs eagerly: ``enable_graphs``
+        does not cover this entry point."""
+        from .colour import check_yuv_shape, yuv420_to_bgr
+        if self.det is None:
+            raise _lib.FrError("FaceAnalysis.prepare() has not been called")
+
+        def one(f):
+            if not torch.is_tensor(f):
+                f = torch.from_numpy(np.ascontiguousarray(np.asarray(f)))
+            if f.dtype != torch.uint8:
+                raise ValueError("YUV frames must be uint8")
+            return f.to(self.device).contiguous()
+        if isinstance(frames, (list, tuple)):
+            if not frames:
+                return []
+            yuv = [one(f) for f in frames]
+            shapes = [check_yuv_shape(f.shape) for f in yuv]
+            if any(s != shapes[0] for s in shapes):
+                if self.det_size is None:
+                    raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
+            else:
+                yuv = torch.stack(yuv)
+        else:
+            yuv = one(frames)
+            if yuv.dim() != 3:
+                raise ValueError("frames must be uint8 [N, H*3/2, W] (or a list of [H*3/2, W] frames)")
+            check_yuv_shape(yuv.shape[1:])
+        with self._lock, torch.cuda.device(self.device):
+            return self._faces_of(self.detect_embed_device(yuv420_to_bgr(yuv, pixel_format, matrix)))
+
+    def get_yuv(self, frame, pixel_format="nv12", matrix="bt601", max_num=0):
+        """``get`` for one YUV 4:2:0 frame (``uint8 [H*3/2, W]``, host array or device tensor): see ``get_batch_yuv``.  Runs
+        eagerly, whatever ``enable_graphs`` says."""
+        if not torch.is_tensor(frame):
+            frame = np.asarray(frame)
+        if frame.ndim != 2:
+            raise ValueError("frame must be uint8 [H*3/2, W]")
+        faces = self.get_batch_yuv(frame[None], pixel_format, matrix)[0]
+        return faces[:max_num] if max_num else faces
+
 
 _GRAPH_KEYS = ("bbox", "kps", "det_score", "embedding", "normed_embedding")
 

@@ -6,6 +6,10 @@ synchronous host-to-device copy per frame.  Here the capture/decoder side writes
 page-locked ring slots (``host_buffer``), ``upload`` starts an asynchronous copy of a whole batch on a
 dedicated HIP copy stream and returns an event; the detector stream waits for that event only, so the copy of
 batch i+1 runs under the kernels of batch i.  The HUD overlay stays on the CPU (out of scope).
+
+``pixel_format="nv12"`` / ``"i420"``: the ring's pinned slots hold YUV 4:2:0 frames (``uint8 [H*3/2, W]``, what a video decoder
+produces: colour.py) - half the bytes on the link and in the pinned ring.  ``upload`` copies them to a device staging arena and
+launches the conversion (csrc/yuv_to_bgr.hip) behind the copy on the copy stream; what it returns is what it returns for BGR.
 """
 import io
 
@@ -31,26 +35,43 @@ def decode_image(data):
 
 
 class FrameIngest:
-    """Ring of ``depth`` batch slots: pinned ``uint8 [N,H,W,3]`` host buffers + matching device buffers."""
+    """Ring of ``depth`` batch slots: pinned ``uint8 [N,H,W,3]`` host buffers + matching device buffers.  With a YUV
+    ``pixel_format`` the pinned buffers are ``uint8 [N,H*3/2,W]`` and the device buffers are still BGR ``[N,H,W,3]``."""
 
-    def __init__(self, n, h, w, device="cuda:0", depth=3):
+    def __init__(self, n, h, w, device="cuda:0", depth=3, pixel_format="bgr", matrix="bt601"):
         """One asynchronous copy of the whole batch per slot on one copy stream (round 4 measured frame groups and a second copy
-        stream: no gain / -5 %, profiles/r04_ingest_ab.txt; the knobs are gone)."""
+        stream: no gain / -5 %, profiles/r04_ingest_ab.txt; the knobs are gone).  ``pixel_format`` ``"nv12"`` / ``"i420"`` with
+        ``matrix`` (colour.MATRICES): YUV 4:2:0 slots, H and W even, converted on the device by ``upload``."""
+        from .colour import check_pixel_format, check_yuv_size
         _lib.require_gpu()
         self.device = torch.device(device)
         self.shape, self.depth = (int(n), int(h), int(w), 3), int(depth)
-        self._host = [torch.empty(self.shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        self.pixel_format = pixel_format
+        self._layout, self._consts = check_pixel_format(pixel_format, matrix)
+        host_shape = self.shape
+        if self._layout is not None:
+            check_yuv_size(self.shape[1], self.shape[2])
+            host_shape = (self.shape[0], self.shape[1] * 3 // 2, self.shape[2])
+            # ONE staging arena serves every slot: copy and conversion of a slot are queued on the one copy stream, so the next
+            # slot's copy starts after this slot's conversion has read the arena
+            self._yuv = torch.empty(host_shape, dtype=torch.uint8, device=self.device)
+            self._lib = _lib.load()
+        self._host = [torch.empty(host_shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
         self._dev = [torch.empty(self.shape, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
         self._stream = torch.cuda.Stream(device=self.device)
         self._busy = [None] * self.depth          # event: last consumer of the slot's device buffer
 
     def host_buffer(self, slot):
-        """NumPy view of the slot's pinned buffer: the decoder / capture thread writes frames here."""
+        """NumPy view of the slot's pinned buffer: the decoder / capture thread writes frames here (BGR ``[N,H,W,3]``, or
+        the ring's YUV format ``[N,H*3/2,W]``)."""
         return self._host[slot % self.depth].numpy()
 
     def decode_into(self, slot, index, data):
         """Decode image bytes straight into frame ``index`` of the slot's pinned buffer (no intermediate pageable
-        copy).  False when the bytes do not decode or the picture is not the ring's H x W."""
+        copy).  False when the bytes do not decode or the picture is not the ring's H x W - and always on a YUV ring: the
+        decoder here produces BGR, and a still image that is to enter a YUV ring is the caller's to convert."""
+        if self._layout is not None:
+            return False
         img = decode_image(data)
         if img is None or img.shape != self.shape[1:]:
             return False
@@ -59,12 +80,19 @@ class FrameIngest:
 
     def upload(self, slot):
         """Start the H2D copy of the slot; returns (device frames, event that fires when they have landed).
-        The copy waits for the slot's previous consumer (see ``release``)."""
+        The copy waits for the slot's previous consumer (see ``release``).  A YUV ring copies the YUV bytes and converts them
+        behind the copy on the same stream; the frames returned are BGR and the event fires after the conversion."""
         k = slot % self.depth
         with torch.cuda.stream(self._stream):
             if self._busy[k] is not None:
                 self._stream.wait_event(self._busy[k])
-            self._dev[k].copy_(self._host[k], non_blocking=True)
+            if self._layout is None:
+                self._dev[k].copy_(self._host[k], non_blocking=True)
+            else:
+                from .colour import convert_batch
+                self._yuv.copy_(self._host[k], non_blocking=True)
+                convert_batch(self._lib, self._yuv, self._dev[k], self.shape[0], self.shape[1], self.shape[2], self._layout,
+                              self._consts)
         ev = torch.cuda.Event()
         ev.record(self._stream)
         return self._dev[k], ev
@@ -82,20 +110,40 @@ class RaggedIngest:
     of the same layout: one H2D copy per batch, the same ``upload`` / ``release`` protocol.  The frame table the kernels
     read (include/frhip.h fr_frame_ref: pointers into the slot's device arena, sizes, and - with ``det_size`` - the sizes on
     the detection canvas) and ``det_scale`` depend on the shapes alone: they are written on the host and uploaded once,
-    here, so a batch adds no copy and no synchronisation for them."""
+    here, so a batch adds no copy and no synchronisation for them.
 
-    def __init__(self, shapes, det_size=None, device="cuda:0", depth=3):
+    ``pixel_format="nv12"`` / ``"i420"`` (``shapes`` stay the frames' (H, W), both even): the pinned arena holds the YUV 4:2:0
+    frames (``[H*3/2, W]`` each, at 16-byte-aligned offsets of their own), ``upload`` copies it to ONE device staging arena
+    and converts the whole table in one launch behind the copy; the device arena, the tables and ``det_scale`` are those of
+    the BGR ring."""
+
+    def __init__(self, shapes, det_size=None, device="cuda:0", depth=3, pixel_format="bgr", matrix="bt601"):
+        from .colour import check_pixel_format, check_yuv_size
         from .letterbox import check_det_size, frame_table
         _lib.require_gpu()
         self.device = torch.device(device)
         self.shapes = tuple((int(s[0]), int(s[1])) for s in shapes)
         self.det_size, self.depth = check_det_size(det_size), int(depth)
+        self.pixel_format = pixel_format
+        self._layout, self._consts = check_pixel_format(pixel_format, matrix)
         self.offsets, off = [], 0
         for h, w in self.shapes:
             self.offsets.append(off)
             off += (h * w * 3 + 15) // 16 * 16
         self.nbytes = max(off, 16)
-        self._host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        host_bytes = self.nbytes
+        if self._layout is not None:
+            self.yuv_offsets, off = [], 0
+            for h, w in self.shapes:
+                check_yuv_size(h, w)
+                self.yuv_offsets.append(off)
+                off += (h * w * 3 // 2 + 15) // 16 * 16
+            host_bytes = max(off, 16)
+            # one staging arena for every slot: a slot's copy and conversion are queued on the one copy stream
+            self._yuv = torch.empty(host_bytes, dtype=torch.uint8, device=self.device)
+            self._src_ptrs = torch.tensor([self._yuv.data_ptr() + o for o in self.yuv_offsets], dtype=torch.int64).to(self.device)
+            self._lib = _lib.load()
+        self._host = [torch.empty(host_bytes, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
         self._dev = [torch.empty(self.nbytes, dtype=torch.uint8, device=self.device) for _ in range(self.depth)]
         self._stream = torch.cuda.Stream(device=self.device)
         self._busy = [None] * self.depth
@@ -107,25 +155,35 @@ class RaggedIngest:
         torch.cuda.synchronize(self.device)              # construction time: the tables are in place before the first upload
 
     def host_frame(self, slot, index):
-        """NumPy view ``uint8 [H,W,3]`` of frame ``index`` in the slot's pinned arena: the capture side writes here."""
+        """NumPy view ``uint8 [H,W,3]`` of frame ``index`` in the slot's pinned arena: the capture side writes here.  On a
+        YUV ring the view is the YUV frame, ``uint8 [H*3/2, W]``."""
         h, w = self.shapes[index]
+        if self._layout is not None:
+            o = self.yuv_offsets[index]
+            return self._host[slot % self.depth].numpy()[o:o + h * w * 3 // 2].reshape(h * 3 // 2, w)
         o = self.offsets[index]
         return self._host[slot % self.depth].numpy()[o:o + h * w * 3].reshape(h, w, 3)
 
     def device_frame(self, slot, index):
-        """The same frame in the slot's device arena (a view)."""
+        """The same frame in the slot's device arena (a view): BGR ``[H,W,3]`` whatever the ring's pixel format."""
         h, w = self.shapes[index]
         o = self.offsets[index]
         return self._dev[slot % self.depth][o:o + h * w * 3].view(h, w, 3)
 
     def upload(self, slot):
         """Start the H2D copy of the slot's arena; returns (device arena, frame table on the device, event that fires when
-        the frames have landed).  The copy waits for the slot's previous consumer (see ``release``)."""
+        the frames have landed).  The copy waits for the slot's previous consumer (see ``release``).  A YUV ring copies the
+        YUV arena and converts every frame of the table in one launch behind the copy; the event fires after it."""
         k = slot % self.depth
         with torch.cuda.stream(self._stream):
             if self._busy[k] is not None:
                 self._stream.wait_event(self._busy[k])
-            self._dev[k].copy_(self._host[k], non_blocking=True)
+            if self._layout is None:
+                self._dev[k].copy_(self._host[k], non_blocking=True)
+            else:
+                from .colour import convert_table
+                self._yuv.copy_(self._host[k], non_blocking=True)
+                convert_table(self._lib, self.tables[k], self._src_ptrs, len(self.shapes), self._layout, self._consts)
         ev = torch.cuda.Event()
         ev.record(self._stream)
         return self._dev[k], self.tables[k], ev

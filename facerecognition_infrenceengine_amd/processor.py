@@ -349,7 +349,7 @@ class FaceRecognitionProcessor:
             self.initialize_detector()
         return getattr(self.face_detector, "det_size", None) is not None
 
-    def _scan_mixed(self, frames, company_ids, k=None):
+    def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601"):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
         no company has a gallery (nothing is run), else (n, slot results, view_set, metadatas, index_of, idx, score);
@@ -366,7 +366,7 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", c)
         if all(v is None for v in index_of):
             return None
-        n, r = _detect_embed_batch(self, self.face_detector, frames)
+        n, r = _detect_embed_batch(self, self.face_detector, frames, pixel_format, matrix)
         cap = r["bbox"].shape[1]
 
         def scan(vs, of):
@@ -380,8 +380,8 @@ class FaceRecognitionProcessor:
             idx, score = scan(view_set, index_of)
         return n, r, view_set, metadatas, index_of, idx, score
 
-    def _recognize_batch_mixed(self, frames, company_ids):
-        got = self._scan_mixed(frames, company_ids)
+    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601"):
+        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score = got
@@ -401,16 +401,17 @@ class FaceRecognitionProcessor:
                         for j in range(int(counts[f]))])
         return out
 
-    def identify_batch(self, frames, company_id, k=5, min_score=None):
+    def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601"):
         """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
         list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
-        whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path."""
+        whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``: as
+        ``recognize_batch``."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
-        got = self._scan_mixed(frames, ids, k=int(k))
+        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score = got
@@ -429,7 +430,7 @@ class FaceRecognitionProcessor:
                         for j in range(int(counts[f]))])
         return out
 
-    def recognize_batch(self, frames, company_id):
+    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601"):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -442,16 +443,21 @@ class FaceRecognitionProcessor:
         engine pass, then one grouped scan in which every frame is matched through its own company's view, one
         decision launch and the one synchronisation.  The result is then always a list: None stands in for the frames
         whose company has no gallery, the other frames are served.  The grouped scan is the exact f32 scan, also when
-        the manager was built with scan="f16" / "f8": the same ids, the exact scan's score bits."""
+        the manager was built with scan="f16" / "f8": the same ids, the exact scan's score bits.
+
+        ``pixel_format="nv12"`` / ``"i420"``: the frames are YUV 4:2:0 as a video decoder produces them (``uint8 [H*3/2, W]``, H
+        and W even) with colour ``matrix`` ``"bt601"`` / ``"bt709"`` / ``"jpeg"`` (colour.py).  They cross the link at half of
+        BGR's bytes and are converted on the device behind the copy; the results are those of the converted BGR frames.
+        ``annotate`` draws on BGR host frames and does not take YUV."""
         if isinstance(company_id, (list, tuple)):
-            return self._recognize_batch_mixed(frames, company_id)
+            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
         if len(matcher) == 0:
             logger.warning("No embeddings found for company %s", company_id)
             return None
-        n, r = _detect_embed_batch(self, self.face_detector, frames)
+        n, r = _detect_embed_batch(self, self.face_detector, frames, pixel_format, matrix)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
                                                      r["normed_embedding"])
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
@@ -699,26 +705,39 @@ def _detect_embed(detector, frame):
         return detector.detect_embed_device(dev)
 
 
-def _detect_embed_batch(owner, det, frames):
+def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601"):
     """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
-    ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape) -> copy stream ->
-    ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
-    engine has a ``det_size``.  Returns (number of frames, the slot results: device tensors)."""
+    ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape and pixel format) -> copy
+    stream -> ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
+    engine has a ``det_size``.  ``pixel_format`` ``"nv12"`` / ``"i420"``: the frames are YUV 4:2:0, ``uint8 [H*3/2, W]``, and the
+    ring converts them on the device behind its copy (ingest.py).  Returns (number of frames, the slot results: device tensors)."""
     import torch
+    from .colour import check_pixel_format, check_yuv_shape
     from .ingest import FrameIngest, RaggedIngest
     arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
-    n, (h, w) = len(arr), arr[0].shape[:2]
     det_size = getattr(det, "det_size", None)
-    if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr) or \
-            (det_size is None and any(a.shape != (h, w, 3) for a in arr)):
+    yuv = check_pixel_format(pixel_format, matrix)[0] is not None
+    if yuv:
+        if any(a.ndim != 2 or a.dtype != np.uint8 for a in arr):
+            raise ValueError(f"{pixel_format} frames of a batch must be uint8 [H*3/2, W]")
+        shapes = tuple(check_yuv_shape(a.shape) for a in arr)
+    else:
+        if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr):
+            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
+        shapes = tuple(a.shape[:2] for a in arr)
+    n, (h, w) = len(arr), shapes[0]
+    if det_size is None and any(s != (h, w) for s in shapes):
         raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
     stages = owner.__dict__.setdefault("_stages", {})
-    key = (n, h, w) if det_size is None else (tuple(a.shape[:2] for a in arr), det_size)
+    key = (n, h, w) if det_size is None else (shapes, det_size)
+    fmt = {"pixel_format": pixel_format, "matrix": matrix} if yuv else {}
+    if yuv:                                           # the BGR rings keep the keys they always had
+        key += (pixel_format, matrix)
     if key not in stages:
         while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
             stages.pop(next(iter(stages)))
-        stages[key] = [FrameIngest(n, h, w, det.device, depth=2) if det_size is None else
-                       RaggedIngest(key[0], det_size, det.device, depth=2), 0]
+        stages[key] = [FrameIngest(n, h, w, det.device, depth=2, **fmt) if det_size is None else
+                       RaggedIngest(key[0], det_size, det.device, depth=2, **fmt), 0]
     ring, turn = stages[key]
     stages[key][1] = turn + 1
     with det._lock, torch.cuda.device(det.device):

@@ -42,7 +42,8 @@ typedef void* fr_stream_t;
  * fr_gallery_first_above_blocked_f32 and fr_enrol_batch_f32 / fr_enrol_batch_workspace (the counting and enrolment paths in
  * batches), added under 106 after those, and for fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32 with their
  * _workspace functions (the grouped view scan of mixed-company batches), and for fr_gallery_pairs_above_f16 /
- * fr_gallery_pairs_workspace (the gallery audit).  fr_version() returns the value the library was built
+ * fr_gallery_pairs_workspace (the gallery audit), and for fr_yuv420_to_bgr_u8 / fr_yuv420_to_bgr_refs_u8 (YUV 4:2:0 frame ingest),
+ * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
 int fr_version(void);
@@ -735,6 +736,37 @@ int fr_letterbox_u8(const fr_frame_ref* refs, int nframes, uint8_t* canvas, int 
  * [nframes,cap,5,2] of the slots j < counts[f] is divided (IEEE f32) by det_scale[f]; other slots are left untouched. */
 int fr_detections_unscale(float* boxes, float* kps, const int32_t* counts, const float* det_scale, int nframes, int cap,
                           fr_stream_t stream);
+
+/* YUV 4:2:0 frames -> the packed BGR u8 [H,W,3] frames every entry above takes: what a video decoder produces (the reference's
+ * live path is RTSP / webcam capture, infrenceServer.py:573-601; cv2.VideoCapture decodes to YUV 4:2:0 and converts on the CPU)
+ * converted on the device, so a frame crosses the link at 1.5 bytes per pixel.  A source frame is u8 [H*3/2, W] (cv2's
+ * convention), H and W even:
+ *   FR_YUV_NV12   Y plane [H,W], then H/2 rows of W bytes holding interleaved U, V
+ *   FR_YUV_I420   Y plane [H,W], then the U plane [H/2,W/2], then the V plane [H/2,W/2]
+ * Nearest chroma (the 2x2 pixel block (2i..2i+1, 2j..2j+1) shares chroma sample (i, j)) and, per pixel, in 32-bit integers:
+ *   y = max(0, Y - y_off) * cy + (1 << 19);   u = U - 128;   v = V - 128
+ *   B = sat8((y + cub u) >> 20)   G = sat8((y + cug u + cvg v) >> 20)   R = sat8((y + cvr v) >> 20)
+ * with an arithmetic shift (floor) and sat8 = clamp to [0, 255]: exact, the same bytes from any launch shape.  The constants
+ * come from the caller, one set per colour matrix (the Python host's table: colour.MATRICES); they are refused unless
+ * 0 <= y_off <= 255, cy >= 0 and 255 cy + 2^19 + 128 max(|cub|, |cug| + |cvg|, |cvr|) < 2^31 - no intermediate leaves int32.
+ * Any byte alignment of the frames; W % 16 == 0 with frames that start on 16 bytes gives aligned 16-byte accesses throughout.
+ * One launch each; nothing outside the source and destination frames is read or written.
+ *
+ * fr_yuv420_to_bgr_u8: a uniform batch, source frames back to back at H*W*3/2 bytes each, destination frames at H*W*3 each.
+ * Refused before any launch: odd or non-positive H or W, a frame of 2 GiB or more (H*W*3 >= 2^31), an unknown layout, bad
+ * constants, a null pointer with N > 0.  N == 0 returns FR_OK and reads nothing.
+ * fr_yuv420_to_bgr_refs_u8: frames of differing sizes.  dst_refs: a DEVICE table whose entry f names destination frame f
+ * (data - written here, the const of the struct notwithstanding -, H, W; nh / nw are not read: the table a RaggedIngest hands
+ * to the warps and the letterbox serves as it is); src_ptrs: a DEVICE array of nframes pointers, src_ptrs[f] the YUV frame of
+ * entry f (dst_refs[f].H * W * 3 / 2 bytes).  The sizes live on the device, so they cannot be refused here: an entry with an
+ * odd or non-positive side, of 2 GiB or more, or with a null pointer on either side is skipped as a whole (the host checks:
+ * colour.check_yuv_shape).  nframes == 0 returns FR_OK and reads nothing; at most 65535 frames. */
+#define FR_YUV_NV12 0
+#define FR_YUV_I420 1
+int fr_yuv420_to_bgr_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, int layout, int y_off, int cy, int cub, int cug,
+                        int cvg, int cvr, fr_stream_t stream);
+int fr_yuv420_to_bgr_refs_u8(const fr_frame_ref* dst_refs, const uint8_t* const* src_ptrs, int nframes, int layout, int y_off,
+                             int cy, int cub, int cug, int cvg, int cvr, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- SCRFD detector ----
  * The detector of insightface's buffalo_l pack (det_10g.onnx; FaceAnalysis(name="buffalo_l"), infrenceServer.py:412-416) as
