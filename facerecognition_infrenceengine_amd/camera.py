@@ -26,8 +26,11 @@ logger = logging.getLogger(__name__)
 
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
-                 dead_after=200):
+                 dead_after=200, gate=None):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
+        ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
+        frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
+        results held from that last processed frame.  None: every frame goes through the engine, as ever.
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
         waits for slow cameras once it holds a frame (latency stays that of the slowest *present* frame).
         ``reopen_after`` / ``dead_after``: consecutive failed reads before a capture is re-opened / given up."""
@@ -44,6 +47,19 @@ class CameraManager:
         self.company_of = {}                   # source -> company id of the start call that added it
         self._control = threading.Lock()       # start / stop calls, one at a time
         self.stats = {"batches": 0, "frames": 0, "dropped_results": 0, "largest_batch": 0, "dead_sources": []}
+        self.gate = gate
+        self._held = {}                        # source -> results of its last processed frame (gate only)
+        if gate is not None:
+            self.stats["gated_frames"] = 0
+
+    def _forget(self, source):
+        """A source that is gone: its gate slot is freed and its held results dropped."""
+        if self.gate is not None:
+            self._held.pop(source, None)
+            try:
+                self.gate.forget(source)
+            except Exception as e:
+                logger.error("Camera %s: the gate did not forget it: %s", source, e)
 
     # ---- capture side (infrenceServer.py:573-601)
     def capture_frames(self, source, frame_queue):
@@ -69,6 +85,7 @@ class CameraManager:
                     if fails >= self.dead_after:
                         logger.error("Camera %s: %d failed reads in a row: giving up on this source", source, fails)
                         self.stats["dead_sources"].append(source)
+                        self._forget(source)
                         break
                     if fails % self.reopen_after == 0:
                         try:
@@ -133,7 +150,9 @@ class CameraManager:
         processor takes mixed sizes (``accepts_mixed_sizes``: an engine with a ``det_size``); results leave in batch order.
         ``company_id``: one id for the whole batch, or a list / tuple aligned with ``batch``.  Frames of several
         companies still go through the engine together: the processor call gets the per-frame list then, and the plain
-        id whenever all its frames share one."""
+        id whenever all its frames share one.  With a gate the processor also gets ``gate=`` and the frames' sources as
+        ``camera_ids=``; where it answers ``UNCHANGED`` the source's held results stand in (here and in the returned list) and
+        ``stats["gated_frames"]`` counts the frame."""
         mixed_ids = isinstance(company_id, (list, tuple))
         if mixed_ids and len(company_id) != len(batch):
             raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
@@ -145,9 +164,18 @@ class CameraManager:
         for ks in by_shape.values():
             ids = [company_id[k] for k in ks] if mixed_ids else [company_id]
             one = all(c == ids[0] for c in ids[1:])
-            res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids)
+            gated = {} if self.gate is None else {"gate": self.gate, "camera_ids": [batch[k][0] for k in ks]}
+            res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids, **gated)
             for j, k in enumerate(ks):
                 results[k] = None if res is None else res[j]
+        if self.gate is not None:
+            from .processor import UNCHANGED
+            for k, (source, _) in enumerate(batch):
+                if results[k] is UNCHANGED:           # the scene is the same, so the boxes are
+                    results[k] = self._held.get(source)
+                    self.stats["gated_frames"] += 1
+                else:
+                    self._held[source] = results[k]
         self.stats["batches"] += 1
         self.stats["frames"] += len(batch)
         self.stats["largest_batch"] = max(self.stats["largest_batch"], len(batch))
@@ -226,6 +254,9 @@ class CameraManager:
             for t in self.threads:
                 t.join(timeout=5)
             self.threads.clear()
+            for s in list(dict.fromkeys(list(self.company_of) + list(self._held))):
+                self._forget(s)
+            self._held = {}
             self.company_of = {}
             self.frame_queues = {}
         logger.info("All camera threads stopped")

@@ -21,6 +21,48 @@ import numpy as np
 logger = logging.getLogger(__name__)
 
 
+class _Unchanged:
+    """The type of ``UNCHANGED``: one instance, compared by identity."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "UNCHANGED"
+
+    def __reduce__(self):
+        return "UNCHANGED"
+
+
+# What ``recognize_batch`` / ``identify_batch`` return for a frame their ``gate`` judged inactive: the scene is what the last
+# processed frame of that camera showed, and the engine did not run for it.  Never None (no gallery) and never [] (no face).
+UNCHANGED = _Unchanged()
+
+
+def _check_gate(gate, camera_ids, n):
+    """The camera ids of a gated call as a list (None without a gate); ValueError before anything runs."""
+    if gate is None:
+        if camera_ids is not None:
+            raise ValueError("camera_ids come with a gate (gate=ActivityGate(...))")
+        return None
+    if camera_ids is None:
+        raise ValueError("a gate needs camera_ids: one camera id per frame")
+    ids = list(camera_ids)
+    if len(ids) != n:
+        raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
+    if len(set(ids)) != len(ids):
+        raise ValueError("a camera id is repeated in one call")
+    return ids
+
+
+def _spread(out, keep, n):
+    """Results of the active frames ``keep`` back at their places among ``n`` frames; UNCHANGED for the others."""
+    if keep is None:
+        return out
+    full = [UNCHANGED] * n
+    for j, f in enumerate(keep):
+        full[f] = out[j]
+    return full
+
+
 class InMemoryStore:
     """Store protocol used by EmbeddingManager (what the Mongo collections + GridFS buckets of
     /root/reference/db/__init__.py:11-26 provide).  Documents use the reference's field names."""
@@ -349,11 +391,14 @@ class FaceRecognitionProcessor:
             self.initialize_detector()
         return getattr(self.face_detector, "det_size", None) is not None
 
-    def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601"):
+    def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
-        no company has a gallery (nothing is run), else (n, slot results, view_set, metadatas, index_of, idx, score);
-        device tensors, no synchronisation beyond the engine's own."""
+        no company has a gallery (nothing is run, a gate is not consulted), else (n, slot results, view_set, metadatas,
+        index_of, idx, score, keep); device tensors, no synchronisation beyond the engine's own.  With a ``gate``, ``keep``
+        lists the active frames and everything else describes exactly those n = len(keep) frames, in order (``keep`` None:
+        all frames, the ungated call's tensors); with none active the slot results are None, and idx / score are None when
+        no active frame's company has a gallery."""
         from .gallery import StaleViewError
         company_ids = list(company_ids)
         if len(company_ids) != len(frames):
@@ -366,7 +411,13 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", c)
         if all(v is None for v in index_of):
             return None
-        n, r = _detect_embed_batch(self, self.face_detector, frames, pixel_format, matrix)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids)
+        if keep is not None:                      # the views of the active frames' companies, as a call on those frames has them
+            company_ids = [company_ids[f] for f in keep]
+            if r is not None:
+                view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
+            if r is None or all(v is None for v in index_of):
+                return n, r, view_set, metadatas, index_of, None, None, keep
         cap = r["bbox"].shape[1]
 
         def scan(vs, of):
@@ -378,13 +429,15 @@ class FaceRecognitionProcessor:
         except StaleViewError:                    # a sync moved the slab on meanwhile: the current views, once
             view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
             idx, score = scan(view_set, index_of)
-        return n, r, view_set, metadatas, index_of, idx, score
+        return n, r, view_set, metadatas, index_of, idx, score, keep
 
-    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601"):
-        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix)
+    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
+        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids)
         if got is None:
             return [None] * len(frames)
-        n, r, view_set, metadatas, index_of, idx, score = got
+        n, r, view_set, metadatas, index_of, idx, score, keep = got
+        if idx is None:                           # no frame active, or none of the active ones has a gallery
+            return _spread([None] * n, keep, len(frames))
         dec = view_set.decide_device(idx, score, self.recognition_threshold)
         cap = r["bbox"].shape[1]
         counts = r["counts"].cpu().numpy()                                   # the one synchronisation
@@ -399,22 +452,26 @@ class FaceRecognitionProcessor:
             ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
             out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], ids, metadata)
                         for j in range(int(counts[f]))])
-        return out
+        return _spread(out, keep, len(frames))
 
-    def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601"):
+    def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601", gate=None,
+                       camera_ids=None):
         """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
         list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
-        whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``: as
-        ``recognize_batch``."""
+        whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``,
+        ``gate`` / ``camera_ids``: as ``recognize_batch``."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
+        camera_ids = _check_gate(gate, camera_ids, len(frames))
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
-        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix)
+        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids)
         if got is None:
             return [None] * len(frames)
-        n, r, view_set, metadatas, index_of, idx, score = got
+        n, r, view_set, metadatas, index_of, idx, score, keep = got
+        if idx is None:
+            return _spread([None] * n, keep, len(frames))
         cap = r["bbox"].shape[1]
         counts = r["counts"].cpu().numpy()                                   # the one synchronisation
         idx, score = idx.cpu().numpy().reshape(n, cap, -1), score.cpu().numpy().reshape(n, cap, -1)
@@ -428,9 +485,9 @@ class FaceRecognitionProcessor:
             pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
             out.append([_face_candidates(bbox[f, j], dscore[f, j], idx[f, j], score[f, j], pids, metadata, min_score)
                         for j in range(int(counts[f]))])
-        return out
+        return _spread(out, keep, len(frames))
 
-    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601"):
+    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -448,16 +505,29 @@ class FaceRecognitionProcessor:
         ``pixel_format="nv12"`` / ``"i420"``: the frames are YUV 4:2:0 as a video decoder produces them (``uint8 [H*3/2, W]``, H
         and W even) with colour ``matrix`` ``"bt601"`` / ``"bt709"`` / ``"jpeg"`` (colour.py).  They cross the link at half of
         BGR's bytes and are converted on the device behind the copy; the results are those of the converted BGR frames.
-        ``annotate`` draws on BGR host frames and does not take YUV."""
+        ``annotate`` draws on BGR host frames and does not take YUV.
+
+        ``gate`` (an ``activity.ActivityGate``) with ``camera_ids`` (one hashable id per frame, none repeated): the frames go
+        through the same ring, the gate judges the ring's device frames (one small device-to-host copy and one
+        synchronisation more), and the engine pass, the scan and the decision run on the ACTIVE frames only - a device
+        gather of those frames (the selected rows of the frame table under ``det_size``: no frame bytes move), or the ring's
+        tensors as they are when every frame is active.  An inactive frame's entry is ``UNCHANGED``; the entries of the
+        active frames are what this call returns, without a gate, for exactly those frames with their company ids, in
+        order.  They are not the full batch's bits: the embed net's small-batch modes sum in another order, and a gated
+        turn embeds fewer faces.  With no frame active nothing but the upload and the gate runs.  When the company has no
+        gallery the None of the ungated call comes first: the gate is not consulted and its state does not move."""
+        camera_ids = _check_gate(gate, camera_ids, len(frames))
         if isinstance(company_id, (list, tuple)):
-            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix)
+            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
         if len(matcher) == 0:
             logger.warning("No embeddings found for company %s", company_id)
             return None
-        n, r = _detect_embed_batch(self, self.face_detector, frames, pixel_format, matrix)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids)
+        if r is None:                                                        # no frame active
+            return [UNCHANGED] * len(frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
                                                      r["normed_embedding"])
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
@@ -470,7 +540,7 @@ class FaceRecognitionProcessor:
         for f in range(n):
             out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], matcher.ids, metadata)
                         for j in range(int(counts[f]))])
-        return out
+        return _spread(out, keep, len(frames))
 
     def annotate(self, frame, results):
         """Draw ``recognize`` / ``recognize_batch`` results onto a frame (colours of infrenceServer.py:546-553)."""
@@ -706,11 +776,25 @@ def _detect_embed(detector, frame):
 
 
 def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601"):
+    """``_detect_embed_batch_gated`` without a gate: (number of frames, the slot results)."""
+    n, r, _ = _detect_embed_batch_gated(owner, det, frames, pixel_format, matrix)
+    return n, r
+
+
+def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
     """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
     ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape and pixel format) -> copy
     stream -> ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
     engine has a ``det_size``.  ``pixel_format`` ``"nv12"`` / ``"i420"``: the frames are YUV 4:2:0, ``uint8 [H*3/2, W]``, and the
-    ring converts them on the device behind its copy (ingest.py).  Returns (number of frames, the slot results: device tensors)."""
+    ring converts them on the device behind its copy (ingest.py).  Returns (number of frames, the slot results: device tensors,
+    keep).
+
+    ``gate`` (``activity.ActivityGate``) with ``camera_ids``: the gate judges the ring's device frames behind the copy - one
+    small device-to-host copy and one synchronisation - and the engine runs on the active frames only: ``keep`` is the list of
+    their indices, the frame count and the slot results are theirs (a device gather of the frames; under ``det_size`` the
+    selected rows of the ring's frame table and of ``det_scale``, no frame bytes move).  With none active the slot results are
+    None and nothing but the upload and the gate has run.  ``keep`` None: every frame, the ring's tensors as they are - the code
+    path of a call without a gate."""
     import torch
     from .colour import check_pixel_format, check_yuv_shape
     from .ingest import FrameIngest, RaggedIngest
@@ -746,14 +830,31 @@ def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601"):
             for i, a in enumerate(arr):
                 host[i] = a
             dev, ready = ring.upload(turn)
-            r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True)      # results go to the host anyway
+            ragged = {}
         else:                                         # one arena, one copy, one engine pass whatever the frames' sizes
             for i, a in enumerate(arr):
                 ring.host_frame(turn, i)[...] = a
             dev, table, ready = ring.upload(turn)
-            r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, table=table, det_scale=ring.det_scale)
+            ragged = {"table": table, "det_scale": ring.det_scale}
+        keep = None
+        if gate is not None:
+            torch.cuda.current_stream(det.device).wait_event(ready)
+            active, _ = gate.judge(dev, camera_ids, table=ragged.get("table"))          # the extra copy and synchronisation
+            if not active.all():
+                keep = [int(f) for f in np.flatnonzero(active)]
+                n = len(keep)
+                if n == 0:
+                    ring.release(turn)
+                    return 0, None, keep
+                sel = torch.tensor(keep, dtype=torch.int64).to(det.device)
+                if det_size is None:
+                    dev = dev.index_select(0, sel)                                      # the one device copy
+                else:                                 # the arena stays where it is: the table's rows name the active frames
+                    ragged = {"table": ragged["table"].view(-1, 32).index_select(0, sel).reshape(-1),
+                              "det_scale": ragged["det_scale"].index_select(0, sel)}
+        r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, **ragged)    # results go to the host anyway
         ring.release(turn)
-    return n, r
+    return n, r, keep
 
 
 def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):

@@ -2,7 +2,7 @@
 
 ``onnx_import.scrfd_plan_from_onnx`` turns the graph into device steps for one canvas size; ``SCRFDHIP`` packs the
 folded weights once (head weights the graph shares across strides are packed once), keeps one activation arena per
-(thread, stream, batch size, canvas size) and walks the steps with the fr_det_* kernels, then fr_scrfd_decode per level and
+(thread, stream, batch size, canvas size) - the ``MAX_ARENAS`` most recently used of a thread - and walks the steps with the fr_det_* kernels, then fr_scrfd_decode per level and
 fr_sort_nms per frame - all on the current stream, no host synchronisation.
 """
 import threading
@@ -12,6 +12,9 @@ import torch
 
 from . import _lib
 from .onnx_import import OnnxGraph, read_onnx, scrfd_plan_from_onnx
+
+
+MAX_ARENAS = 8          # activation arenas kept per thread: the most recently used (batch size, canvas size, stream) keys
 
 
 def _ceil(x, m):
@@ -139,9 +142,11 @@ class SCRFDHIP:
     4096); ``cap_out``: faces per frame.  ``share``: another SCRFDHIP of the same graph and device whose packed weights
     are used (``FaceAnalysis.clone_with``).
 
-    Memory: one activation arena is kept per (thread, stream, batch size N, canvas size) that has been seen and is never
-    released while the detector lives (a captured graph may hold its addresses); an arena grows with N - several hundred MB
-    at N = 64 on 640 x 640 - so a caller that varies N freely should pad its batches to a few fixed sizes."""
+    Memory: one activation arena is kept per (thread, stream, batch size N, canvas size), the ``MAX_ARENAS`` most recently
+    used of each thread (a gated camera turn brings any N from 1 to the camera count: DESIGN.md 4.5c); an arena grows with
+    N - several hundred MB at N = 64 on 640 x 640.  A dropped arena's blocks return to torch's allocator, which hands them
+    out again only behind the work already queued on them; no path of this package captures ``detect_batch`` in a graph (an
+    engine with a detection canvas runs eagerly), and a caller that does keeps the capture's own memory pool alive."""
 
     def __init__(self, path_or_graph, device="cuda:0", det_thresh=0.5, nms_thresh=0.4, cap=1024, cap_out=16, share=None):
         _lib.require_gpu()
@@ -179,9 +184,14 @@ class SCRFDHIP:
     def _arena(self, N, hw):
         arenas = self._tls.__dict__.setdefault("arenas", {})
         key = (N, hw, torch.cuda.current_stream(self.device).cuda_stream)
-        a = arenas.get(key)
+        a = arenas.pop(key, None)
         if a is None:
-            a = arenas[key] = _Arena(self, self.plan(hw), N)
+            # a gated camera turn (activity.ActivityGate) brings any frame count from 1 to the camera count: keep the
+            # MAX_ARENAS most recently used (a dropped arena's blocks go back to the allocator behind the work queued on them)
+            while len(arenas) >= MAX_ARENAS:
+                arenas.pop(next(iter(arenas)))
+            a = _Arena(self, self.plan(hw), N)
+        arenas[key] = a                                 # most recently used last
         return a
 
     def forward_heads(self, canvas):

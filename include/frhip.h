@@ -43,6 +43,7 @@ typedef void* fr_stream_t;
  * batches), added under 106 after those, and for fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32 with their
  * _workspace functions (the grouped view scan of mixed-company batches), and for fr_gallery_pairs_above_f16 /
  * fr_gallery_pairs_workspace (the gallery audit), and for fr_yuv420_to_bgr_u8 / fr_yuv420_to_bgr_refs_u8 (YUV 4:2:0 frame ingest),
+ * and for fr_frame_activity_u8 / fr_frame_activity_refs_u8 (the activity gate in front of the engine pass),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -767,6 +768,40 @@ int fr_yuv420_to_bgr_u8(const uint8_t* src, uint8_t* dst, int N, int H, int W, i
                         int cvg, int cvr, fr_stream_t stream);
 int fr_yuv420_to_bgr_refs_u8(const fr_frame_ref* dst_refs, const uint8_t* const* src_ptrs, int nframes, int layout, int y_off,
                              int cy, int cub, int cug, int cvg, int cvr, fr_stream_t stream);
+
+/* Activity gate: which frames of a camera batch differ from the last PROCESSED frame of the same camera, so that the engine
+ * pass can leave the others out (the reference takes every 2nd frame whatever it shows, peopleCount.py:938,962, and drops
+ * frames when a queue is full, infrenceServer.py:595-598,614-617).  A frame is BGR u8 [H,W,3].  In 32-bit integers:
+ *   L = (29 B + 150 G + 77 R + 128) >> 8                 per pixel, 0 .. 255 (the weights sum to 256)
+ *   m = (sum of L over the cell + 128) >> 8              per 16 x 16 cell; gh = H / 16 rows of gw = W / 16 cells, row-major
+ *                                                        (remainder rows and columns belong to no cell)
+ * State lives on the device, per camera slot s < S, and belongs to the caller (zeroed once):
+ *   grid u8 [S][C]     the cell means of the last frame of the slot that was judged active
+ *   geom i32 [S][2]    the (H, W) grid[s] was taken at, (0, 0): none
+ *   idle i32 [S]       consecutive frames judged inactive
+ * Per frame f, with s = slot[f] and cur[f] = its cell means (u8 [N][C] scratch, written for every judged frame):
+ *   changed[f] = -1 if geom[s] != (H, W), else the number of cells with |cur - grid[s]| > thr          (strictly greater)
+ *   active[f]  = changed < 0 or changed >= min_cells or (max_idle > 0 and idle[s] >= max_idle)
+ *   active: grid[s] = cur[f], geom[s] = (H, W), idle[s] = 0;   else idle[s] += 1 (grid and geom untouched).
+ * A frame with H < 16 or W < 16, with more than C cells, or whose slot is outside [0, S) is active with changed = -1 and no
+ * state is read or written for it.  slot, changed, active: i32 [N] on the device.  Two frames of one batch must not name one
+ * slot (the result is then unspecified, every access still inside the arrays).
+ * Two launches on `stream` (cell means: every byte of the cell area read once, any byte alignment; then one workgroup per
+ * frame that counts, judges and commits), no synchronisation, allocation, memset or atomics: the same bytes from any launch
+ * shape.
+ *
+ * fr_frame_activity_u8: a uniform batch u8 [N,H,W,3].  Refused before any launch: more than 65535 frames, non-positive H, W, S
+ * or C, thr outside 0 .. 255, min_cells < 1, max_idle < 0, H*W*3 >= 2^31, a null pointer with N > 0.  N == 0 returns FR_OK
+ * and touches nothing.
+ * fr_frame_activity_refs_u8: the same over a DEVICE frame table (data, H and W are read; the table a RaggedIngest hands to the
+ * letterbox serves as it is).  The sizes live on the device: an entry of 2 GiB or more or with a null pointer is treated as
+ * one without cells (active, changed = -1, no state).  Added under ABI 106. */
+int fr_frame_activity_u8(const uint8_t* frames, int N, int H, int W, const int32_t* slot, int S, uint8_t* grid, int32_t* geom,
+                         int32_t* idle, int C, uint8_t* cur, int32_t* changed, int32_t* active, int thr, int min_cells,
+                         int max_idle, fr_stream_t stream);
+int fr_frame_activity_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* slot, int S, uint8_t* grid, int32_t* geom,
+                              int32_t* idle, int C, uint8_t* cur, int32_t* changed, int32_t* active, int thr, int min_cells,
+                              int max_idle, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- SCRFD detector ----
  * The detector of insightface's buffalo_l pack (det_10g.onnx; FaceAnalysis(name="buffalo_l"), infrenceServer.py:412-416) as
