@@ -169,6 +169,9 @@ SIGNATURES = {
     "fr_pnet_conv1_band": (_I, [_I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "fr_pnet_band_tiles_count": (_Z, [_I, _I, _I]),
     "fr_pnet_band_tiles": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "fr_pnet23_coarse_workspace_bytes": (_Z, [_I, _I, _I]),
+    "fr_pnet23_coarse_f16": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _Z, _F, _P, _Z, _P, _P]),
+    "fr_pnet_pyramid_p23_coarse": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, C.POINTER(_P), _P, _P]),
     "fr_pnet_finish_levels": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _F, _P, _P]),
     "fr_pnet_pyramid_conv1": (_I, [_I, _P, _I, _I, _I, C.POINTER(PnetLevel), _I, _P, _P, _P, _P, _P, _I, _P]),
     "fr_pnet_pyramid_p23": (_I, [C.POINTER(PnetLevel), _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P]),

@@ -14,6 +14,9 @@
 // threshold or above it - about 1 % of the cells, which this kernel appends to per-block work lists as it goes.  Cells the
 // exact pass does not touch are below the threshold by more than the error bound, i.e. certainly rejected, whatever the
 // rounding.  Kept-box sets and all downstream values therefore equal those of an all-f32 evaluation.
+// On the batch path the kernel runs in TWO TIERS (fr_pnet23_coarse_f16 / fr_pnet_pyramid_p23_coarse): a coarse pass over every cell
+// with the hi halves only - one MFMA per product - and this split arithmetic over just the ~1 % of cells the coarse pass cannot
+// rule out, bit for bit; what everything behind it finds is unchanged (pnet23_body<true>, pnet23_reeval_levels below).
 //
 // Tile: 8 x 32 conv3 cells per pass of a block (8 waves); needs conv2 on 10 x 34 and the conv1 map on 12 x 36.
 // GEMM view (both convs): D[cout][pixel] = sum_k W[cout][k] X[pixel][k], k = (tap, channel) with 16 channels per tap
@@ -50,23 +53,19 @@ struct P23Args {
                                           // face threshold) and every cell with dl >= logit_thr gets its split-precision head row written;
                                           // otherwise (the default) every cell with dl >= logit_thr is listed: kept cells carry f32 bits
     int B, H1, W1, H3, W3, tiles_x, tiles_y, ntiles;
+    // the coarse pass (pnet23_body<true>) and the split re-evaluation of its list (pnet23_reeval_levels)
+    int* clist; int* ccounts;             // the coarse list: one segment of seg_cap cells per block and its count, laid out like list / counts
+    float coarse_thr;                     // cells with a hi-only dl >= coarse_thr (= logit_thr - coarse_margin), or a non-finite one, are listed
+    int* visited;                         // optional: accumulated number of cells on the coarse lists (diagnostics), or NULL
 };
 
-// The body is block `vb` of a grid of `vgrid` blocks over the level's tiles: the whole launch (pnet23_split_f16), or the
-// level's share of a pyramid-wide one (pnet23_split_levels) - the level's workspace is laid out for `vgrid` blocks either way.
-__device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, const int vgrid, char* lds) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    char* x1t = lds;                                        // hi plane [448 px][32 B] | lo plane [448][32] (432 used; 448 = 14 DMA pieces)
-    char* x2t = x1t + 2 * P23_X1PL;                         // hi plane [340 px][32 B] | lo plane
-    char* wf = x2t + 2 * P23_X2PL;                          // fragments: conv2 [5 ks][2 planes][64 lanes][16 B], conv3 [2 ct][5][2][64][16]
-    float* cst = reinterpret_cast<float*>(wf + 30 * 1024);  // b2[16] s2[16] b3[32] s3[32] hb[8]
-    int* lcnt = reinterpret_cast<int*>(cst + 104);           // cells this block has appended to its list segment
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 15, fq = lane >> 4;
-
-    // ---- once per block: weights -> split f16 fragments in LDS (A operand: row = cout fr, k = 8*fq + j within a K step)
-    for (int e = tid; e < 30 * 64; e += P23_NT) {           // e = ((slot * 2 + plane) * 64 + lane'), slot = conv2 ks | 5 + ct*5 + ks
-        const int l2 = e & 63, plane = (e >> 6) & 1, slot = e >> 7;
+// Weights -> f16 fragments in LDS (A operand: row = cout fr, k = 8*fq + j within a K step), NP planes (2: hi | lo, 1: hi only) per
+// slot = conv2 ks | 5 + ct*5 + ks, and the constants b2[16] s2-1[16] b3[32] s3-1[32] hb[8]; by all NT threads of the block.
+template <int NP, int NT>
+__device__ __forceinline__ void p23_stage_weights(const P23Args& a, char* wf, float* cst) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 15 * NP * 64; e += NT) {          // e = ((slot * NP + plane) * 64 + lane')
+        const int l2 = e & 63, plane = NP == 2 ? (e >> 6) & 1 : 0, slot = e / (64 * NP);
         const int r = l2 & 15, q = l2 >> 4;
         const bool c3 = slot >= 5;
         const int ct = c3 ? (slot - 5) / 5 : 0, ks = c3 ? (slot - 5) % 5 : slot;
@@ -76,11 +75,32 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
         for (int j = 0; j < 8; ++j) o[j] = split_f16_plane(w[j], plane);
         *reinterpret_cast<half8*>(wf + (size_t)e * 16) = o;
     }
-    for (int e = tid; e < 16; e += P23_NT) { cst[e] = a.b2[e]; cst[16 + e] = a.s2[e] - 1.f; }      // slopes as s - 1: PReLU = x + (s - 1) min(x, 0), two operations
-    for (int e = tid; e < 32; e += P23_NT) { cst[32 + e] = a.b3[e]; cst[64 + e] = a.s3[e] - 1.f; }
-    for (int e = tid; e < 8; e += P23_NT) cst[96 + e] = e < 6 ? a.hb[e] : 0.f;
+    for (int e = tid; e < 16; e += NT) { cst[e] = a.b2[e]; cst[16 + e] = a.s2[e] - 1.f; }      // slopes as s - 1: PReLU = x + (s - 1) min(x, 0), two operations
+    for (int e = tid; e < 32; e += NT) { cst[32 + e] = a.b3[e]; cst[64 + e] = a.s3[e] - 1.f; }
+    for (int e = tid; e < 8; e += NT) cst[96 + e] = e < 6 ? a.hb[e] : 0.f;
+}
+
+// The body is block `vb` of a grid of `vgrid` blocks over the level's tiles: the whole launch (pnet23_split_f16), or the
+// level's share of a pyramid-wide one (pnet23_split_levels) - the level's workspace is laid out for `vgrid` blocks either way.
+// COARSE: the same walk with the hi plane of every operand only - ONE MFMA per product, no lo plane loaded, written or read - which
+// decides nothing: it writes its dl and lists, in the coarse list, every cell whose dl is within `coarse_margin` of what the split
+// form could list (>= coarse_thr, or non-finite); pnet23_reeval_levels gives exactly those cells the split form's bits.
+template <bool COARSE>
+__device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, const int vgrid, char* lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int NP = COARSE ? 1 : 2;                      // operand planes
+    char* x1t = lds;                                        // hi plane [448 px][32 B] | lo plane [448][32] (432 used; 448 = 14 DMA pieces)
+    char* x2t = x1t + NP * P23_X1PL;                        // hi plane [340 px][32 B] | lo plane
+    char* wf = x2t + NP * P23_X2PL;                         // fragments: conv2 [5 ks][NP planes][64 lanes][16 B], conv3 [2 ct][5][NP][64][16]
+    float* cst = reinterpret_cast<float*>(wf + NP * 15 * 1024);  // b2[16] s2[16] b3[32] s3[32] hb[8]
+    int* lcnt = reinterpret_cast<int*>(cst + 104);           // cells this block has appended to its list segment
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // ---- once per block: weights -> split f16 fragments in LDS
+    p23_stage_weights<NP, P23_NT>(a, wf, cst);
     if (tid == 0) *lcnt = 0;
-    int* const seg = a.list + (size_t)vb * a.seg_cap;
+    int* const seg = (COARSE ? a.clist : a.list) + (size_t)vb * a.seg_cap;
 
     // per-lane tap offsets of the 5 K steps (lane quarter fq < 2: tap 2ks, else tap 2ks+1; tap 9 does not exist: its
     // weights are zero, it reads tap 8's pixels)
@@ -101,9 +121,10 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
     // instruction), piece j by wave j % 8; a lane moves 16-B chunk (lane & 1) of pixel 32 (j % 14) + (lane >> 1) from
     // the 64-B global row [hi 32 B | lo 32 B]; pixels outside the map (and the 16 padding pixels of piece 13) read zeros.
     __amdgpu_buffer_rsrc_t xrs = buffer_rsrc(a.x1s, a.x1s_bytes);
-    int wy[4], wx[4], wc[4];
+    constexpr int NPIECE = 14 * NP, NI = (NPIECE + 7) / 8;  // the coarse pass moves the hi plane's 14 pieces only
+    int wy[NI], wx[NI], wc[NI];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NI; ++i) {
         const int j = wave + 8 * i, pl = j >= 14 ? 1 : 0;
         const int p = (j - 14 * pl) * 32 + (lane >> 1);
         wy[i] = p < P23_X1PX ? p / P23_X1W : 1 << 20; wx[i] = p % P23_X1W;
@@ -114,9 +135,9 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
         const int n = tile / per, rem = tile - n * per;
         const int ty0 = (rem / a.tiles_x) * P23_RH, tx0 = (rem % a.tiles_x) * P23_RW;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < NI; ++i) {
             const int j = wave + 8 * i;
-            if (j < 28) {
+            if (j < NPIECE) {
                 const int gy = ty0 + wy[i], gx = tx0 + wx[i];
                 const unsigned off = (gy < a.H1 && gx < a.W1) ? (unsigned)(((n * a.H1 + gy) * a.W1 + gx) * 64 + wc[i]) : 0x80000000u;
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (lds_ptr_t)(x1t + (j >= 14 ? P23_X1PL + (j - 14) * 1024 : j * 1024)), 16, off, 0, 0, 0);
@@ -132,6 +153,7 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
         const float w = fr < 6 ? a.hw[co * 6 + fr] : 0.f;
         split_f16(w, hwh, hwl, j);
     }
+    (void)hwl;
     issue_window(vb);
     for (int tile = vb; tile < a.ntiles; tile += vgrid) {
         const int per = a.tiles_x * a.tiles_y;
@@ -153,17 +175,27 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
             }
 #pragma unroll
             for (int ks = 0; ks < 5; ++ks) {
-                const half8 ahi = *reinterpret_cast<const half8*>(wf + ((ks * 2 + 0) * 64 + lane) * 16);
-                const half8 alo = *reinterpret_cast<const half8*>(wf + ((ks * 2 + 1) * 64 + lane) * 16);
+                const half8 ahi = *reinterpret_cast<const half8*>(wf + ((ks * NP + 0) * 64 + lane) * 16);
+                if constexpr (COARSE) {
 #pragma unroll
-                for (int t = 0; t < 3; ++t) {
-                    if (t < nt) {
-                        const char* bp = x1t + (pb[t] + off2[ks]);
-                        const half8 bhi = *reinterpret_cast<const half8*>(bp);
-                        const half8 blo = *reinterpret_cast<const half8*>(bp + P23_X1PL);
-                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[t], 0, 0, 0);
+                    for (int t = 0; t < 3; ++t) {
+                        if (t < nt) {
+                            const half8 bhi = *reinterpret_cast<const half8*>(x1t + (pb[t] + off2[ks]));
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[t], 0, 0, 0);
+                        }
+                    }
+                } else {
+                    const half8 alo = *reinterpret_cast<const half8*>(wf + ((ks * 2 + 1) * 64 + lane) * 16);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        if (t < nt) {
+                            const char* bp = x1t + (pb[t] + off2[ks]);
+                            const half8 bhi = *reinterpret_cast<const half8*>(bp);
+                            const half8 blo = *reinterpret_cast<const half8*>(bp + P23_X1PL);
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc[t], 0, 0, 0);
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc[t], 0, 0, 0);
+                            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc[t], 0, 0, 0);
+                        }
                     }
                 }
             }
@@ -176,12 +208,19 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
                     float4v v = acc[t] + bb;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(fminf(v[e], 0.f), ss[e], v[e]);
-                    half4 hi, lo;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) split_f16(v[e], hi, lo, e);
                     char* o = x2t + q * 32 + fq * 8;
-                    *reinterpret_cast<half4*>(o) = hi;
-                    *reinterpret_cast<half4*>(o + P23_X2PL) = lo;
+                    if constexpr (COARSE) {                 // convert, do not split: the tile has no lo plane
+                        half4 hi;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) hi[e] = (half_t)v[e];
+                        *reinterpret_cast<half4*>(o) = hi;
+                    } else {
+                        half4 hi, lo;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) split_f16(v[e], hi, lo, e);
+                        *reinterpret_cast<half4*>(o) = hi;
+                        *reinterpret_cast<half4*>(o + P23_X2PL) = lo;
+                    }
                 }
             }
         }
@@ -199,6 +238,18 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
             }
 #pragma unroll
             for (int ks = 0; ks < 5; ++ks) {
+                if constexpr (COARSE) {
+                    half8 ahi[2];
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) ahi[ct] = *reinterpret_cast<const half8*>(wf + ((5 + ct * 5 + ks) * 64 + lane) * 16);
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) {
+                        const half8 bhi = *reinterpret_cast<const half8*>(x2t + (pb[t] + off3[ks]));
+#pragma unroll
+                        for (int ct = 0; ct < 2; ++ct) acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[ct], bhi, acc[t][ct], 0, 0, 0);
+                    }
+                    continue;
+                }
                 half8 ahi[2], alo[2];
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
@@ -236,8 +287,10 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
                     bh[4 + e] = h1; bl[4 + e] = (half_t)(x1 - (float)h1);
                 }
                 float4v d = {0.f, 0.f, 0.f, 0.f};
-                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwl, bh, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh, bl, d, 0, 0, 0);
+                if constexpr (!COARSE) {
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwl, bh, d, 0, 0, 0);
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh, bl, d, 0, 0, 0);
+                }
                 d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh, bh, d, 0, 0, 0);
                 // d[r] = head 4*fq + r of pixel fr (heads 6..15 are zero rows)
                 const int q = (wave * 2 + t) * 16 + fr;
@@ -250,7 +303,8 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
                 const bool band = a.band_hi > a.logit_thr;
                 // the exact pass's work list: one LDS atomic per wave and pixel tile that holds a flagged cell (a non-finite
                 // split value is flagged whatever the mode: only the f32 arithmetic can decide that cell)
-                const bool flag = inb && fq == 0 && (split_nonfinite(dlv) || (dlv >= a.logit_thr && (!band || dlv <= a.band_hi)));
+                // (the coarse pass lists every cell the split form could list, band or not: the re-evaluation applies the flag rule)
+                const bool flag = inb && fq == 0 && (split_nonfinite(dlv) || (COARSE ? dlv >= a.coarse_thr : (dlv >= a.logit_thr && (!band || dlv <= a.band_hi))));
                 const unsigned long long fm = __ballot(flag);
                 if (fm) {
                     int base = 0;
@@ -262,7 +316,7 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
                     if (fq == 0) a.dl[cell] = o1 - o0;
                     // the approximate heads themselves are read by nobody in the product path (fr_pnet_candidates skips the
                     // cells below the margin, the exact pass overwrites the others): 24 B per cell of HBM writes saved
-                    if (a.all_heads || (band && dlv >= a.logit_thr)) {
+                    if (!COARSE && (a.all_heads || (band && dlv >= a.logit_thr))) {      // (the coarse pass writes no head rows)
                         float* o = a.head + cell * 6 + 4 * fq;
                         *reinterpret_cast<float2*>(o) = make_float2(o0, o1);
                         if (fq == 0) *reinterpret_cast<float2*>(o + 2) = make_float2(d[2] + hb4[2], d[3] + hb4[3]);
@@ -272,13 +326,17 @@ __device__ __forceinline__ void pnet23_body(const P23Args& a, const int vb, cons
         }
     }
     __syncthreads();
-    if (tid == 0) a.counts[vb] = *lcnt;
+    if (tid == 0) (COARSE ? a.ccounts : a.counts)[vb] = *lcnt;
 #endif
 }
 
 __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_f16(P23Args a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    pnet23_body(a, (int)blockIdx.x, (int)gridDim.x, lds);
+    pnet23_body<false>(a, (int)blockIdx.x, (int)gridDim.x, lds);
+}
+__global__ __launch_bounds__(P23_NT, 4) void pnet23_coarse_f16(P23Args a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    pnet23_body<true>(a, (int)blockIdx.x, (int)gridDim.x, lds);
 }
 
 // ALL pyramid levels of a batch in one launch (fr_pnet_pyramid_p23): level l owns the blocks first[l] .. first[l + 1] - the
@@ -300,7 +358,204 @@ __global__ __launch_bounds__(P23_NT, 4) void pnet23_split_levels(P23Args a, P23L
     a.x1s = t.x1s[l]; a.x1s_bytes = (unsigned)a.B * a.H1 * a.W1 * 64; a.head = t.head[l];
     a.dl = t.dl[l]; a.counts = reinterpret_cast<int*>(a.dl + (size_t)a.B * a.H3 * a.W3); a.list = a.counts + 512;
     a.seg_cap = t.seg_cap[l];
-    pnet23_body(a, (int)blockIdx.x - t.first[l], t.first[l + 1] - t.first[l], lds);
+    pnet23_body<false>(a, (int)blockIdx.x - t.first[l], t.first[l + 1] - t.first[l], lds);
+}
+
+// The level table of the coarse launches: a level's coarse buffer ([512 counts | grid x seg_cap cells]) rides beside it.
+struct P23Coarse { int* buf[P23_MAXL]; };
+__device__ __forceinline__ int p23_find_level(const P23Levels& t, const int g) {          // the level that owns block / segment g
+    int l = 0;
+    while (l + 1 < t.nlevels && g >= t.first[l + 1]) ++l;
+    return l;
+}
+__device__ __forceinline__ void p23_set_level(P23Args& a, const P23Levels& t, const P23Coarse& c, const int l) {
+    a.H1 = t.H1[l]; a.W1 = t.W1[l]; a.H3 = a.H1 - 4; a.W3 = a.W1 - 4;
+    a.tiles_x = (a.W3 + P23_RW - 1) / P23_RW; a.tiles_y = (a.H3 + P23_RH - 1) / P23_RH;
+    a.ntiles = a.B * a.tiles_x * a.tiles_y;
+    a.x1s = t.x1s[l]; a.x1s_bytes = (unsigned)a.B * a.H1 * a.W1 * 64; a.head = t.head[l];
+    a.dl = t.dl[l]; a.counts = reinterpret_cast<int*>(a.dl + (size_t)a.B * a.H3 * a.W3); a.list = a.counts + 512;
+    a.seg_cap = t.seg_cap[l];
+    a.ccounts = c.buf[l]; a.clist = c.buf[l] + 512;
+}
+__global__ __launch_bounds__(P23_NT, 4) void pnet23_coarse_levels(P23Args a, P23Levels t, P23Coarse c) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int l = p23_find_level(t, (int)blockIdx.x);
+    p23_set_level(a, t, c, l);
+    pnet23_body<true>(a, (int)blockIdx.x - t.first[l], t.first[l + 1] - t.first[l], lds);
+}
+
+// ---------------------------------------------------------------- split-precision re-evaluation of the coarse list
+// Gives the cells on the coarse lists the values pnet23_body<false> computes for them, bit for bit, SIXTEEN cells per wave trip:
+// an MFMA output element depends on its own row (weights) and column (cell) operands only, so it is enough that a cell's column
+// sees the operands of the full kernel in the full kernel's order -
+//   the cell's 5 x 5 window of the split map -> LDS as a hi and a lo plane of 25 x 32 B (100 16-B pieces per cell, 25 per lane and
+//         trip, all in flight at once; the NEXT trip's pieces are fetched into registers under this trip's arithmetic)
+//   conv2 at the cell's 3 x 3 positions: the five K steps of two taps x 16 channels, lane quarter fq feeding tap 2ks + (fq >> 1)
+//         (tap 9 = tap 8's pixel under zero weights), channels 8 (fq & 1) .., the MFMAs alo*bhi, ahi*blo, ahi*bhi per step
+//   bias + PReLU as fma(min(v, 0), s - 1, v), split_f16, through LDS (D rows are couts 4fq + r, a B operand wants 8 channels):
+//         the nine positions' tile takes the head of the cell's window slot once every window read is done
+//   conv3 over the 9 positions as taps, both cout tiles; heads with the k order (fq, [tile 0 x 4, tile 1 x 4])
+// and then does for the cell what pnet23_body<false>'s epilogue does: dl, the head row in band mode, the flag rule's append to
+// the segment's EXISTING list, its count.  Cells not on a coarse list keep the coarse dl (< logit_thr - margin).
+// A WAVE owns a segment (coarse list of tier-0 block b -> list segment b): its append counter is a register, nothing is shared
+// between waves but the weight fragments, staged once per block; the launch is persistent, wave w of W takes the segments w,
+// w + W, .. of the level table (largest level first: every wave gets its share of the long lists).
+#define P23R_NT 256
+#define P23R_SLOT 1616                                     // bytes of a cell's slot: hi plane 25 x 32 B | lo plane; 404 dwords: conflict-free b128 reads
+#define P23R_LO 800
+#define P23R_LDS ((size_t)30 * 1024 + 108 * 4 + (P23R_NT / 64) * 16 * P23R_SLOT)      // 134,576 B: one block per CU
+__global__ __launch_bounds__(P23R_NT, 1) void pnet23_reeval_levels(P23Args a, P23Levels t, P23Coarse c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    char* wf = lds;                                         // the fragments of pnet23_body<false>: [15 slots][2 planes][64 lanes][16 B]
+    float* cst = reinterpret_cast<float*>(wf + 30 * 1024);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fq = lane >> 4;
+    char* const win = reinterpret_cast<char*>(cst + 108) + wave * (16 * P23R_SLOT);      // this wave's 16 cell slots
+    p23_stage_weights<2, P23R_NT>(a, wf, cst);
+    half8 hwh, hwl;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int co = j < 4 ? 4 * fq + j : 16 + 4 * fq + (j - 4);
+        const float w = fr < 6 ? a.hw[co * 6 + fr] : 0.f;
+        split_f16(w, hwh, hwl, j);
+    }
+    __syncthreads();                                        // the only block-wide step: from here on every wave is on its own
+    const float4v bb = *reinterpret_cast<const float4v*>(cst + 4 * fq), ss = *reinterpret_cast<const float4v*>(cst + 16 + 4 * fq);
+    const float4v b30 = *reinterpret_cast<const float4v*>(cst + 32 + 4 * fq), s30 = *reinterpret_cast<const float4v*>(cst + 64 + 4 * fq);
+    const float4v b31 = *reinterpret_cast<const float4v*>(cst + 48 + 4 * fq), s31 = *reinterpret_cast<const float4v*>(cst + 80 + 4 * fq);
+    const float4v hb4 = *reinterpret_cast<const float4v*>(cst + 96 + 4 * (fq & 1));
+    const bool band = a.band_hi > a.logit_thr;
+    char* const xc = win + fr * P23R_SLOT + (fq & 1) * 16;  // the lane's cell slot, at its 8-channel chunk
+    // the lane's 25 pieces of a trip: piece it * 64 + lane = (cell slot j, window pixel px, 16-B chunk ch of the 64-B row)
+    int pj[25], psrc[25], pdst[25];
+    const int nseg = t.first[t.nlevels];
+    for (int g = (int)blockIdx.x * (P23R_NT / 64) + wave; g < nseg; g += (int)gridDim.x * (P23R_NT / 64)) {
+        const int l = p23_find_level(t, g);
+        p23_set_level(a, t, c, l);
+        const int vb = g - t.first[l];
+        const int n_list = a.ccounts[vb];
+        const int* const lst = a.clist + (size_t)vb * a.seg_cap;
+        int* const seg = a.list + (size_t)vb * a.seg_cap;
+        const int hw3 = a.H3 * a.W3;
+        int nflag = 0;                                      // cells this wave has appended to the segment (wave-uniform)
+        if (a.visited && lane == 0 && n_list) atomicAdd(a.visited, n_list);
+#pragma unroll
+        for (int it = 0; it < 25; ++it) {
+            const int idx = it * 64 + lane, j = idx / 100, rem = idx - j * 100, px = rem >> 2, ch = rem & 3;
+            pj[it] = j;
+            psrc[it] = ((px / 5) * a.W1 + px % 5) * 64 + ch * 16;
+            pdst[it] = j * P23R_SLOT + (ch >> 1) * P23R_LO + px * 32 + (ch & 1) * 16;
+        }
+        // slots past the list's end repeat its last cell and store nothing
+        auto corner_of = [&](int i0) {                      // byte offset of the window corner of the trip's cell `fr` (the map stays below 2 GiB)
+            const int cell = lst[min(i0 + fr, n_list - 1)];
+            const int n = cell / hw3, rem = cell - n * hw3, y = rem / a.W3, x = rem - y * a.W3;
+            return ((n * a.H1 + y) * a.W1 + x) * 64;
+        };
+        float4v pf[25];
+        if (n_list > 0) {
+            const int corner = corner_of(0);
+#pragma unroll
+            for (int it = 0; it < 25; ++it)
+                pf[it] = *reinterpret_cast<const float4v*>(a.x1s + (size_t)(unsigned)(__shfl(corner, pj[it], 64) + psrc[it]));
+        }
+        for (int i0 = 0; i0 < n_list; i0 += 16) {
+            const int cell = lst[min(i0 + fr, n_list - 1)];
+#pragma unroll
+            for (int it = 0; it < 25; ++it) *reinterpret_cast<float4v*>(win + pdst[it]) = pf[it];
+            __builtin_amdgcn_wave_barrier();                // (a wave's LDS operations execute in order: the window writes precede the reads below)
+            if (i0 + 16 < n_list) {                         // the next trip's windows, under this trip's arithmetic
+                const int corner = corner_of(i0 + 16);
+#pragma unroll
+                for (int it = 0; it < 25; ++it)
+                    pf[it] = *reinterpret_cast<const float4v*>(a.x1s + (size_t)(unsigned)(__shfl(corner, pj[it], 64) + psrc[it]));
+            }
+            // ---- conv2 at the 3 x 3 positions
+            float4v acc2[9];
+#pragma unroll
+            for (int p = 0; p < 9; ++p) acc2[p] = float4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 5; ++ks) {
+                int tp = 2 * ks + (fq >> 1);
+                if (tp > 8) tp = 8;
+                const half8 ahi = *reinterpret_cast<const half8*>(wf + ((ks * 2 + 0) * 64 + lane) * 16);
+                const half8 alo = *reinterpret_cast<const half8*>(wf + ((ks * 2 + 1) * 64 + lane) * 16);
+#pragma unroll
+                for (int p = 0; p < 9; ++p) {
+                    const char* bp = xc + ((p / 3 + tp / 3) * 5 + (p % 3 + tp % 3)) * 32;
+                    const half8 bhi = *reinterpret_cast<const half8*>(bp);
+                    const half8 blo = *reinterpret_cast<const half8*>(bp + P23R_LO);
+                    acc2[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc2[p], 0, 0, 0);
+                    acc2[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc2[p], 0, 0, 0);
+                    acc2[p] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc2[p], 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();                // every window read is done: the conv2 tile takes the head of the slot
+#pragma unroll
+            for (int p = 0; p < 9; ++p) {
+                float4v v = acc2[p] + bb;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(fminf(v[e], 0.f), ss[e], v[e]);
+                half4 hi, lo;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split_f16(v[e], hi, lo, e);
+                char* o = win + fr * P23R_SLOT + p * 32 + fq * 8;
+                *reinterpret_cast<half4*>(o) = hi;
+                *reinterpret_cast<half4*>(o + P23R_LO) = lo;
+            }
+            __builtin_amdgcn_wave_barrier();
+            // ---- conv3 (position = tap), both cout tiles
+            float4v acc3[2] = {float4v{0.f, 0.f, 0.f, 0.f}, float4v{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int ks = 0; ks < 5; ++ks) {
+                int tp = 2 * ks + (fq >> 1);
+                if (tp > 8) tp = 8;
+                const half8 bhi = *reinterpret_cast<const half8*>(xc + tp * 32);
+                const half8 blo = *reinterpret_cast<const half8*>(xc + tp * 32 + P23R_LO);
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const half8 ahi = *reinterpret_cast<const half8*>(wf + (((5 + ct * 5 + ks) * 2 + 0) * 64 + lane) * 16);
+                    const half8 alo = *reinterpret_cast<const half8*>(wf + (((5 + ct * 5 + ks) * 2 + 1) * 64 + lane) * 16);
+                    acc3[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, bhi, acc3[ct], 0, 0, 0);
+                    acc3[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, blo, acc3[ct], 0, 0, 0);
+                    acc3[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, bhi, acc3[ct], 0, 0, 0);
+                }
+            }
+            __builtin_amdgcn_wave_barrier();                // every tile read is issued before the next trip's window writes
+            // ---- heads and the epilogue of pnet23_body<false>
+            const float4v v0 = acc3[0] + b30, v1 = acc3[1] + b31;
+            half8 bh, bl;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float x0 = __builtin_fmaf(fminf(v0[e], 0.f), s30[e], v0[e]), x1 = __builtin_fmaf(fminf(v1[e], 0.f), s31[e], v1[e]);
+                const half_t h0 = (half_t)x0, h1 = (half_t)x1;
+                bh[e] = h0; bl[e] = (half_t)(x0 - (float)h0);
+                bh[4 + e] = h1; bl[4 + e] = (half_t)(x1 - (float)h1);
+            }
+            float4v d = {0.f, 0.f, 0.f, 0.f};
+            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwl, bh, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh, bl, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_16x16x32_f16(hwh, bh, d, 0, 0, 0);
+            const bool inb = fq < 2 && i0 + fr < n_list;
+            const float o0 = d[0] + hb4[0], o1 = d[1] + hb4[1];
+            const float dlv = __shfl(o1 - o0, fr, 64);
+            const bool flag = inb && fq == 0 && (split_nonfinite(dlv) || (dlv >= a.logit_thr && (!band || dlv <= a.band_hi)));
+            const unsigned long long fm = __ballot(flag);
+            if (flag) seg[nflag + (int)__builtin_popcountll(fm & ((1ull << lane) - 1ull))] = cell;
+            nflag += (int)__builtin_popcountll(fm);
+            if (inb) {
+                if (fq == 0) a.dl[cell] = o1 - o0;
+                if (band && dlv >= a.logit_thr) {
+                    float* o = a.head + (size_t)cell * 6 + 4 * fq;
+                    *reinterpret_cast<float2*>(o) = make_float2(o0, o1);
+                    if (fq == 0) *reinterpret_cast<float2*>(o + 2) = make_float2(d[2] + hb4[2], d[3] + hb4[3]);
+                }
+            }
+        }
+        if (lane == 0) a.counts[vb] = nflag;
+    }
+#endif
 }
 
 // ---------------------------------------------------------------- exact f32 re-evaluation of the cells that matter
@@ -476,22 +731,65 @@ extern "C" size_t fr_pnet23_workspace_bytes(int B, int H1, int W1) {
     return (size_t)ncell * 4 + 512 * 4 + (size_t)grid * seg_cap * 4;
 }
 
+extern "C" size_t fr_pnet23_coarse_workspace_bytes(int B, int H1, int W1) {      // [512 counts | one list segment per block]
+    if (B <= 0 || H1 < 5 || W1 < 5) return 0;
+    long long ncell, ntiles; int grid, seg_cap;
+    p23_layout(B, H1, W1, ncell, ntiles, grid, seg_cap);
+    return 512 * 4 + (size_t)grid * seg_cap * 4;
+}
+
+// blocks of the persistent re-evaluation launch over `segments` coarse lists: a wave per list, one block per CU at most
+static unsigned p23_reeval_grid(long long segments) {
+    const long long blocks = (segments + P23R_NT / 64 - 1) / (P23R_NT / 64);
+    return (unsigned)(blocks < 256 ? blocks : 256);
+}
+
+constexpr size_t P23_LDS = (size_t)2 * P23_X1PL + (size_t)2 * P23_X2PL + 30 * 1024 + 108 * 4;      // 81,584 B: two blocks per CU
+constexpr size_t P23C_LDS = (size_t)P23_X1PL + (size_t)P23_X2PL + 15 * 1024 + 108 * 4;             // 41,008 B: the coarse pass, hi planes only
+
+// One level: the split kernel over every cell (coarse == nullptr), or the coarse pass and the split re-evaluation of its list.
+static int p23_level(const char* who, const float* x1, const void* x1s, int B, int H1, int W1, const float* w2, const float* b2,
+                     const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                     const float* hb, float* head, int all_heads, float refine_logit_thr, float refine_band_hi,
+                     int32_t* refined_count, void* workspace, size_t workspace_bytes, float coarse_margin, void* coarse,
+                     size_t coarse_bytes, int32_t* visited_count, fr_stream_t stream);
+
 extern "C" int fr_pnet23_split_f16(const float* x1, const void* x1s, int B, int H1, int W1, const float* w2, const float* b2,
                                    const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
                                    const float* hb, float* head, int all_heads, float refine_logit_thr, float refine_band_hi,
                                    int32_t* refined_count, void* workspace, size_t workspace_bytes, fr_stream_t stream) {
-    FR_REQUIRE(x1 && x1s && w2 && b2 && s2 && w3 && b3 && s3 && hw && hb && head, "fr_pnet23_split_f16: null pointer");
-    FR_REQUIRE((int64_t)B * H1 * W1 * 64 < (1ll << 31), "fr_pnet23_split_f16: the split conv1 map must stay below 2 GiB (got %lld bytes)", (long long)B * H1 * W1 * 64);
-    FR_REQUIRE(B > 0 && H1 >= 5 && W1 >= 5, "fr_pnet23_split_f16: the conv1 map must be at least 5x5 (got %dx%d)", H1, W1);
+    return p23_level("fr_pnet23_split_f16", x1, x1s, B, H1, W1, w2, b2, s2, w3, b3, s3, hw, hb, head, all_heads, refine_logit_thr,
+                     refine_band_hi, refined_count, workspace, workspace_bytes, 0.f, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int fr_pnet23_coarse_f16(const float* x1, const void* x1s, int B, int H1, int W1, const float* w2, const float* b2,
+                                    const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                                    const float* hb, float* head, int all_heads, float refine_logit_thr, float refine_band_hi,
+                                    int32_t* refined_count, void* workspace, size_t workspace_bytes, float coarse_margin,
+                                    void* coarse, size_t coarse_bytes, int32_t* visited_count, fr_stream_t stream) {
+    FR_REQUIRE(!(all_heads & 1), "fr_pnet23_coarse_f16: all_heads & 1 (the approximate heads of every cell) needs fr_pnet23_split_f16");
+    FR_REQUIRE(coarse && coarse_margin >= 0.f, "fr_pnet23_coarse_f16: needs a coarse buffer and a margin >= 0");
+    return p23_level("fr_pnet23_coarse_f16", x1, x1s, B, H1, W1, w2, b2, s2, w3, b3, s3, hw, hb, head, all_heads, refine_logit_thr,
+                     refine_band_hi, refined_count, workspace, workspace_bytes, coarse_margin, coarse, coarse_bytes, visited_count, stream);
+}
+
+static int p23_level(const char* who, const float* x1, const void* x1s, int B, int H1, int W1, const float* w2, const float* b2,
+                     const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                     const float* hb, float* head, int all_heads, float refine_logit_thr, float refine_band_hi,
+                     int32_t* refined_count, void* workspace, size_t workspace_bytes, float coarse_margin, void* coarse,
+                     size_t coarse_bytes, int32_t* visited_count, fr_stream_t stream) {
+    FR_REQUIRE(x1 && x1s && w2 && b2 && s2 && w3 && b3 && s3 && hw && hb && head, "%s: null pointer", who);
+    FR_REQUIRE((int64_t)B * H1 * W1 * 64 < (1ll << 31), "%s: the split conv1 map must stay below 2 GiB (got %lld bytes)", who, (long long)B * H1 * W1 * 64);
+    FR_REQUIRE(B > 0 && H1 >= 5 && W1 >= 5, "%s: the conv1 map must be at least 5x5 (got %dx%d)", who, H1, W1);
     P23Args a;
     a.x1 = x1; a.x1s = (const unsigned char*)x1s; a.x1s_bytes = (unsigned)((int64_t)B * H1 * W1 * 64); a.w2 = w2; a.b2 = b2; a.s2 = s2; a.w3 = w3; a.b3 = b3; a.s3 = s3; a.hw = hw; a.hb = hb; a.head = head; a.all_heads = all_heads & 1;
     a.B = B; a.H1 = H1; a.W1 = W1; a.H3 = H1 - 4; a.W3 = W1 - 4;
     a.tiles_x = (a.W3 + P23_RW - 1) / P23_RW; a.tiles_y = (a.H3 + P23_RH - 1) / P23_RH;
     long long ncell, nt; int grid, seg_cap;
     p23_layout(B, H1, W1, ncell, nt, grid, seg_cap);
-    FR_REQUIRE(nt < (1ll << 31) && ncell < (1ll << 31), "fr_pnet23_split_f16: too many tiles");
+    FR_REQUIRE(nt < (1ll << 31) && ncell < (1ll << 31), "%s: too many tiles", who);
     const size_t need = fr_pnet23_workspace_bytes(B, H1, W1);
-    FR_REQUIRE(workspace && workspace_bytes >= need, "fr_pnet23_split_f16: workspace needs %zu bytes (fr_pnet23_workspace_bytes)", need);
+    FR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace needs %zu bytes (fr_pnet23_workspace_bytes)", who, need);
     a.dl = reinterpret_cast<float*>(workspace);
     a.counts = reinterpret_cast<int*>(a.dl + ncell);
     a.list = a.counts + 512;
@@ -499,12 +797,30 @@ extern "C" int fr_pnet23_split_f16(const float* x1, const void* x1s, int B, int 
     a.logit_thr = refine_logit_thr;
     a.band_hi = refine_band_hi;
     a.ntiles = (int)nt;
-    constexpr size_t lds = (size_t)2 * P23_X1PL + (size_t)2 * P23_X2PL + 30 * 1024 + 108 * 4;       // 81,584 B: two blocks per CU
-    static FrDevLatch latch;
-    if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_split_f16), lds, latch)) { fr_set_error("fr_pnet23_split_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+    a.clist = a.ccounts = a.visited = nullptr; a.coarse_thr = 0.f;
     hipStream_t s = fr_stream(stream);
-    pnet23_split_f16<<<grid, P23_NT, lds, s>>>(a);
-    FR_CHECK_LAUNCH("pnet23_split_f16");
+    if (coarse) {
+        const size_t cneed = fr_pnet23_coarse_workspace_bytes(B, H1, W1);
+        FR_REQUIRE(coarse_bytes >= cneed, "%s: the coarse buffer needs %zu bytes (fr_pnet23_coarse_workspace_bytes)", who, cneed);
+        a.ccounts = reinterpret_cast<int*>(coarse); a.clist = a.ccounts + 512;
+        a.coarse_thr = refine_logit_thr - coarse_margin; a.visited = visited_count;
+        static FrDevLatch latch0, latch1;
+        if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_coarse_f16), P23C_LDS, latch0) ||
+            !fr_raise_lds(reinterpret_cast<const void*>(pnet23_reeval_levels), P23R_LDS, latch1)) { fr_set_error("fr_pnet23_coarse_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+        pnet23_coarse_f16<<<grid, P23_NT, P23C_LDS, s>>>(a);
+        FR_CHECK_LAUNCH("pnet23_coarse_f16");
+        P23Levels t{};                                      // the level as a table of one
+        P23Coarse c{};
+        t.nlevels = 1; t.x1s[0] = a.x1s; t.head[0] = head; t.dl[0] = a.dl; t.H1[0] = H1; t.W1[0] = W1; t.seg_cap[0] = seg_cap;
+        t.first[0] = 0; t.first[1] = grid; c.buf[0] = a.ccounts;
+        pnet23_reeval_levels<<<p23_reeval_grid(grid), P23R_NT, P23R_LDS, s>>>(a, t, c);
+        FR_CHECK_LAUNCH("pnet23_reeval_levels");
+    } else {
+        static FrDevLatch latch;
+        if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_split_f16), P23_LDS, latch)) { fr_set_error("fr_pnet23_split_f16: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+        pnet23_split_f16<<<grid, P23_NT, P23_LDS, s>>>(a);
+        FR_CHECK_LAUNCH("pnet23_split_f16");
+    }
     if (all_heads & 2) return FR_OK;                        // the exact pass of every level follows in ONE launch: fr_pnet_finish_levels
     PRefArgs r;
     r.x1 = x1; r.w2 = w2; r.b2 = b2; r.s2 = s2; r.w3 = w3; r.b3 = b3; r.s3 = s3; r.hw = hw; r.hb = hb; r.head = head;
@@ -601,18 +917,48 @@ extern "C" int fr_pnet_band_tiles(const void* workspace, int B, int H1, int W1, 
 // ---------------------------------------------------------------- the pyramid-wide launches (the batch path's launch plan)
 // conv2 / conv3 / heads of every level in ONE launch; the exact pass is always deferred to fr_pnet_finish_levels.  A level's
 // workspace is that of its own fr_pnet23_split_f16 call (fr_pnet23_workspace_bytes).
+static int p23_pyramid(const char* who, const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
+                       const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                       const float* hb, int all_heads, float refine_logit_thr, float refine_band_hi, float coarse_margin,
+                       void* const* coarse, int32_t* visited_count, fr_stream_t stream);
+
 extern "C" int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
                                    const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
                                    const float* hb, int all_heads, float refine_logit_thr, float refine_band_hi, fr_stream_t stream) {
-    FR_REQUIRE(levels && nlevels > 0 && nlevels <= P23_MAXL && nframes > 0, "fr_pnet_pyramid_p23: 1 .. %d levels", P23_MAXL);
-    FR_REQUIRE(w2 && b2 && s2 && w3 && b3 && s3 && hw && hb, "fr_pnet_pyramid_p23: null pointer");
+    return p23_pyramid("fr_pnet_pyramid_p23", levels, nlevels, nframes, w2, b2, s2, w3, b3, s3, hw, hb, all_heads, refine_logit_thr,
+                       refine_band_hi, 0.f, nullptr, nullptr, stream);
+}
+
+// The coarse pass and the split re-evaluation of its lists over every level, one launch each; coarse[l]: level l's coarse buffer
+// (fr_pnet23_coarse_workspace_bytes of its shape).
+extern "C" int fr_pnet_pyramid_p23_coarse(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
+                                          const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                                          const float* hb, int all_heads, float refine_logit_thr, float refine_band_hi,
+                                          float coarse_margin, void* const* coarse, int32_t* visited_count, fr_stream_t stream) {
+    FR_REQUIRE(!(all_heads & 1), "fr_pnet_pyramid_p23_coarse: all_heads & 1 (the approximate heads of every cell) needs fr_pnet_pyramid_p23");
+    FR_REQUIRE(coarse && coarse_margin >= 0.f, "fr_pnet_pyramid_p23_coarse: needs the coarse buffers and a margin >= 0");
+    return p23_pyramid("fr_pnet_pyramid_p23_coarse", levels, nlevels, nframes, w2, b2, s2, w3, b3, s3, hw, hb, all_heads, refine_logit_thr,
+                       refine_band_hi, coarse_margin, coarse, visited_count, stream);
+}
+
+static int p23_pyramid(const char* who, const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2,
+                       const float* s2, const float* w3, const float* b3, const float* s3, const float* hw,
+                       const float* hb, int all_heads, float refine_logit_thr, float refine_band_hi, float coarse_margin,
+                       void* const* coarse, int32_t* visited_count, fr_stream_t stream) {
+    FR_REQUIRE(levels && nlevels > 0 && nlevels <= P23_MAXL && nframes > 0, "%s: 1 .. %d levels", who, P23_MAXL);
+    FR_REQUIRE(w2 && b2 && s2 && w3 && b3 && s3 && hw && hb, "%s: null pointer", who);
     P23Levels t;
+    P23Coarse c{};
     t.nlevels = nlevels;
     long long total = 0;
     for (int l = 0; l < nlevels; ++l) {
         const fr_pnet_level& L = levels[l];
-        FR_REQUIRE(L.x1s && L.head && L.workspace && L.H1 >= 5 && L.W1 >= 5, "fr_pnet_pyramid_p23: level %d: bad entry", l);
-        FR_REQUIRE((int64_t)nframes * L.H1 * L.W1 * 64 < (1ll << 31), "fr_pnet_pyramid_p23: level %d: the split conv1 map must stay below 2 GiB", l);
+        if (coarse) {
+            FR_REQUIRE(coarse[l], "%s: level %d: no coarse buffer", who, l);
+            c.buf[l] = reinterpret_cast<int*>(coarse[l]);
+        }
+        FR_REQUIRE(L.x1s && L.head && L.workspace && L.H1 >= 5 && L.W1 >= 5, "%s: level %d: bad entry", who, l);
+        FR_REQUIRE((int64_t)nframes * L.H1 * L.W1 * 64 < (1ll << 31), "%s: level %d: the split conv1 map must stay below 2 GiB", who, l);
         long long ncell, nt; int grid, seg_cap;
         p23_layout(nframes, L.H1, L.W1, ncell, nt, grid, seg_cap);
         t.x1s[l] = reinterpret_cast<const unsigned char*>(L.x1s); t.head[l] = L.head; t.dl[l] = reinterpret_cast<float*>(L.workspace);
@@ -624,10 +970,20 @@ extern "C" int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int
     P23Args a{};
     a.w2 = w2; a.b2 = b2; a.s2 = s2; a.w3 = w3; a.b3 = b3; a.s3 = s3; a.hw = hw; a.hb = hb; a.all_heads = all_heads & 1;
     a.logit_thr = refine_logit_thr; a.band_hi = refine_band_hi; a.B = nframes;
-    constexpr size_t lds = (size_t)2 * P23_X1PL + (size_t)2 * P23_X2PL + 30 * 1024 + 108 * 4;
+    if (coarse) {
+        a.coarse_thr = refine_logit_thr - coarse_margin; a.visited = visited_count;
+        static FrDevLatch latch0, latch1;
+        if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_coarse_levels), P23C_LDS, latch0) ||
+            !fr_raise_lds(reinterpret_cast<const void*>(pnet23_reeval_levels), P23R_LDS, latch1)) { fr_set_error("fr_pnet_pyramid_p23_coarse: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+        pnet23_coarse_levels<<<(unsigned)total, P23_NT, P23C_LDS, fr_stream(stream)>>>(a, t, c);
+        FR_CHECK_LAUNCH("pnet23_coarse_levels");
+        pnet23_reeval_levels<<<p23_reeval_grid(total), P23R_NT, P23R_LDS, fr_stream(stream)>>>(a, t, c);
+        FR_CHECK_LAUNCH("pnet23_reeval_levels");
+        return FR_OK;
+    }
     static FrDevLatch latch;
-    if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_split_levels), lds, latch)) { fr_set_error("fr_pnet_pyramid_p23: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
-    pnet23_split_levels<<<(unsigned)total, P23_NT, lds, fr_stream(stream)>>>(a, t);
+    if (!fr_raise_lds(reinterpret_cast<const void*>(pnet23_split_levels), P23_LDS, latch)) { fr_set_error("fr_pnet_pyramid_p23: cannot raise dynamic LDS"); return FR_E_LAUNCH; }
+    pnet23_split_levels<<<(unsigned)total, P23_NT, P23_LDS, fr_stream(stream)>>>(a, t);
     FR_CHECK_LAUNCH("pnet23_split_levels");
     return FR_OK;
 }

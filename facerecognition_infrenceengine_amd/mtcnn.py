@@ -156,6 +156,13 @@ class DetectSettings:
     # tail layers as split-precision GEMMs (csrc/ro_gemm.hip); the crops whose logit lies within ``ro_margin`` of the stage
     # threshold are re-evaluated by the all-f32 layers, so every keep / reject decision is that of f32 arithmetic
     split_ro = True
+    # The batch path's conv2 / conv3 / heads in two tiers (csrc/pnet_fused.hip): a coarse pass over every cell with the hi halves of the
+    # split operands only (one MFMA per product instead of three), then the split-precision form over just the cells whose coarse logit
+    # difference is within ``coarse_margin`` of the exact pass's pre-filter (~1 %) - which then carry the bits the one-tier kernel gives
+    # them; no other cell's value is ever read beyond "below the pre-filter".  With pnet_band only; False: the one-tier split kernel.
+    coarse_p23 = True
+    coarse_margin = 0.05            # in logit units; >= 20x the hi-only format's error inside the envelope of DESIGN.md 4.3a
+    visited_cells = None            # optional device int32[1]: cells the second tier re-evaluated (diagnostics)
 
     def __init__(self, minsize=20, factor=0.709, fused_pnet=True, batch_min_pixels=None):
         self.minsize, self.factor = minsize, factor
@@ -187,6 +194,7 @@ class DetectPlan(NamedTuple):
     cache: bool         # the work tensors of the last call of this frame shape are used again ...
     recorder: bool      # ... and the call may be recorded and replayed as one C call list
     split: bool         # R-/O-Net on the f16 matrix cores + exact pass at the thresholds
+    coarse: float       # the fused P-Net in two tiers: the coarse pass's margin (> 0), or 0.0 - the one-tier split kernel
     chunks: tuple       # ((first frame, end frame), ...) when the call must be cut into groups of frames, else ()
 
 
@@ -221,7 +229,8 @@ def detect_plan(N, H, W, cfg, trace=False, level_streams=None, out=False, captur
 
 
 _PLAN_READS = ("minsize", "factor", "fused_pnet", "batch_min_pixels", "solo_max_frames", "pnet_band", "split_pconv1", "split_pconv1_min_px",
-               "pyramid_launch", "one_stream", "level_streams", "single_frame_level_streams", "split_ro", "fused_crop", "use_sequence")
+               "pyramid_launch", "one_stream", "level_streams", "single_frame_level_streams", "split_ro", "fused_crop", "use_sequence",
+               "coarse_p23", "coarse_margin")
 
 
 @functools.lru_cache(maxsize=256)
@@ -262,7 +271,8 @@ def _plan(N, H, W, settings, recordable, trace, level_streams, out, capturing):
     # streams) would not honour.
     recorder = bool(cache and recordable and cfg.use_sequence and cfg.fused_pnet and cfg.fused_crop and not cfg.one_stream)
     split = bool(cfg.split_ro and cfg.fused_crop and batch and not trace)
-    return DetectPlan(N, scales, geo, batch, few, band, fused, f16, pyramid, eager or pyramid, nside, cache, recorder, split, chunks)
+    coarse = float(cfg.coarse_margin) if cfg.coarse_p23 and band else 0.0
+    return DetectPlan(N, scales, geo, batch, few, band, fused, f16, pyramid, eager or pyramid, nside, cache, recorder, split, coarse, chunks)
 
 
 # What differs between R-Net / stage 2 and O-Net / stage 3; the row index is the kernels' net id and picks the stage's threshold
@@ -442,16 +452,22 @@ class MTCNNHIP(DetectSettings):
         lt = math.log(self.thresholds[0] / (1.0 - self.thresholds[0]))
         return lt - self.refine_margin, lt + self.refine_margin if band else float("-inf")
 
-    def _level_buffers(self, N, scale, geo, band, f16, cand):
+    def _coarse(self, margin):
+        """The coarse pass's margin for this call's fused levels, or 0.0: ``p23_all_heads`` asks for the split heads of every cell."""
+        return 0.0 if self.p23_all_heads else margin
+
+    def _level_buffers(self, N, scale, geo, band, f16, cand, coarse=0.0):
         """The work tensors of one fused P-Net level - the split-f16 copy ``xs`` of conv1's map, the f32 map ``x`` (a level with ``f16``:
         SPARSE, written only in the 16 x 64-pixel tiles the band-tile list names, where the exact pass needs a 5x5 window, uninitialised
         elsewhere), the heads, the fused kernel's workspace, the candidate kernel's block counts - as a dict (``level_tensors``), and the
-        level's fr_pnet_level entry; cand: its candidate list (boxes, scores, regs, counts) or None.  Notes the level in ``_tls.path``."""
+        level's fr_pnet_level entry; cand: its candidate list (boxes, scores, regs, counts) or None.  coarse: the level runs in two tiers and
+        gets the coarse pass's buffer ``cws`` too.  Notes the level in ``_tls.path``."""
         hs, ws, h, w = geo
         path = getattr(self._tls, "path", None)
         if path is not None:
             path["fused_levels"] += 1
             path["band_levels"] += int(band)
+            path["coarse_levels"] += int(coarse > 0.0)
             if f16:
                 path["pconv1_mfma_levels"].append((h, w))
         xs = self._new((N, h, w, 64), torch.uint8)
@@ -459,13 +475,14 @@ class MTCNNHIP(DetectSettings):
         head = self._f32(N, h - 4, w - 4, 6)
         wsp = self._new((self.lib.fr_pnet23_workspace_bytes(N, h, w) // 4,), torch.float32)
         bc = self._i32(N * (-(-(h - 4) * (w - 4) // 256)))
+        cws = self._i32(self.lib.fr_pnet23_coarse_workspace_bytes(N, h, w) // 4) if coarse > 0.0 else None
         entry = None
         if cand is not None:
             entry = _lib.PnetLevel(x.data_ptr(), head.data_ptr(), wsp.data_ptr(), h, w, float(scale), *[t.data_ptr() for t in cand],
                                    bc.data_ptr(), xs.data_ptr(), hs, ws, int(f16))
-        return dict(h=h, w=w, f16=f16, x=x, xs=xs, head=head, wsp=wsp, bc=bc), entry
+        return dict(h=h, w=w, f16=f16, x=x, xs=xs, head=head, wsp=wsp, bc=bc, cws=cws), entry
 
-    def _level(self, frames, scale, geo, fused, band, f16, trace, cand):
+    def _level(self, frames, scale, geo, fused, band, f16, trace, cand, coarse=0.0):
         """One pyramid level's P-Net -> (head, hc, wc, bc, dl, dl_min, keep): the heads f32 [N,hc,wc,6]; the block counts,
         logit-difference map and pre-filter for fr_pnet_candidates; keep: None, or - the level has extracted its candidates itself
         (``f16``) - its tensors (x, xs, head, wsp, tbuf, tiles, bc), to be kept alive until the level's stream has been joined."""
@@ -486,16 +503,22 @@ class MTCNNHIP(DetectSettings):
             head, h, w = self._dconv(x, self.p3, N, h, w)
             return head, h, w, self._i32(N * (-(-h * w // 256))), None, 0.0, None
         lo, hi = self._band_logits(band)
-        t, entry = self._level_buffers(N, scale, geo, band, f16, cand[3:] if f16 else None)
-        x, xs, head, wsp = t["x"], t["xs"], t["head"], t["wsp"]
+        coarse = self._coarse(coarse)
+        t, entry = self._level_buffers(N, scale, geo, band, f16, cand[3:] if f16 else None, coarse)
+        x, xs, head, wsp, cws = t["x"], t["xs"], t["head"], t["wsp"], t["cws"]
         p1w, p23 = (_lib.ptr(p1.w), _lib.ptr(p1.b), _lib.ptr(p1.slope)), [_lib.ptr(v) for v in self._p23]
         if f16:         # conv1 on the f16 matrix cores: the split map only (csrc/pnet_conv1.hip F16)
             lib.fr_pnet_conv1_band(0, self._fptr(frames), N, H, W, hs, ws, *p1w, None, _lib.ptr(xs), None, None, 0, self._s)
         else:
             self._dconv(None, p1, N, hs, ws, frames=frames, y_split=xs, y=x)
-        lib.fr_pnet23_split_f16(_lib.ptr(x), _lib.ptr(xs), N, h, w, *p23, _lib.ptr(head),
-                                (1 if (self.p23_all_heads or trace is not None) else 0) | (2 if f16 else 0), lo, hi,
-                                _lib.ptr(self.refined_cells), _lib.ptr(wsp), wsp.numel() * 4, self._s)
+        if coarse > 0.0:
+            lib.fr_pnet23_coarse_f16(_lib.ptr(x), _lib.ptr(xs), N, h, w, *p23, _lib.ptr(head), 2 if f16 else 0, lo, hi,
+                                     _lib.ptr(self.refined_cells), _lib.ptr(wsp), wsp.numel() * 4, coarse, _lib.ptr(cws), cws.numel() * 4,
+                                     _lib.ptr(self.visited_cells), self._s)
+        else:
+            lib.fr_pnet23_split_f16(_lib.ptr(x), _lib.ptr(xs), N, h, w, *p23, _lib.ptr(head),
+                                    (1 if (self.p23_all_heads or trace is not None) else 0) | (2 if f16 else 0), lo, hi,
+                                    _lib.ptr(self.refined_cells), _lib.ptr(wsp), wsp.numel() * 4, self._s)
         keep = None
         if f16:         # -> the conv1 tiles under the band cells' windows, EXACTLY (LIST) -> the exact pass + the candidates
             nt = lib.fr_pnet_band_tiles_count(N, h, w)
@@ -504,7 +527,7 @@ class MTCNNHIP(DetectSettings):
             lib.fr_pnet_conv1_band(1, self._fptr(frames), N, H, W, hs, ws, *p1w, _lib.ptr(x), None, _lib.ptr(tiles), _lib.ptr(tbuf), nt, self._s)
             lib.fr_pnet_finish_levels((_lib.PnetLevel * 1)(entry), 1, N, *p23, cand[1], cand[2], lo, _lib.ptr(self.refined_cells), self._s)
             t.update(tbuf=tbuf, tiles=tiles)
-            keep = (x, xs, head, wsp, tbuf, tiles, t["bc"])
+            keep = (x, xs, head, wsp, tbuf, tiles, t["bc"])      # (cws: read by the two launches above only, on the stream it was allocated on)
         if self.level_tensors is not None:
             self.level_tensors.append(t)
         return head, h - 4, w - 4, t["bc"], wsp, lo, keep
@@ -519,7 +542,8 @@ class MTCNNHIP(DetectSettings):
         fused = bool(self.fused_pnet) and N <= _frames32(*geo[2:])
         band = bool(self.pnet_band and _is_batch(self, N, H, W) and trace is None)
         f16 = fused and cand is not None and _f16_conv1(self, band, *geo[2:])
-        head, hc, wc, _, dl, dl_min, keep = self._level(frames, scale, geo, fused, band, f16, trace, cand)
+        coarse = self.coarse_margin if self.coarse_p23 and band else 0.0
+        head, hc, wc, _, dl, dl_min, keep = self._level(frames, scale, geo, fused, band, f16, trace, cand, coarse)
         self._tls.dl, self._tls.level_done, self._tls.keep = (dl, dl_min), keep is not None, keep
         return head, hc, wc
 
@@ -533,16 +557,20 @@ class MTCNNHIP(DetectSettings):
         lib, p1, nlev = self.lib, self.p1, len(plan.scales)
         lo, hi = self._band_logits(plan.band)
         lv = (_lib.PnetLevel * nlev)()
-        keep, ntile, words = [], 0, 0
+        keep, ntile, words, coarse = [], 0, 0, self._coarse(plan.coarse)
         for li, (s, geo, f16) in enumerate(zip(plan.scales, plan.geo, plan.f16)):
-            t, lv[li] = self._level_buffers(N, s, geo, plan.band, f16, [c[li] for c in cand])
+            t, lv[li] = self._level_buffers(N, s, geo, plan.band, f16, [c[li] for c in cand], coarse)
             keep.append(t)
             if f16:
                 nt = lib.fr_pnet_band_tiles_count(N, t["h"], t["w"])
                 ntile, words = ntile + nt, words + (nt + 31) // 32
         p1w, p23 = (_lib.ptr(p1.w), _lib.ptr(p1.b), _lib.ptr(p1.slope)), [_lib.ptr(t) for t in self._p23]
         lib.fr_pnet_pyramid_conv1(0, self._fptr(frames), N, H, W, lv, nlev, *p1w, None, None, 0, self._s)
-        lib.fr_pnet_pyramid_p23(lv, nlev, N, *p23, 1 if self.p23_all_heads else 0, lo, hi, self._s)
+        if coarse > 0.0:
+            cws = (ctypes.c_void_p * nlev)(*[t["cws"].data_ptr() for t in keep])
+            lib.fr_pnet_pyramid_p23_coarse(lv, nlev, N, *p23, 0, lo, hi, coarse, cws, _lib.ptr(self.visited_cells), self._s)
+        else:
+            lib.fr_pnet_pyramid_p23(lv, nlev, N, *p23, 1 if self.p23_all_heads else 0, lo, hi, self._s)
         if ntile:
             tbuf, tiles = self._i32(1 + words), self._i32(ntile)
             lib.fr_pnet_pyramid_band_tiles(lv, nlev, N, _lib.ptr(tbuf), _lib.ptr(tiles), self._s)
@@ -599,7 +627,7 @@ class MTCNNHIP(DetectSettings):
                     lcand = [c[li] for c in cand]
                     head, hc, wc, bc, dl, dl_min, done = self._level(
                         frames, s, plan.geo[li], plan.fused[li], plan.band, plan.f16[li], trace,
-                        (float(s), t0, cs, *lcand) if plan.batch and trace is None else None)
+                        (float(s), t0, cs, *lcand) if plan.batch and trace is None else None, plan.coarse)
                     prob = self._f32(N, hc, wc) if trace is not None else None
                     if done is not None:                            # the level extracted its candidates itself
                         keep.append(done)
@@ -792,7 +820,7 @@ class MTCNNHIP(DetectSettings):
         known = key in caches
         tls.cache = [caches.setdefault(key, []), 0]
         cfg = (self.fused_pnet, self.fused_crop, self.p23_all_heads, self.thresholds, self.refine_margin,
-               self.cap_scale, self.keep_scale, self.cap_p, self.cap_r, self.cap_o, self.minsize, self.factor)
+               self.cap_scale, self.keep_scale, self.cap_p, self.cap_r, self.cap_o, self.minsize, self.factor, self.coarse_p23, self.coarse_margin)
         seq = seqs.get(key)
         if seq is not None and (not plan.recorder or seq["cfg"] != cfg):
             seqs.pop(key)                                   # recorded under another configuration: never replayed again
@@ -836,7 +864,7 @@ class MTCNNHIP(DetectSettings):
         Returns device tensors: boxes f32 [N,cap_o,4], scores f32 [N,cap_o], kps f32 [N,cap_o,5,2],
         counts i32 [N] (faces per frame, in descending-score order).
 
-        ``_tls.path`` (this thread's last call): which arithmetic ran - {"frames", "batch", "chunks", "fused_levels", "band_levels",
+        ``_tls.path`` (this thread's last call): which arithmetic ran - {"frames", "batch", "chunks", "fused_levels", "band_levels", "coarse_levels" [fused levels run in two tiers, ``coarse_p23``],
         "pconv1_mfma_levels" [(h, w) of the conv1 maps computed on the f16 matrix cores], "unfused_levels", "split_ro",
         "exact_lists" [(net, list capacity) of every exact R-/O-Net pass, all chunks]} - so that a test can assert the path it means
         to test was the one taken (the decisions are ``detect_plan``'s); ``exact_lists()`` / ``exact_list_overflow()`` read the lists' counters."""
@@ -845,7 +873,7 @@ class MTCNNHIP(DetectSettings):
         with torch.cuda.device(self.device):
             plan = detect_plan(N, H, W, self, trace is not None, level_streams, _out is not None, torch.cuda.is_current_stream_capturing())
             if _out is None:
-                self._tls.path = {"frames": N, "batch": plan.batch, "chunks": max(1, len(plan.chunks)), "fused_levels": 0, "band_levels": 0,
+                self._tls.path = {"frames": N, "batch": plan.batch, "chunks": max(1, len(plan.chunks)), "fused_levels": 0, "band_levels": 0, "coarse_levels": 0,
                                   "pconv1_mfma_levels": [], "unfused_levels": 0, "split_ro": False, "exact_lists": []}
                 self._tls.exact_counters = []       # device counters of the exact lists of path["exact_lists"] (no sync here)
             if plan.chunks:

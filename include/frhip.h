@@ -44,6 +44,7 @@ typedef void* fr_stream_t;
  * _workspace functions (the grouped view scan of mixed-company batches), and for fr_gallery_pairs_above_f16 /
  * fr_gallery_pairs_workspace (the gallery audit), and for fr_yuv420_to_bgr_u8 / fr_yuv420_to_bgr_refs_u8 (YUV 4:2:0 frame ingest),
  * and for fr_frame_activity_u8 / fr_frame_activity_refs_u8 (the activity gate in front of the engine pass),
+ * and for fr_pnet23_coarse_f16 / fr_pnet23_coarse_workspace_bytes / fr_pnet_pyramid_p23_coarse (the P-Net's coarse pass),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -641,6 +642,21 @@ int fr_pnet23_split_f16(const float* x1, const void* x1s, int B, int H1, int W1,
                         const float* w3, const float* b3, const float* s3, const float* hw, const float* hb,
                         float* head, int all_heads, float refine_logit_thr, float refine_band_hi, int32_t* refined_count,
                         void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* The same post-state as fr_pnet23_split_f16 - dl, head rows, per-block lists and counts, the exact pass unless all_heads & 2 -
+ * in two tiers: a COARSE pass over every cell with the hi halves of the operands only (one MFMA per product, no lo plane moved),
+ * which writes its logit difference and lists every cell with dl >= refine_logit_thr - coarse_margin or a non-finite dl, and the
+ * split-precision re-evaluation of the listed cells with the operand composition of fr_pnet23_split_f16, whose bits they then
+ * carry.  Every cell fr_pnet23_split_f16 would list, or write a head row for, is re-evaluated while coarse_margin >= the hi-only
+ * format's error of dl; the other cells hold a dl < refine_logit_thr, which is all that is ever asked of them.
+ * coarse_margin = INFINITY re-evaluates every cell.  all_heads & 1 is refused (FR_E_INVALID): the approximate heads of every
+ * cell are the split kernel's business.  coarse: fr_pnet23_coarse_workspace_bytes(B, H1, W1) bytes = [512 counts | the blocks'
+ * coarse list segments].  visited_count (optional device i32, accumulated): cells on the coarse lists. */
+size_t fr_pnet23_coarse_workspace_bytes(int B, int H1, int W1);
+int fr_pnet23_coarse_f16(const float* x1, const void* x1s, int B, int H1, int W1, const float* w2, const float* b2, const float* s2,
+                         const float* w3, const float* b3, const float* s3, const float* hw, const float* hb,
+                         float* head, int all_heads, float refine_logit_thr, float refine_band_hi, int32_t* refined_count,
+                         void* workspace, size_t workspace_bytes, float coarse_margin, void* coarse, size_t coarse_bytes,
+                         int32_t* visited_count, fr_stream_t stream);
 /* max pool, ceil mode, f32 NHWC */
 int fr_maxpool_f32(const float* x, float* y, int B, int H, int W, int C, int k, int stride,
                    fr_stream_t stream);
@@ -724,6 +740,12 @@ int fr_pnet_pyramid_p23(const fr_pnet_level* levels, int nlevels, int nframes, c
                         const float* w3, const float* b3, const float* s3, const float* hw, const float* hb, int all_heads,
                         float refine_logit_thr, float refine_band_hi, fr_stream_t stream);
 int fr_pnet_pyramid_band_tiles(const fr_pnet_level* levels, int nlevels, int nframes, int32_t* tbuf, int32_t* tiles, fr_stream_t stream);
+/* fr_pnet_pyramid_p23 in the two tiers of fr_pnet23_coarse_f16, one launch each over all levels: the same post-state.
+ * coarse[l]: level l's coarse buffer (fr_pnet23_coarse_workspace_bytes(nframes, H1, W1) bytes), beside the level table. */
+int fr_pnet_pyramid_p23_coarse(const fr_pnet_level* levels, int nlevels, int nframes, const float* w2, const float* b2, const float* s2,
+                               const float* w3, const float* b3, const float* s3, const float* hw, const float* hb, int all_heads,
+                               float refine_logit_thr, float refine_band_hi, float coarse_margin, void* const* coarse,
+                               int32_t* visited_count, fr_stream_t stream);
 
 /* det_size: the detection canvas of insightface's FaceAnalysis.prepare(det_size=(dw, dh)) (the reference's prepare(ctx_id=0)
  * means 640 x 640, infrenceServer.py:416).  ONE launch for a ragged batch: frame f of `refs` is resized to refs[f].nh x
