@@ -378,7 +378,7 @@ class FaceAnalysis:
         return out
 
     def detect_embed_slots(self, frames, det_stream=None, ready_event=None, compact_embed=False, crops_out=None,
-                           table=None, det_scale=None):
+                           table=None, det_scale=None, tracks=None, camera_ids=None):
         """Sync-free form for streaming/serving: every frame owns ``cap_o`` face slots.
 
         frames: uint8 [N,H,W,3] BGR on the device; with ``det_size`` also a list of [Hi,Wi,3] device frames of any sizes,
@@ -398,9 +398,24 @@ class FaceAnalysis:
         8 cameras x 16 slots with a face or two each would otherwise pay for 128 embeddings.
 
         crops_out: f16 [N*cap,112,112,8] (a slice of a larger buffer): detect + align only - the aligned crops land there, the
-        returned dict holds the detector outputs, and the caller runs ``embed_slots`` over the whole buffer."""
+        returned dict holds the detector outputs, and the caller runs ``embed_slots`` over the whole buffer.
+
+        tracks: a ``tracks.FaceTracks`` with ``camera_ids`` (one per frame, none repeated), only with ``compact_embed``: behind
+        the detector one launch decides which detections are faces the camera's tracks hold an embedding for, the copy of the
+        face counts carries that verdict along (no second sync), align and embed run for the others only, and a second launch
+        fills the carried rows from the bank and stores the new ones.  The dict gains ``track_id`` and ``carried`` i32 [N,cap]."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
+        if tracks is not None:
+            if not compact_embed or crops_out is not None:
+                raise ValueError("tracks need compact_embed=True: the carried faces are left out of the embed pass on the host")
+            if camera_ids is None:
+                raise ValueError("tracks need camera_ids: one camera id per frame")
+            camera_ids = list(camera_ids)
+            if len(set(camera_ids)) != len(camera_ids):
+                raise ValueError("a camera id is repeated in one call")
+        elif camera_ids is not None:
+            raise ValueError("camera_ids come with tracks (tracks=FaceTracks(...))")
         cur = torch.cuda.current_stream(self.device)
         if ready_event is not None:
             (det_stream if det_stream is not None else cur).wait_event(ready_event)
@@ -417,8 +432,31 @@ class FaceAnalysis:
         N = src.n if src is not None else frames.shape[0]
         cap = boxes.shape[1]
         if compact_embed:
-            cnt = counts.cpu()                                            # the extra sync
-            sel = (torch.arange(cap)[None, :] < cnt[:, None]).reshape(-1).nonzero().squeeze(1).to(self.device)
+            if tracks is None:
+                cnt = counts.cpu()                                        # the extra sync
+                sel = (torch.arange(cap)[None, :] < cnt[:, None]).reshape(-1).nonzero().squeeze(1).to(self.device)
+            else:
+                if len(camera_ids) != N:
+                    raise ValueError(f"one camera id per frame: {N} frames, {len(camera_ids)} ids")
+                with torch.cuda.device(self.device):
+                    entry, need, tid = tracks.associate_device(boxes, counts, camera_ids)
+                    both = torch.cat([counts.reshape(N, 1), need, entry], dim=1).cpu()   # the same one sync, a wider row
+                cnt, need_h = both[:, 0], both[:, 1:1 + cap]
+                tracks.count(cnt.numpy(), need_h.numpy(), both[:, 1 + cap:].numpy())
+                sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (need_h != 0)).reshape(-1).nonzero().squeeze(1).to(self.device)
+            if tracks is not None:
+                # the associate launch has moved the state: should align or embed fail, the bank misses this turn's rows, and no
+                # track of these cameras may be carried from it
+                try:
+                    emb, normed = self._embed_selected(frames, src, kps, sel, N, cap)
+                    with torch.cuda.device(self.device):
+                        tracks.commit_device(entry, need, counts, camera_ids, emb, normed)
+                        carried = ((need == 0) & (entry >= 0)).to(torch.int32)   # a slot past the count has entry -1
+                except BaseException:
+                    tracks.reset(camera_ids)
+                    raise
+                return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
+                        "normed_embedding": normed, "track_id": tid, "carried": carried}
             emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
             emb[:, 0] = 1.0                                               # empty slots: a unit vector, never NaN downstream
             normed = emb.clone()
@@ -445,6 +483,23 @@ class FaceAnalysis:
             emb, normed = self.rec.forward(crops)
         return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
                 "normed_embedding": normed}
+
+    def _embed_selected(self, frames, src, kps, sel, N, cap):
+        """The ``compact_embed`` pass of ``detect_embed_slots`` over the slots ``sel`` (a device index): slot-layout (embedding,
+        normed_embedding) f32 [N*cap,512], unit vectors in the rows that are not selected."""
+        emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
+        emb[:, 0] = 1.0                                                   # never NaN downstream
+        normed = emb.clone()
+        if sel.numel():
+            with torch.cuda.device(self.device):
+                F = sel.numel()
+                crops = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
+                kps_sel = kps.reshape(-1, 5, 2)[sel].contiguous()         # named, not inline (see detect_embed_slots)
+                frame_idx = (sel // cap).to(torch.int32)
+                self._warp_faces(frames, src, kps_sel, frame_idx, F, crops)
+                e, nm = self.rec.forward(crops)
+                emb[sel], normed[sel] = e, nm
+        return emb, normed
 
     def embed_slots(self, crops):
         """Second half of ``detect_embed_slots(..., crops_out=...)``: ONE embed forward over the aligned crops of several

@@ -37,20 +37,35 @@ class _Unchanged:
 UNCHANGED = _Unchanged()
 
 
-def _check_gate(gate, camera_ids, n):
-    """The camera ids of a gated call as a list (None without a gate); ValueError before anything runs."""
-    if gate is None:
+def _check_gate(gate, camera_ids, n, tracks=None):
+    """The camera ids of a gated or tracked call as a list (None without gate and tracks: one list serves both);
+    ValueError before anything runs."""
+    if gate is None and tracks is None:
         if camera_ids is not None:
-            raise ValueError("camera_ids come with a gate (gate=ActivityGate(...))")
+            raise ValueError("camera_ids come with a gate (gate=ActivityGate(...)) or with tracks (tracks=FaceTracks(...))")
         return None
     if camera_ids is None:
-        raise ValueError("a gate needs camera_ids: one camera id per frame")
+        raise ValueError(("a gate needs" if gate is not None else "tracks need") + " camera_ids: one camera id per frame")
     ids = list(camera_ids)
     if len(ids) != n:
         raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
     if len(set(ids)) != len(ids):
         raise ValueError("a camera id is repeated in one call")
     return ids
+
+
+def _track_columns(r):
+    """Host copies of the slot results' ``track_id`` and ``carried`` [n,cap], (None, None) for a call without tracks."""
+    if "track_id" not in r:
+        return None, None
+    return r["track_id"].cpu().numpy(), r["carried"].cpu().numpy()
+
+
+def _tracked(face, tid, carried, f, j):
+    """The face dict with ``track_id`` (-1: untracked) and ``tracked`` (True: its embedding was carried); as it is without tracks."""
+    if tid is not None:
+        face["track_id"], face["tracked"] = int(tid[f, j]), bool(carried[f, j])
+    return face
 
 
 def _spread(out, keep, n):
@@ -391,7 +406,8 @@ class FaceRecognitionProcessor:
             self.initialize_detector()
         return getattr(self.face_detector, "det_size", None) is not None
 
-    def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
+    def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
+                    tracks=None):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
         no company has a gallery (nothing is run, a gate is not consulted), else (n, slot results, view_set, metadatas,
@@ -411,7 +427,7 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", c)
         if all(v is None for v in index_of):
             return None
-        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks)
         if keep is not None:                      # the views of the active frames' companies, as a call on those frames has them
             company_ids = [company_ids[f] for f in keep]
             if r is not None:
@@ -431,8 +447,10 @@ class FaceRecognitionProcessor:
             idx, score = scan(view_set, index_of)
         return n, r, view_set, metadatas, index_of, idx, score, keep
 
-    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
-        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids)
+    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
+                               tracks=None):
+        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
+                               tracks=tracks)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score, keep = got
@@ -444,29 +462,31 @@ class FaceRecognitionProcessor:
         idx, score, dec = (t.cpu().numpy().reshape(n, cap) for t in (idx, score, dec))
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
+        tid, carried = _track_columns(r)
         out = []
         for f in range(n):
             if index_of[f] is None:
                 out.append(None)
                 continue
             ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], ids, metadata)
-                        for j in range(int(counts[f]))])
+            out.append([_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], ids, metadata),
+                                 tid, carried, f, j) for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
     def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601", gate=None,
-                       camera_ids=None):
+                       camera_ids=None, tracks=None):
         """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
         list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
         whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``,
-        ``gate`` / ``camera_ids``: as ``recognize_batch``."""
+        ``gate`` / ``tracks`` / ``camera_ids``: as ``recognize_batch``."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
-        camera_ids = _check_gate(gate, camera_ids, len(frames))
+        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
-        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids)
+        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
+                               tracks=tracks)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score, keep = got
@@ -477,17 +497,18 @@ class FaceRecognitionProcessor:
         idx, score = idx.cpu().numpy().reshape(n, cap, -1), score.cpu().numpy().reshape(n, cap, -1)
         bbox = r["bbox"].cpu().numpy().astype(int)
         dscore = r["det_score"].cpu().numpy()
+        tid, carried = _track_columns(r)
         out = []
         for f in range(n):
             if index_of[f] is None:
                 out.append(None)
                 continue
             pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_face_candidates(bbox[f, j], dscore[f, j], idx[f, j], score[f, j], pids, metadata, min_score)
-                        for j in range(int(counts[f]))])
+            out.append([_tracked(_face_candidates(bbox[f, j], dscore[f, j], idx[f, j], score[f, j], pids, metadata, min_score),
+                                 tid, carried, f, j) for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
-    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
+    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -515,17 +536,24 @@ class FaceRecognitionProcessor:
         active frames are what this call returns, without a gate, for exactly those frames with their company ids, in
         order.  They are not the full batch's bits: the embed net's small-batch modes sum in another order, and a gated
         turn embeds fewer faces.  With no frame active nothing but the upload and the gate runs.  When the company has no
-        gallery the None of the ungated call comes first: the gate is not consulted and its state does not move."""
-        camera_ids = _check_gate(gate, camera_ids, len(frames))
+        gallery the None of the ungated call comes first: the gate is not consulted and its state does not move.
+
+        ``tracks`` (a ``tracks.FaceTracks``) with the same ``camera_ids``: a face that the camera's previous frame showed at
+        nearly the same place, alone, keeps the embedding it was given then for up to ``max_reuse`` turns and skips align and
+        the embed net; the held embedding goes through THIS call's scan and decision, so the identity is never cached.  Each
+        face dict gains ``"track_id"`` (int, -1: untracked) and ``"tracked"`` (True: carried).  With a gate too, a frame
+        answered ``UNCHANGED`` never reaches the tracks and its camera's track state does not move; nor does it when the
+        company has no gallery."""
+        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
         if isinstance(company_id, (list, tuple)):
-            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids)
+            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
         if len(matcher) == 0:
             logger.warning("No embeddings found for company %s", company_id)
             return None
-        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks)
         if r is None:                                                        # no frame active
             return [UNCHANGED] * len(frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
@@ -536,10 +564,11 @@ class FaceRecognitionProcessor:
         idx, score, dec = (t.cpu().numpy().reshape(n, cap) for t in (idx, score, dec))
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
+        tid, carried = _track_columns(r)
         out = []
         for f in range(n):
-            out.append([_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], matcher.ids, metadata)
-                        for j in range(int(counts[f]))])
+            out.append([_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], matcher.ids, metadata),
+                                 tid, carried, f, j) for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
     def annotate(self, frame, results):
@@ -781,7 +810,7 @@ def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601"):
     return n, r
 
 
-def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None):
+def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None):
     """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
     ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape and pixel format) -> copy
     stream -> ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
@@ -794,7 +823,10 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
     their indices, the frame count and the slot results are theirs (a device gather of the frames; under ``det_size`` the
     selected rows of the ring's frame table and of ``det_scale``, no frame bytes move).  With none active the slot results are
     None and nothing but the upload and the gate has run.  ``keep`` None: every frame, the ring's tensors as they are - the code
-    path of a call without a gate."""
+    path of a call without a gate.
+
+    ``tracks`` (``tracks.FaceTracks``) with ``camera_ids``: handed to the engine pass with the camera ids of the frames that
+    reach it - all of them, or with a gate the kept ones, so a frame judged inactive never moves its camera's tracks."""
     import torch
     from .colour import check_pixel_format, check_yuv_shape
     from .ingest import FrameIngest, RaggedIngest
@@ -852,6 +884,8 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
                 else:                                 # the arena stays where it is: the table's rows name the active frames
                     ragged = {"table": ragged["table"].view(-1, 32).index_select(0, sel).reshape(-1),
                               "det_scale": ragged["det_scale"].index_select(0, sel)}
+        if tracks is not None:
+            ragged = dict(ragged, tracks=tracks, camera_ids=camera_ids if keep is None else [camera_ids[f] for f in keep])
         r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, **ragged)    # results go to the host anyway
         ring.release(turn)
     return n, r, keep

@@ -1,0 +1,167 @@
+"""Face tracks: carry a face's embedding from one frame of a camera to the next and embed only the faces that are new.
+
+In an active frame nearly every face is one the previous frame of the same camera already showed, a few pixels away, and
+``recognize_batch`` pushes it through align and the embed net again to get the same row of the gallery.  ``FaceTracks`` keeps,
+per camera and on the device, the boxes of the faces last seen and the embedding each was last given; between detect and
+align one launch decides per detection whether it is such a face (csrc/face_tracks.hip; the rule: include/frhip.h
+fr_track_associate_f32), the embed net runs for the others only, and a second launch moves rows between the
+batch's embeddings and the bank.  What is held is the embedding, never the identity: a carried face goes through the gallery
+scan of the current call like any other row, so syncs, evictions and per-company views act on it as on a fresh one.
+"""
+import threading
+
+import numpy as np
+import torch
+
+from . import _lib
+
+DIM = 512
+
+
+class FaceTracks:
+    """The tracks of ``slots`` cameras, ``entries`` (1 .. 64) faces each, and the two launches of a batch of their frames.
+
+    ``iou_thr=0.5, max_reuse=4, max_misses=1`` are a judgment, not a measurement.  A face 60 pixels wide that moves 10 pixels
+    between two frames keeps an IoU of about 0.7, so 0.5 follows a walking person at 30 fps and loses a running one - who is
+    then embedded, the safe side.  ``max_reuse=4`` embeds a standing face every fifth active frame: pose and light drift
+    slowly, and the embed load of a persistent scene falls to a fifth.  ``max_misses=1`` keeps a track over one frame in which
+    the detector lost the face.  A matched face is never carried while another track of its camera overlaps it at all: faces
+    that touch or cross are embedded again, which is the guard against handing one person's embedding to another.  None of
+    these figures' error rates on real video is measured.
+
+    Camera ids are any hashable values; a new id takes a free slot, ``forget`` gives it back.  One lock orders the launches and
+    the state they move, in call order, on the calling thread's current stream.  The bank takes slots x entries x 4 KB of
+    device memory: 32 MB with the defaults."""
+
+    _CACHE = 64                              # slot arrays kept: one per tuple of camera ids, oldest dropped first
+
+    def __init__(self, device="cuda:0", slots=256, entries=32, iou_thr=0.5, max_reuse=4, max_misses=1):
+        if int(slots) < 1:
+            raise ValueError("slots must be positive")
+        if not 1 <= int(entries) <= 64:
+            raise ValueError("entries 1 .. 64 (one lane of a wave each)")
+        if not 0.0 < float(iou_thr) <= 1.0 or int(max_reuse) < 0 or int(max_misses) < 0:
+            raise ValueError("iou_thr in (0, 1], max_reuse >= 0, max_misses >= 0")
+        _lib.require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.index is None:                            # "cuda": the current device, by its number
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.slots, self.entries = int(slots), int(entries)
+        self.iou_thr, self.max_reuse, self.max_misses = float(iou_thr), int(max_reuse), int(max_misses)
+        self.tbox = torch.zeros((self.slots, self.entries, 4), dtype=torch.float32, device=self.device)
+        self.tstate = torch.zeros((self.slots, self.entries, 4), dtype=torch.int32, device=self.device)
+        self.next_id = torch.zeros(self.slots, dtype=torch.int32, device=self.device)
+        self.bank = torch.zeros((self.slots, self.entries, 2, DIM), dtype=torch.float32, device=self.device)
+        self.stats = {"faces": 0, "embedded": 0, "carried": 0, "untracked": 0}
+        self._slot_of, self._free = {}, list(range(self.slots - 1, -1, -1))
+        self._slot_arrays = {}                                   # tuple of camera ids -> int32 [N] on the device
+        self._lock = threading.Lock()
+
+    def __len__(self):
+        return len(self._slot_of)
+
+    def slot_of(self, camera_id):
+        """The slot of a camera id, None when it has none (yet)."""
+        return self._slot_of.get(camera_id)
+
+    def forget(self, camera_id):
+        """Free the camera's slot; its ``live`` flags are zeroed, so whoever takes the slot next starts without tracks (the
+        slot's id counter runs on).  Unknown ids are ignored."""
+        with self._lock:
+            s = self._slot_of.pop(camera_id, None)
+            if s is None:
+                return
+            self._slot_arrays.clear()                            # the id -> slot map moved
+            with torch.cuda.device(self.device):
+                self.tstate[s, :, 0].zero_()
+            self._free.append(s)
+
+    def reset(self, camera_ids):
+        """Drop the tracks of these cameras (their slots stay theirs): for a caller whose embed pass failed between
+        ``associate_device`` and ``commit_device``, when the bank does not hold what the state says it holds."""
+        with self._lock, torch.cuda.device(self.device):
+            for c in camera_ids:
+                s = self._slot_of.get(c)
+                if s is not None:
+                    self.tstate[s, :, 0].zero_()
+
+    def _slots_for(self, camera_ids):
+        """int32 [N] on the device for this tuple of ids (under the lock); uploaded once per tuple"""
+        key = tuple(camera_ids)
+        if len(set(key)) != len(key):
+            raise ValueError("a camera id is repeated in one call: a slot's tracks move once per batch")
+        hit = self._slot_arrays.pop(key, None)
+        if hit is None:
+            new = [c for c in key if c not in self._slot_of]
+            if len(new) > len(self._free):
+                raise ValueError(f"the tracks have {self.slots} slots and {len(self._free)} free: "
+                                 f"{len(new)} new camera ids do not fit (forget() frees one)")
+            for c in new:
+                self._slot_of[c] = self._free.pop()
+            hit = torch.tensor([self._slot_of[c] for c in key], dtype=torch.int32).to(self.device)
+            while len(self._slot_arrays) >= self._CACHE:
+                self._slot_arrays.pop(next(iter(self._slot_arrays)))
+        self._slot_arrays[key] = hit                             # most recently used last
+        return hit
+
+    def _check(self, t, dtype, shape, what):
+        if not (torch.is_tensor(t) and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous()
+                and t.device == self.device):
+            raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)} tensor on {self.device}")
+
+    def associate_device(self, boxes, counts, camera_ids):
+        """``boxes`` f32 [N,cap,4] and ``counts`` i32 [N] as the detector leaves them, frame i from camera ``camera_ids[i]``.
+        Returns ``(entry, need, tid)``, int32 [N,cap] device tensors: the track entry of a detection (-1: untracked), 1 where
+        it has to be embedded (0: its embedding is in the bank, and in slots past a frame's count), its track id (-1: none).
+        Runs on the current stream, no synchronisation; the state moves with the call."""
+        ids = list(camera_ids)
+        if not (torch.is_tensor(boxes) and boxes.dim() == 3):
+            raise ValueError("boxes must be f32 [N,cap,4]")
+        n, cap = boxes.shape[0], boxes.shape[1]
+        self._check(boxes, torch.float32, (n, cap, 4), "boxes")
+        self._check(counts, torch.int32, (n,), "counts")
+        if len(ids) != n:
+            raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
+        with self._lock, torch.cuda.device(self.device):
+            slot = self._slots_for(ids)
+            entry = torch.empty((n, cap), dtype=torch.int32, device=self.device)
+            need = torch.empty_like(entry)
+            tid = torch.empty_like(entry)
+            self.lib.fr_track_associate_f32(_lib.ptr(boxes), _lib.ptr(counts), _lib.ptr(slot), n, cap, self.slots, self.entries,
+                                            _lib.ptr(self.tbox), _lib.ptr(self.tstate), _lib.ptr(self.next_id), self.iou_thr,
+                                            self.max_reuse, self.max_misses, _lib.ptr(entry), _lib.ptr(need), _lib.ptr(tid),
+                                            _lib.stream_ptr())
+        return entry, need, tid
+
+    def commit_device(self, entry, need, counts, camera_ids, emb, normed):
+        """The second launch, over the slot-layout ``emb`` / ``normed`` f32 [N*cap,512]: the rows embedded this turn go to the
+        bank, the carried rows come from it (in place); every other row stays as it is.  ``camera_ids``: those of the
+        ``associate_device`` call that made ``entry`` and ``need``."""
+        ids = list(camera_ids)
+        if not (torch.is_tensor(entry) and entry.dim() == 2):
+            raise ValueError("entry must be i32 [N,cap]")
+        n, cap = entry.shape
+        self._check(entry, torch.int32, (n, cap), "entry")
+        self._check(need, torch.int32, (n, cap), "need")
+        self._check(counts, torch.int32, (n,), "counts")
+        self._check(emb, torch.float32, (n * cap, DIM), "emb")
+        self._check(normed, torch.float32, (n * cap, DIM), "normed")
+        if len(ids) != n:
+            raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
+        with self._lock, torch.cuda.device(self.device):
+            slot = self._slots_for(ids)
+            self.lib.fr_track_commit_f32(_lib.ptr(entry), _lib.ptr(need), _lib.ptr(slot), _lib.ptr(counts), n, cap, self.slots,
+                                         self.entries, _lib.ptr(self.bank), _lib.ptr(emb), _lib.ptr(normed), _lib.stream_ptr())
+
+    def count(self, counts, need, entry):
+        """Add one batch to ``stats`` from host copies of its counts [N], need and entry [N,cap] (the batch path reads them
+        back anyway): faces = embedded + carried, untracked are the embedded ones no entry was free for."""
+        counts, need, entry = np.asarray(counts), np.asarray(need), np.asarray(entry)
+        valid = np.arange(need.shape[1])[None, :] < counts[:, None]
+        faces, embedded = int(valid.sum()), int((valid & (need != 0)).sum())
+        with self._lock:
+            self.stats["faces"] += faces
+            self.stats["embedded"] += embedded
+            self.stats["carried"] += faces - embedded
+            self.stats["untracked"] += int((valid & (entry < 0)).sum())

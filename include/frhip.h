@@ -45,6 +45,7 @@ typedef void* fr_stream_t;
  * fr_gallery_pairs_workspace (the gallery audit), and for fr_yuv420_to_bgr_u8 / fr_yuv420_to_bgr_refs_u8 (YUV 4:2:0 frame ingest),
  * and for fr_frame_activity_u8 / fr_frame_activity_refs_u8 (the activity gate in front of the engine pass),
  * and for fr_pnet23_coarse_f16 / fr_pnet23_coarse_workspace_bytes / fr_pnet_pyramid_p23_coarse (the P-Net's coarse pass),
+ * and for fr_track_associate_f32 / fr_track_commit_f32 (face tracks: a face's embedding carried across a camera's frames),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -824,6 +825,50 @@ int fr_frame_activity_u8(const uint8_t* frames, int N, int H, int W, const int32
 int fr_frame_activity_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* slot, int S, uint8_t* grid, int32_t* geom,
                               int32_t* idle, int C, uint8_t* cur, int32_t* changed, int32_t* active, int thr, int min_cells,
                               int max_idle, fr_stream_t stream);
+
+/* ---------------------------------------------------------------- face tracks ----
+ * Between detect and align: is this detection a face the camera's previous frame already showed, so that the embedding held
+ * for it can stand in for a new one?  (The reference embeds every face of every frame it keeps and sheds load by taking every
+ * 2nd frame, peopleCount.py:938,962.)  Only the EMBEDDING is held, never an identity: the held row goes through the gallery
+ * scan of the current call.  State lives on the device, per camera slot s < S with T <= 64 entries, and belongs to the caller
+ * (zeroed once):
+ *   tbox    f32 [S][T][4]        the box an entry was last seen at (x1, y1, x2, y2)
+ *   tstate  i32 [S][T][4]        (live, since, misses, id): since = turns carried since the last embed, misses = turns unseen
+ *   next_id i32 [S]              the id the slot's next new track gets
+ *   bank    f32 [S][T][2][512]   (embedding, normed embedding) of the entry's last embed
+ *
+ * fr_track_associate_f32: boxes f32 [N][cap][4] and counts i32 [N] as the detectors leave them (descending score), slot i32 [N];
+ * outputs entry, need, tid i32 [N][cap].  Frame i with s = slot[i], detections j = 0 .. counts[i] - 1 (clamped to 0 .. cap) one
+ * after the other:
+ *   o[t]    IoU of detection j and tbox[s][t] for every live entry, in float32 with one IEEE rounding per operation:
+ *           area(b) = (b.x2 - b.x1 + 1) * (b.y2 - b.y1 + 1);  w = max(0, min(x2) - max(x1) + 1), h likewise, inter = w * h;
+ *           o = inter / ((area(detection) + area(entry)) - inter)      (the form and operand order fr_sort_nms is pinned to);
+ *           max / min pass a NaN on, so a NaN coordinate on either side gives o = NaN
+ *   match   among the live entries not claimed this turn with o[t] >= iou_thr (false for a NaN): the largest o, the lowest t
+ *           among equal values.  The entry is claimed, tbox[s][t] = the detection's box, misses = 0, entry = t, tid = id.
+ *   carry   a matched detection with since < max_reuse and with NO other live entry of the slot, claimed or not, at o > 0:
+ *           need = 0, since += 1.  Any other matched detection: need = 1, since = 0.  Faces that touch or cross are therefore
+ *           always embedded again - the guard against handing one person's embedding to another.
+ * then every live entry not claimed gets misses += 1 and live = 0 when misses > max_misses (nothing else of it changes); then
+ * every unmatched detection, in j order, takes the lowest entry that is not live (those retired this turn included):
+ * live = 1, since = misses = 0, id = next_id[s], next_id[s] += 1 (wrapping), tbox = its box, entry = t, tid = id, need = 1.  With no
+ * such entry the detection stays untracked: entry = tid = -1, need = 1.  Slots j >= counts[i]: entry = -1, need = 0, tid = -1.
+ * A frame whose slot is outside [0, S) has no state: need = 1, entry = tid = -1 for its detections, nothing else is touched.  Two
+ * frames of one call must not name one slot (the result is then unspecified, every access still inside the arrays).
+ * One launch on `stream`, one wave per frame with entry t in lane t, no synchronisation, allocation or atomics.
+ * Refused before any launch: T or cap outside 1 .. 64, S < 1, N outside 0 .. 65535, negative max_reuse or max_misses, iou_thr
+ * outside (0, 1] (a NaN included), a null pointer with N > 0.  N == 0 returns FR_OK and touches nothing.
+ *
+ * fr_track_commit_f32: after the embed net has filled the need = 1 rows of emb / normed f32 [N*cap][512] (slot layout), one
+ * workgroup per (frame, detection slot j < counts) with 0 <= entry < T and a slot inside [0, S):
+ *   need != 0:  bank[s][entry] = (emb row, normed row)          need == 0:  (emb row, normed row) = bank[s][entry]
+ * as 16-byte moves; every other row of emb / normed and of bank is left untouched.  Refusals as above (those of its arguments).
+ * Added under ABI 106: no existing signature changed. */
+int fr_track_associate_f32(const float* boxes, const int32_t* counts, const int32_t* slot, int N, int cap, int S, int T,
+                           float* tbox, int32_t* tstate, int32_t* next_id, float iou_thr, int max_reuse, int max_misses,
+                           int32_t* entry, int32_t* need, int32_t* tid, fr_stream_t stream);
+int fr_track_commit_f32(const int32_t* entry, const int32_t* need, const int32_t* slot, const int32_t* counts, int N, int cap,
+                        int S, int T, float* bank, float* emb, float* normed, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- SCRFD detector ----
  * The detector of insightface's buffalo_l pack (det_10g.onnx; FaceAnalysis(name="buffalo_l"), infrenceServer.py:412-416) as
