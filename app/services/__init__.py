@@ -7,5 +7,6 @@ from facerecognition_infrenceengine_amd.processor import (CameraProcessor, Embed
 from facerecognition_infrenceengine_amd.camera import CameraManager  # noqa: F401
 from facerecognition_infrenceengine_amd.activity import ActivityGate  # noqa: F401
 from facerecognition_infrenceengine_amd.tracks import FaceTracks  # noqa: F401
+from facerecognition_infrenceengine_amd.quality import FaceQuality  # noqa: F401
 from facerecognition_infrenceengine_amd.processor import UNCHANGED  # noqa: F401
 from facerecognition_infrenceengine_amd.server import create_app  # noqa: F401

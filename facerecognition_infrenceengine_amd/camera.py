@@ -26,13 +26,15 @@ logger = logging.getLogger(__name__)
 
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
-                 dead_after=200, gate=None, tracks=None):
+                 dead_after=200, gate=None, tracks=None, quality=None):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
         ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
         frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
         results held from that last processed frame.  None: every frame goes through the engine, as ever.
         ``tracks``: a ``tracks.FaceTracks``; the processor then embeds only the faces a source's previous frame did not show
         (the sources are its camera ids too).  None: every face is embedded, as ever.
+        ``quality``: a ``quality.FaceQuality``; the processor then embeds only the faces judged fit and reports the others as
+        Unknown with ``quality_ok`` False.  None: no face is judged, as ever.  Not together with ``tracks`` (ValueError).
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
         waits for slow cameras once it holds a frame (latency stays that of the slowest *present* frame).
         ``reopen_after`` / ``dead_after``: consecutive failed reads before a capture is re-opened / given up."""
@@ -54,6 +56,9 @@ class CameraManager:
         if gate is not None:
             self.stats["gated_frames"] = 0
         self.tracks = tracks
+        if quality is not None and tracks is not None:
+            raise ValueError("quality together with tracks is not supported yet")
+        self.quality = quality
 
     def _forget(self, source):
         """A source that is gone: its gate slot and its track slot are freed and its held results dropped."""
@@ -175,6 +180,8 @@ class CameraManager:
             gated = {} if self.gate is None else {"gate": self.gate, "camera_ids": [batch[k][0] for k in ks]}
             if self.tracks is not None:
                 gated = dict(gated, tracks=self.tracks, camera_ids=[batch[k][0] for k in ks])
+            if self.quality is not None:
+                gated = dict(gated, quality=self.quality)
             res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids, **gated)
             for j, k in enumerate(ks):
                 results[k] = None if res is None else res[j]

@@ -32,23 +32,33 @@ def largest_face_index(faces):
 
 
 class Enroller:
-    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4):
+    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4, quality=None):
+        """``quality`` (a ``quality.FaceQuality``): ``process_image`` has the engine judge the aligned faces, and ``enrol`` refuses a
+        job whose pose image shows an unfit largest face (``{"status": "low_quality", "image": i, "reasons": [...]}``) - a gallery
+        row lives for years.  ``enrol_batch`` and ``enrol_slots`` of such an Enroller raise ValueError: the batch kernel
+        (fr_enrol_batch_f32) picks the largest face on the device and takes no mask yet.  None: no face is judged, as ever."""
         self.app, self.similarity_threshold, self.duplicate_threshold = face_analysis, similarity_threshold, duplicate_threshold
+        self.quality = quality
         self.lib = _lib.load()
         self.device = face_analysis.device
 
     def process_image(self, image):
         """trainingServer.py:216-247: normed embedding of the largest face, or None.  ``image``: a BGR uint8 array, or
         the encoded bytes the reference reads from GridFS (``:219-221``: decoded here, None when they do not decode)."""
+        face = self._largest_face(image)
+        return None if face is None else face.normed_embedding
+
+    def _largest_face(self, image):
+        """The Face ``process_image`` takes its embedding from, or None; with ``quality`` it carries the verdict."""
         if isinstance(image, (bytes, bytearray, memoryview)):
             from .ingest import decode_image
             image = decode_image(image)
             if image is None:
                 return None
-        faces = self.app.get(image)
+        faces = self.app.get(image) if self.quality is None else self.app.get(image, quality=self.quality)
         if not faces:
             return None
-        return faces[largest_face_index(faces) if len(faces) > 1 else 0].normed_embedding
+        return faces[largest_face_index(faces) if len(faces) > 1 else 0]
 
     def check_image_similarity(self, embeddings):
         """trainingServer.py:202-214: first (i, j), i < j, with cosine < threshold."""
@@ -81,8 +91,20 @@ class Enroller:
         return (idx >= 0), (matcher.ids[idx] if idx >= 0 else None)
 
     def enrol(self, pose_images, matcher):
-        """Whole job arithmetic (trainingServer.py:312-398).  Returns dict(status=..., ...)."""
-        embs = [e for e in (self.process_image(im) for im in pose_images) if e is not None]
+        """Whole job arithmetic (trainingServer.py:312-398).  Returns dict(status=..., ...).  With ``quality``: the first pose
+        image whose largest face is not fit ends the job, before the similarity check, with ``{"status": "low_quality",
+        "image": its index, "reasons": [...]}``."""
+        if self.quality is None:
+            embs = [e for e in (self.process_image(im) for im in pose_images) if e is not None]
+        else:
+            embs = []
+            for i, im in enumerate(pose_images):
+                face = self._largest_face(im)
+                if face is None:
+                    continue
+                if not face.quality_ok:
+                    return {"status": "low_quality", "image": i, "reasons": list(face.quality["reasons"])}
+                embs.append(face.normed_embedding)
         if not embs:
             return {"status": "no_face"}
         ok, pair = self.check_image_similarity(embs)
@@ -105,7 +127,10 @@ class Enroller:
         gallery: a GalleryMatcher of unit rows or a GalleryView (a stale one raises StaleViewError).
         Returns device tensors on the current stream: status i32 [J] (ENROL_*), pair i32 [J,2], face i32 [I] (the chosen
         slot of each image in ``job_images`` order, flattened; -1: no face), avg f32 [J,512], row f32 [J,512], dup_pos
-        i64 [J] (gallery position, len(gallery) + i for the batch's job i, -1), dup_score f32 [J]."""
+        i64 [J] (gallery position, len(gallery) + i for the batch's job i, -1), dup_score f32 [J].
+        An Enroller with ``quality`` raises ValueError: the kernel takes no mask of unfit faces yet."""
+        if getattr(self, "quality", None) is not None:
+            raise ValueError("an Enroller with quality enrols job by job (enrol): the batch kernel takes no quality mask yet")
         parts = list(slots) if isinstance(slots, (list, tuple)) else [slots]
         job_images = [list(im) for im in job_images]
         J = len(job_images)
@@ -188,7 +213,10 @@ class Enroller:
         embedding, blob); a duplicate of the batch's own job i carries ``duplicate_of_job: i`` and ``duplicate_id =
         ids[i]`` (None without ``ids``).  commit=True (needs a GalleryView and ``ids``): the ``done`` rows are upserted into
         ``gallery.gallery`` under their ids in one call, and ``result.view`` is the view of the old ids followed by the
-        done ids in job order - the gallery the next batch is checked against."""
+        done ids in job order - the gallery the next batch is checked against.
+        An Enroller with ``quality`` raises ValueError: the batch kernel picks the largest face on the device and takes no mask."""
+        if getattr(self, "quality", None) is not None:
+            raise ValueError("an Enroller with quality enrols job by job (enrol): the batch kernel takes no quality mask yet")
         jobs = [list(job) for job in jobs]
         if len(jobs) > ENROL_MAX_JOBS:
             raise ValueError(f"at most {ENROL_MAX_JOBS} jobs a batch (got {len(jobs)})")

@@ -340,9 +340,13 @@ class FaceAnalysis:
                                              F, 112, _lib.ptr(crops), None, None, _lib.stream_ptr())
 
     # ------------------------------------------------------------------ device-side pipeline
-    def detect_embed_device(self, frames):
+    def detect_embed_device(self, frames, quality=None):
         """frames: uint8 [N,H,W,3] BGR on the device, or - with ``det_size`` - a list of [Hi,Wi,3] device frames of any
         sizes.  One host sync (face counts).
+
+        quality: a ``quality.FaceQuality`` - one launch more measures the F aligned crops (no sync more) and the dict gains
+        ``quality`` i32 [F,8], ``quality_f`` f32 [F,4] and ``quality_verdict`` i32 [F] (0: fit).  EVERY face is still embedded:
+        enrolment wants the embedding whatever the verdict.
 
         Returns dict of device tensors for the F detected faces (frame-major, descending score
         within a frame): frame_idx i32 [F], bbox f32 [F,4], kps f32 [F,5,2], det_score f32 [F],
@@ -373,12 +377,18 @@ class FaceAnalysis:
             with torch.cuda.device(self.device):
                 crops = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
                 self._warp_faces(frames, src, out["kps"], frame_idx, F, crops)
+                if quality is not None:
+                    out["quality"], out["quality_f"], out["quality_verdict"] = quality.measure_device(crops, out["kps"])
                 emb, normed = self.rec.forward(crops)
+        elif quality is not None:
+            out["quality"] = torch.empty((0, 8), dtype=torch.int32, device=self.device)
+            out["quality_f"] = torch.empty((0, 4), dtype=torch.float32, device=self.device)
+            out["quality_verdict"] = torch.empty(0, dtype=torch.int32, device=self.device)
         out["embedding"], out["normed_embedding"] = emb, normed
         return out
 
     def detect_embed_slots(self, frames, det_stream=None, ready_event=None, compact_embed=False, crops_out=None,
-                           table=None, det_scale=None, tracks=None, camera_ids=None):
+                           table=None, det_scale=None, tracks=None, camera_ids=None, quality=None):
         """Sync-free form for streaming/serving: every frame owns ``cap_o`` face slots.
 
         frames: uint8 [N,H,W,3] BGR on the device; with ``det_size`` also a list of [Hi,Wi,3] device frames of any sizes,
@@ -403,7 +413,15 @@ class FaceAnalysis:
         tracks: a ``tracks.FaceTracks`` with ``camera_ids`` (one per frame, none repeated), only with ``compact_embed``: behind
         the detector one launch decides which detections are faces the camera's tracks hold an embedding for, the copy of the
         face counts carries that verdict along (no second sync), align and embed run for the others only, and a second launch
-        fills the carried rows from the bank and stores the new ones.  The dict gains ``track_id`` and ``carried`` i32 [N,cap]."""
+        fills the carried rows from the bank and stores the new ones.  The dict gains ``track_id`` and ``carried`` i32 [N,cap].
+
+        quality: a ``quality.FaceQuality``, only with ``compact_embed`` and without ``crops_out`` (ValueError otherwise): every
+        slot is aligned (sync-free, empty slots skipped by their counts), ONE launch judges the aligned crops, the copy of the
+        face counts carries the verdicts along (no second sync), and the embed net runs over the slots that hold a face AND are
+        fit.  A rejected slot keeps the unit-vector placeholder of an empty one.  The dict gains ``quality`` i32 [N,cap,8],
+        ``quality_f`` f32 [N,cap,4] and ``quality_verdict`` i32 [N,cap] (0: fit, -1: no face, else the reason bits of
+        include/frhip.h fr_face_quality_f16).  Quality together with ``tracks`` is left for later and raises ValueError: the
+        tracks' commit launch expects an embedded row for every face that needs one, and a rejected face has none."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         if tracks is not None:
@@ -416,6 +434,12 @@ class FaceAnalysis:
                 raise ValueError("a camera id is repeated in one call")
         elif camera_ids is not None:
             raise ValueError("camera_ids come with tracks (tracks=FaceTracks(...))")
+        if quality is not None:
+            if not compact_embed or crops_out is not None:
+                raise ValueError("quality needs compact_embed=True and no crops_out: the rejected faces are left out of the "
+                                 "embed pass on the host")
+            if tracks is not None:
+                raise ValueError("quality together with tracks is not supported yet")
         cur = torch.cuda.current_stream(self.device)
         if ready_event is not None:
             (det_stream if det_stream is not None else cur).wait_event(ready_event)
@@ -432,6 +456,8 @@ class FaceAnalysis:
         N = src.n if src is not None else frames.shape[0]
         cap = boxes.shape[1]
         if compact_embed:
+            if quality is not None:
+                return self._embed_fit(frames, src, boxes, scores, kps, counts, N, cap, quality)
             if tracks is None:
                 cnt = counts.cpu()                                        # the extra sync
                 sel = (torch.arange(cap)[None, :] < cnt[:, None]).reshape(-1).nonzero().squeeze(1).to(self.device)
@@ -501,6 +527,26 @@ class FaceAnalysis:
                 emb[sel], normed[sel] = e, nm
         return emb, normed
 
+    def _embed_fit(self, frames, src, boxes, scores, kps, counts, N, cap, quality):
+        """The ``quality`` pass of ``detect_embed_slots``: align every slot, judge the crops, embed the fit faces."""
+        with torch.cuda.device(self.device):
+            kps = kps.contiguous()
+            crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
+            self._warp_slots(frames, src, kps, counts, cap, crops)
+            qi, qf, verdict = quality.measure_device(crops, kps, counts, cap)
+            both = torch.cat([counts.reshape(N, 1), verdict.view(N, cap)], dim=1).cpu()       # the same one sync, a wider row
+            cnt, ver = both[:, 0], both[:, 1:]
+            sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (ver == 0)).reshape(-1).nonzero().squeeze(1).to(self.device)
+            emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
+            emb[:, 0] = 1.0                                               # empty and rejected slots: a unit vector
+            normed = emb.clone()
+            if sel.numel():
+                fit = crops.index_select(0, sel)                          # named, not inline (see detect_embed_slots)
+                e, nm = self.rec.forward(fit)
+                emb[sel], normed[sel] = e, nm
+        return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
+                "quality": qi.view(N, cap, 8), "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict.view(N, cap)}
+
     def embed_slots(self, crops):
         """Second half of ``detect_embed_slots(..., crops_out=...)``: ONE embed forward over the aligned crops of several
         detector calls (f16 [S,112,112,8], slot-major as those calls filled it) -> (embedding, normed_embedding) f32 [S,512].
@@ -532,9 +578,12 @@ class FaceAnalysis:
         return g
 
     # ------------------------------------------------------------------ reference-shaped API
-    def get_batch(self, frames):
+    def get_batch(self, frames, quality=None):
         """list/array of BGR uint8 frames -> list (per frame) of lists of Face.  The frames are of one size; under
-        ``det_size`` a list may mix sizes (bbox / kps are in each frame's own pixels)."""
+        ``det_size`` a list may mix sizes (bbox / kps are in each frame's own pixels).
+
+        ``quality`` (a ``quality.FaceQuality``): every Face gains ``quality`` (the dict of ``FaceQuality.describe``) and
+        ``quality_ok``; every face is embedded whatever its verdict.  Such a call runs eagerly, also under ``enable_graphs``."""
         if not isinstance(frames, np.ndarray):
             frames = [np.ascontiguousarray(np.asarray(f)) for f in frames]
             if any(f.ndim != 3 or f.shape[2] != 3 or f.dtype != np.uint8 for f in frames):
@@ -543,26 +592,28 @@ class FaceAnalysis:
                 if self.det_size is None:
                     raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
                 with self._lock:
-                    return self._faces_of(self.detect_embed_device(self._to_device(frames)))
+                    return self._faces_of(self.detect_embed_device(self._to_device(frames), quality))
             frames = np.stack(frames)
         arr = np.ascontiguousarray(frames)
         if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
             raise ValueError("frames must be uint8 [N,H,W,3] BGR")
-        if getattr(self, "_use_graphs", False) and self.det_size is None:
+        if getattr(self, "_use_graphs", False) and self.det_size is None and quality is None:
             with self._lock:
                 counts, host = self._graph_for(tuple(arr.shape)).run(arr)
             return _faces_from_slots(counts, host)
         with self._lock:
             dev = torch.from_numpy(arr).to(self.device)
-            return self._faces_of(self.detect_embed_device(dev))
+            return self._faces_of(self.detect_embed_device(dev, quality))
 
     @staticmethod
     def _faces_of(r):
         """``detect_embed_device``'s result -> per-frame lists of Face"""
         # ONE device-to-host copy (and sync) for the five result tensors instead of five
         F = r["bbox"].shape[0]
+        judged = "quality" in r                    # its integers ride in the same copy: all below 2^24, exact in float32
+        extra = [r["quality"].to(torch.float32), r["quality_f"], r["quality_verdict"].reshape(F, 1).to(torch.float32)] if judged else []
         pack = torch.cat([r["bbox"].reshape(F, 4), r["kps"].reshape(F, 10), r["det_score"].reshape(F, 1),
-                          r["embedding"], r["normed_embedding"]], dim=1).cpu().numpy()
+                          r["embedding"], r["normed_embedding"]] + extra, dim=1).cpu().numpy()
         host = {"bbox": pack[:, 0:4], "kps": pack[:, 4:14].reshape(F, 5, 2), "det_score": pack[:, 14],
                 "embedding": pack[:, 15:527], "normed_embedding": pack[:, 527:1039]}
         res, i = [], 0
@@ -572,13 +623,18 @@ class FaceAnalysis:
                 faces.append(Face(bbox=host["bbox"][i].copy(), kps=host["kps"][i].copy(),
                                   det_score=float(host["det_score"][i]), embedding=host["embedding"][i].copy(),
                                   normed_embedding=host["normed_embedding"][i].copy()))
+                if judged:
+                    from .quality import FaceQuality
+                    q = FaceQuality.describe(pack[i, 1039:1047], pack[i, 1047:1051], pack[i, 1051])
+                    faces[-1]["quality"], faces[-1]["quality_ok"] = q, q["ok"]
                 i += 1
             res.append(faces)
         return res
 
-    def get(self, img, max_num=0):
-        """One BGR uint8 HWC frame -> list of Face (descending det_score), as infrenceServer.py:528."""
-        faces = self.get_batch(np.asarray(img)[None])[0]
+    def get(self, img, max_num=0, quality=None):
+        """One BGR uint8 HWC frame -> list of Face (descending det_score), as infrenceServer.py:528.  ``quality``: as
+        ``get_batch``."""
+        faces = self.get_batch(np.asarray(img)[None], quality)[0]
         return faces[:max_num] if max_num else faces
 
     def get_batch_yuv(self, frames, pixel_format="nv12", matrix="bt601"):

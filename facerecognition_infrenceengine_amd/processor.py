@@ -68,6 +68,28 @@ def _tracked(face, tid, carried, f, j):
     return face
 
 
+def _quality_columns(r):
+    """Host copies of the slot results' ``quality`` [n,cap,8], ``quality_f`` [n,cap,4] and ``quality_verdict`` [n,cap]; None for
+    a call without quality."""
+    if "quality" not in r:
+        return None
+    return r["quality"].cpu().numpy(), r["quality_f"].cpu().numpy(), r["quality_verdict"].cpu().numpy()
+
+
+def _fit(q, f, j):
+    """True for a call without quality and for a face judged fit"""
+    return q is None or q[2][f, j] == 0
+
+
+def _judged(face, q, f, j):
+    """The face dict with ``quality`` (``FaceQuality.describe``) and ``quality_ok``; as it is without quality."""
+    if q is not None:
+        from .quality import FaceQuality
+        face["quality"] = FaceQuality.describe(q[0][f, j], q[1][f, j], q[2][f, j])
+        face["quality_ok"] = face["quality"]["ok"]
+    return face
+
+
 def _spread(out, keep, n):
     """Results of the active frames ``keep`` back at their places among ``n`` frames; UNCHANGED for the others."""
     if keep is None:
@@ -407,7 +429,7 @@ class FaceRecognitionProcessor:
         return getattr(self.face_detector, "det_size", None) is not None
 
     def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
-                    tracks=None):
+                    tracks=None, quality=None):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
         no company has a gallery (nothing is run, a gate is not consulted), else (n, slot results, view_set, metadatas,
@@ -427,7 +449,8 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", c)
         if all(v is None for v in index_of):
             return None
-        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks,
+                                               quality)
         if keep is not None:                      # the views of the active frames' companies, as a call on those frames has them
             company_ids = [company_ids[f] for f in keep]
             if r is not None:
@@ -448,9 +471,9 @@ class FaceRecognitionProcessor:
         return n, r, view_set, metadatas, index_of, idx, score, keep
 
     def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
-                               tracks=None):
+                               tracks=None, quality=None):
         got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
-                               tracks=tracks)
+                               tracks=tracks, quality=quality)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score, keep = got
@@ -463,30 +486,34 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        q = _quality_columns(r)
         out = []
         for f in range(n):
             if index_of[f] is None:
                 out.append(None)
                 continue
             ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], ids, metadata),
-                                 tid, carried, f, j) for j in range(int(counts[f]))])
+            out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
+                                                      score[f, j], ids, metadata), tid, carried, f, j), q, f, j)
+                        for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
     def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601", gate=None,
-                       camera_ids=None, tracks=None):
+                       camera_ids=None, tracks=None, quality=None):
         """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
         list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
         whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``,
-        ``gate`` / ``tracks`` / ``camera_ids``: as ``recognize_batch``."""
+        ``gate`` / ``tracks`` / ``camera_ids`` / ``quality``: as ``recognize_batch``; a face judged unfit has no candidates."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
+        if quality is not None and tracks is not None:
+            raise ValueError("quality together with tracks is not supported yet")
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
         got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
-                               tracks=tracks)
+                               tracks=tracks, quality=quality)
         if got is None:
             return [None] * len(frames)
         n, r, view_set, metadatas, index_of, idx, score, keep = got
@@ -498,17 +525,20 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        q = _quality_columns(r)
         out = []
         for f in range(n):
             if index_of[f] is None:
                 out.append(None)
                 continue
             pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_tracked(_face_candidates(bbox[f, j], dscore[f, j], idx[f, j], score[f, j], pids, metadata, min_score),
-                                 tid, carried, f, j) for j in range(int(counts[f]))])
+            out.append([_judged(_tracked(_face_candidates(bbox[f, j], dscore[f, j], idx[f, j] if _fit(q, f, j) else (), score[f, j],
+                                                          pids, metadata, min_score), tid, carried, f, j), q, f, j)
+                        for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
-    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None):
+    def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
+                        quality=None):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -543,17 +573,25 @@ class FaceRecognitionProcessor:
         the embed net; the held embedding goes through THIS call's scan and decision, so the identity is never cached.  Each
         face dict gains ``"track_id"`` (int, -1: untracked) and ``"tracked"`` (True: carried).  With a gate too, a frame
         answered ``UNCHANGED`` never reaches the tracks and its camera's track state does not move; nor does it when the
-        company has no gallery."""
+        company has no gallery.
+
+        ``quality`` (a ``quality.FaceQuality``): behind align one launch judges every aligned face (sharpness, exposure,
+        contrast, size, pose: DESIGN.md 4.5e) and the embed net runs for the fit ones only.  Every face dict gains ``"quality"``
+        (the dict of ``FaceQuality.describe``) and ``"quality_ok"``; a rejected face is reported as the Unknown dict whatever the
+        scan made of its placeholder row.  Not together with ``tracks`` (ValueError)."""
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
+        if quality is not None and tracks is not None:
+            raise ValueError("quality together with tracks is not supported yet")
         if isinstance(company_id, (list, tuple)):
-            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks)
+            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks, quality)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
         if len(matcher) == 0:
             logger.warning("No embeddings found for company %s", company_id)
             return None
-        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks)
+        n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks,
+                                               quality)
         if r is None:                                                        # no frame active
             return [UNCHANGED] * len(frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
@@ -565,10 +603,12 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        q = _quality_columns(r)
         out = []
         for f in range(n):
-            out.append([_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j], idx[f, j], score[f, j], matcher.ids, metadata),
-                                 tid, carried, f, j) for j in range(int(counts[f]))])
+            out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
+                                                      score[f, j], matcher.ids, metadata), tid, carried, f, j), q, f, j)
+                        for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
     def annotate(self, frame, results):
@@ -681,7 +721,7 @@ class CameraProcessor:
                                              for i in range(len(banks))]
         return list(zip(banks, masks))
 
-    def process_batch(self, frames, camera_ids):
+    def process_batch(self, frames, camera_ids, quality=None):
         """Batch form of ``process_frame``: ``frames`` = list of BGR uint8 frames (of one size, or of any sizes when the
         engine has a ``det_size``), ``camera_ids`` = their cameras.  ONE pass of the slot pipeline over the batch,
         whole-gallery scan, the 0.45 / 0.35 decision and - with ``unknown_clusters`` - the clustering of the unknown
@@ -692,7 +732,12 @@ class CameraProcessor:
         a clustered face instead of ``process_unknown_detection`` (no embedding travels to the host); a face its bank
         refused (capacity) goes to ``process_unknown_detection``.  Returns one stats dict per frame, with clusters plus
         ``"unknown_clusters": [(cluster, is_new, detection_count), ...]``.  Errors are logged and swallowed as
-        ``process_frame``'s are; only ``len(camera_ids) != len(frames)`` raises (ValueError), before anything runs."""
+        ``process_frame``'s are; only ``len(camera_ids) != len(frames)`` raises (ValueError), before anything runs.
+
+        ``quality`` (a ``quality.FaceQuality``): the engine pass judges every aligned face and embeds the fit ones only.  A
+        rejected face is taken out of the unknown mask before ``assign_batch`` - it opens and joins no cluster - and reaches
+        neither ``process_detection`` nor the unknown fan-out; it still counts under ``"faces"``, and every stats dict gains
+        ``"low_quality"``, the number of such faces of the frame."""
         import torch
         from . import _lib
         if self.face_detector is None:
@@ -701,15 +746,15 @@ class CameraProcessor:
         if len(camera_ids) != n:                  # the caller's mistake, and the one error that raises (gallery or not)
             raise ValueError(f"{n} frames but {len(camera_ids)} camera ids")
         clustered = self.unknown_clusters is not None
-        stats = [dict({"faces": 0, "recognized": 0, "unknown": 0}, **({"unknown_clusters": []} if clustered else {}))
-                 for _ in range(n)]
+        stats = [dict({"faces": 0, "recognized": 0, "unknown": 0}, **({"unknown_clusters": []} if clustered else {}),
+                      **({"low_quality": 0} if quality is not None else {})) for _ in range(n)]
         matcher, metadata = self.embedding_manager.get_matcher_for_company(None)
         if len(matcher) == 0 or n == 0:
             return stats
         timestamp = datetime.utcnow()
         try:
             det = self.face_detector
-            n, r = _detect_embed_batch(self, det, frames)
+            n, r = _detect_embed_batch(self, det, frames, quality=quality)
             E = r["normed_embedding"]
             matcher, metadata, idx, score = _match_fresh(self.embedding_manager, None, matcher, metadata, E)
             dec = matcher.decide_device(idx, score, self.recognition_threshold, self.unknown_threshold)
@@ -724,15 +769,22 @@ class CameraProcessor:
                     qn = torch.empty_like(E)                                          # peopleCount.py:863
                     _lib.load().fr_l2norm_rows_f32(_lib.ptr(E), _lib.ptr(qn), S, 512, _lib.stream_ptr())
                     unknown = (torch.arange(cap, device=det.device)[None, :] < r["counts"][:, None]) & (dec.view(n, cap) == 0)
+                    if quality is not None:                                           # a rejected face joins no cluster
+                        unknown = unknown & (r["quality_verdict"] == 0)
                     trip = None
                     for bank, mask in banks:
                         take = (unknown if mask is None else unknown & mask[:, None]).reshape(-1)
                         t = torch.stack(bank.assign_batch(qn, take))                  # [3,S]: cluster, is_new, count
                         trip = t if trip is None else torch.where(take[None, :], t, trip)   # a slot belongs to one bank
                 ints.append(trip.reshape(-1).to(torch.int64))
+            if quality is not None:
+                ints.append(r["quality_verdict"].reshape(-1).to(torch.int64))         # last, behind the banks' columns
             # ---- the one group of device -> host copies
             counts = r["counts"].cpu().numpy()
             ints = torch.cat(ints).cpu().numpy()
+            verdict_h = None
+            if quality is not None:
+                ints, verdict_h = ints[:-S], ints[-S:]
             flt = torch.cat([score.reshape(S, 1), r["bbox"].reshape(S, 4)], dim=1).cpu().numpy()
             idx_h, dec_h = ints[:S], ints[S:2 * S]
             trip_h = ints[2 * S:].reshape(3, S) if banks else None
@@ -747,7 +799,9 @@ class CameraProcessor:
                 st, cam = stats[f], camera_ids[f]
                 st["faces"] = int(counts[f])
                 for s in range(f * cap, f * cap + int(counts[f])):
-                    if dec_h[s] == 1:
+                    if verdict_h is not None and verdict_h[s] != 0:
+                        st["low_quality"] += 1
+                    elif dec_h[s] == 1:
                         pid = matcher.ids[idx_h[s]]
                         self.manager.process_detection(pid, metadata[pid], cam, timestamp, float(score_h[s]))
                         st["recognized"] += 1
@@ -804,13 +858,14 @@ def _detect_embed(detector, frame):
         return detector.detect_embed_device(dev)
 
 
-def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601"):
+def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601", quality=None):
     """``_detect_embed_batch_gated`` without a gate: (number of frames, the slot results)."""
-    n, r, _ = _detect_embed_batch_gated(owner, det, frames, pixel_format, matrix)
+    n, r, _ = _detect_embed_batch_gated(owner, det, frames, pixel_format, matrix, quality=quality)
     return n, r
 
 
-def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None):
+def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
+                              quality=None):
     """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
     ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape and pixel format) -> copy
     stream -> ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
@@ -826,7 +881,10 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
     path of a call without a gate.
 
     ``tracks`` (``tracks.FaceTracks``) with ``camera_ids``: handed to the engine pass with the camera ids of the frames that
-    reach it - all of them, or with a gate the kept ones, so a frame judged inactive never moves its camera's tracks."""
+    reach it - all of them, or with a gate the kept ones, so a frame judged inactive never moves its camera's tracks.
+
+    ``quality`` (``quality.FaceQuality``): handed to the engine pass, which then embeds the faces judged fit only; a call
+    without it passes no such argument on, and runs the code it always ran."""
     import torch
     from .colour import check_pixel_format, check_yuv_shape
     from .ingest import FrameIngest, RaggedIngest
@@ -886,6 +944,8 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
                               "det_scale": ragged["det_scale"].index_select(0, sel)}
         if tracks is not None:
             ragged = dict(ragged, tracks=tracks, camera_ids=camera_ids if keep is None else [camera_ids[f] for f in keep])
+        if quality is not None:
+            ragged = dict(ragged, quality=quality)
         r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, **ragged)    # results go to the host anyway
         ring.release(turn)
     return n, r, keep

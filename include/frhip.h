@@ -46,6 +46,7 @@ typedef void* fr_stream_t;
  * and for fr_frame_activity_u8 / fr_frame_activity_refs_u8 (the activity gate in front of the engine pass),
  * and for fr_pnet23_coarse_f16 / fr_pnet23_coarse_workspace_bytes / fr_pnet_pyramid_p23_coarse (the P-Net's coarse pass),
  * and for fr_track_associate_f32 / fr_track_commit_f32 (face tracks: a face's embedding carried across a camera's frames),
+ * and for fr_face_quality_f16 (face quality: which aligned faces are worth the embed net),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -869,6 +870,44 @@ int fr_track_associate_f32(const float* boxes, const int32_t* counts, const int3
                            int32_t* entry, int32_t* need, int32_t* tid, fr_stream_t stream);
 int fr_track_commit_f32(const int32_t* entry, const int32_t* need, const int32_t* slot, const int32_t* counts, int N, int cap,
                         int S, int T, float* bank, float* emb, float* normed, fr_stream_t stream);
+
+/* ---------------------------------------------------------------- face quality ----
+ * Between align and embed: is this aligned face worth the embed net and a gallery scan?  (The reference embeds every detected
+ * face, infrenceServer.py:528-532; its only guard is the silent [0.35, 0.45) drop band of the counting path.)  The crops are in
+ * fixed geometry, so what is measured on them compares between faces of any size in the frame.
+ *   crops        f16 [S][112][112][8] as fr_warp_affine_5pt* write them: channels 0..2 are R, G, B as (u - 127.5) / 127.5
+ *   kps          f32 [S][5][2] in frame pixels: left eye, right eye, nose, left mouth, right mouth
+ *   slot_counts  i32 [S / cap] with cap: slot s holds a face iff s % cap < slot_counts[s / cap];  NULL: all S rows hold faces
+ *   qi i32 [S][8], qf f32 [S][4], verdict i32 [S]      the outputs
+ * A slot without a face writes verdict = -1 and zeros, and reads neither its crop nor its kps.
+ * Pixel: per channel u = rint(h * 127.5f + 127.5f) clamped to 0 .. 255, two singly rounded f32 operations (the byte the warp
+ * rounded to, for all 256 values);  L = (77 R + 150 G + 29 B + 128) >> 8, the activity gate's weights.
+ * Window: rows 20 .. 99 and columns 16 .. 95 inclusive, n = 6400 pixels, the face interior of the ArcFace template; the Laplacian
+ * also reads the one-pixel ring round it (rows 19 .. 100, columns 15 .. 96).  Nothing else of the crop is read.
+ * Integer metrics, exact (the same bytes from any launch shape), over the window:
+ *   D(y,x) = 4 L(y,x) - L(y-1,x) - L(y+1,x) - L(y,x-1) - L(y,x+1)
+ *   qi[0] = mean     = (sum L + n/2) / n
+ *   qi[1] = contrast = (n sum L^2 - (sum L)^2) / n^2        64-bit, floor
+ *   qi[2] = sharp    = (n sum D^2 - (sum D)^2) / n^2        64-bit, floor; sum D^2 reaches 6 658 560 000 on a checkerboard (more
+ *                                                           than 2^32), sharp itself is at most 1 040 400
+ *   qi[3] = dark   = pixels with L <= 15        qi[4] = bright = pixels with L >= 240        qi[5..7] = 0
+ * Landmark metrics, float32, one IEEE rounding per operation in exactly this order (no fused multiply-add, no division):
+ *   e = re - le;  d2 = e.x e.x + e.y e.y;  a = nose - le;  t = a.x e.x + a.y e.y;  mid = (lm + rm) 0.5f;
+ *   c = cross(e, a);  m = cross(e, mid - le)  with cross(a, b) = a.x b.y - a.y b.x;      qf = (d2, t, c, m)
+ * (on the template itself t / d2 = 0.500 and c / m = 0.495).
+ * Verdict: 0 when the face is fit, otherwise the sum of
+ *     1 small    d2 < min_eye2                 2 dark     mean < mean_lo             4 bright  mean > mean_hi
+ *     8 flat     contrast < contrast_min      16 blurred  sharp < sharp_min         32 clipped dark + bright > clip_max
+ *    64 yaw      fabsf((t + t) - d2) > yaw_max d2
+ *   128 pitch    !(m > 0), or c < pitch_lo m, or c > pitch_hi m
+ * One launch on `stream`, one workgroup per slot, no allocation, atomics or synchronisation.  Refused before any launch: S
+ * outside 0 .. 65535 * 64, cap < 1 with slot_counts given, min_eye2 negative, infinite or NaN, mean_lo or mean_hi outside
+ * 0 .. 255, negative contrast_min or sharp_min, clip_max outside 0 .. 6400, yaw_max negative or NaN (infinity switches the
+ * test off), pitch_lo > pitch_hi or a NaN among them (infinities allowed), and with S > 0 a null crops, kps, qi, qf or verdict or
+ * crops not on a 16-byte boundary.  S == 0 returns FR_OK and touches nothing.  Added under ABI 106: no existing signature changed. */
+int fr_face_quality_f16(const void* crops, const float* kps, const int32_t* slot_counts, int cap, int S, int32_t* qi, float* qf,
+                        int32_t* verdict, float min_eye2, int mean_lo, int mean_hi, int contrast_min, int sharp_min, int clip_max,
+                        float yaw_max, float pitch_lo, float pitch_hi, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- SCRFD detector ----
  * The detector of insightface's buffalo_l pack (det_10g.onnx; FaceAnalysis(name="buffalo_l"), infrenceServer.py:412-416) as
