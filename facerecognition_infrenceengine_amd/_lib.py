@@ -153,6 +153,7 @@ SIGNATURES = {
     "fr_frame_activity_refs_u8": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P]),
     "fr_track_associate_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P]),
     "fr_track_commit_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "fr_track_resolve_quality_i32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
     "fr_face_quality_f16": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
     "fr_pyramid_resize_norm":(_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "fr_dconv_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),

@@ -34,7 +34,9 @@ class CameraManager:
         ``tracks``: a ``tracks.FaceTracks``; the processor then embeds only the faces a source's previous frame did not show
         (the sources are its camera ids too).  None: every face is embedded, as ever.
         ``quality``: a ``quality.FaceQuality``; the processor then embeds only the faces judged fit and reports the others as
-        Unknown with ``quality_ok`` False.  None: no face is judged, as ever.  Not together with ``tracks`` (ValueError).
+        Unknown with ``quality_ok`` False.  None: no face is judged, as ever.  Not beside ``tracks`` (ValueError): the two
+        combine as ``tracks=FaceTracks(..., quality=q)``, tracks that judge - only fit embeddings enter their bank, and a face
+        that turns unfit for a few frames is carried on its track's held row; no further argument is needed here.
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
         waits for slow cameras once it holds a frame (latency stays that of the slowest *present* frame).
         ``reopen_after`` / ``dead_after``: consecutive failed reads before a capture is re-opened / given up."""

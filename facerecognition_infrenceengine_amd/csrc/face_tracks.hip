@@ -21,6 +21,13 @@
 //    them); the guard is a ballot of o > 0.  Nothing is read back from memory inside the loop, the state is written once at
 //    the end with one 16-byte store per array and lane.
 // 2. track_commit: one workgroup per (frame, detection slot), 128 lanes x 16 bytes per 512-float row.
+// 3. track_resolve_quality (judging tracks; include/frhip.h fr_track_resolve_quality_i32, DESIGN.md 4.5f,
+//    tests/helpers/track_quality_ref.py is the definition): between the quality launch and the one host copy, one thread per
+//    detection slot decides embed, carry or reject from (entry, need, tid) of the associate launch and the verdict, and keeps
+//    tqual i32 [S,T,4] = (has, age, id, 0): the entry holds a FIT row for the current track iff has == 1 and id == tstate.id.
+//    Safe without atomics or ordering for two reasons: each (slot, entry) is claimed by at most one detection per turn (the
+//    associate launch claims an entry once), and a call never names a slot twice (FaceTracks refuses repeats) - so no two
+//    threads touch one tqual / tstate row.  Plain vector loads and stores, no LDS, no synchronisation.
 #include "common.h"
 
 namespace {
@@ -168,7 +175,56 @@ __global__ __launch_bounds__(128) void track_commit(const int32_t* __restrict__ 
     }
 }
 
-// the checks both entries share
+constexpr int TQ_NONE = 0, TQ_EMBED = 1, TQ_CARRY = 2, TQ_REJECT = 3;
+
+// thread q = frame * cap + detection slot
+__global__ __launch_bounds__(256) void track_resolve_quality(const int32_t* __restrict__ entry, const int32_t* __restrict__ need,
+                                                             const int32_t* __restrict__ tid,
+                                                             const int32_t* __restrict__ verdict, const int32_t* __restrict__ slot,
+                                                             const int32_t* __restrict__ counts, int total, int cap, int S, int T,
+                                                             int32_t* tstate, int32_t* tqual, int max_age,
+                                                             int32_t* __restrict__ action, int32_t* __restrict__ need2,
+                                                             int32_t* __restrict__ entry2) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= total) return;
+    const int f = q / cap, j = q - f * cap;
+    int act = TQ_NONE, e = -1;
+    if (j < min(max(counts[f], 0), cap)) {
+        const int s = slot[f];
+        const bool fit = verdict[q] == 0;
+        e = entry[q];
+        if (s < 0 || s >= S || e < 0 || e >= T) {                  // A: no state behind this face
+            act = fit ? TQ_EMBED : TQ_REJECT;
+        } else {                                                    // B
+            const int64_t row = (int64_t)s * T + e;
+            int4v* qrow = reinterpret_cast<int4v*>(tqual) + row;
+            int4v tq = *qrow;
+            const int id = tid[q];
+            const bool valid = tq[0] == 1 && tq[2] == id;
+            const bool young = valid && tq[1] < max_age;
+            if (need[q] == 0 && young) {
+                act = TQ_CARRY;
+                tq[1] += 1;
+            } else {
+                if (fit) {
+                    act = TQ_EMBED;
+                    tq[0] = 1, tq[1] = 0, tq[2] = id, tq[3] = 0;
+                } else {
+                    act = TQ_REJECT;
+                    if (young) tq[1] += 1;                          // the row stays for a later carry
+                    else tq[0] = 0;
+                }
+                tstate[row * 4 + 1] = 0;                            // since: the next turn starts a new count
+            }
+            *qrow = tq;
+        }
+    }
+    action[q] = act;
+    need2[q] = act == TQ_EMBED ? 1 : 0;
+    entry2[q] = (act == TQ_EMBED || act == TQ_CARRY) ? e : -1;
+}
+
+// the checks the entries share
 int track_check(const char* who, int N, int cap, int S, int T) {
     FR_REQUIRE(N >= 0 && N <= 65535, "%s: bad size (0 .. 65535 frames)", who);
     FR_REQUIRE(cap >= 1 && cap <= 64, "%s: cap %d outside 1 .. 64 detection slots per frame", who, cap);
@@ -203,5 +259,21 @@ extern "C" int fr_track_commit_f32(const int32_t* entry, const int32_t* need, co
     track_commit<<<dim3((unsigned)cap, (unsigned)N), 128, 0, fr_stream(stream)>>>(entry, need, slot, counts, cap, S, T, bank, emb,
                                                                                   normed);
     FR_CHECK_LAUNCH("track_commit");
+    return FR_OK;
+}
+
+extern "C" int fr_track_resolve_quality_i32(const int32_t* entry, const int32_t* need, const int32_t* tid, const int32_t* verdict,
+                                            const int32_t* slot, const int32_t* counts, int N, int cap, int S, int T,
+                                            int32_t* tstate, int32_t* tqual, int max_age, int32_t* action, int32_t* need2,
+                                            int32_t* entry2, fr_stream_t stream) {
+    if (const int rc = track_check("fr_track_resolve_quality_i32", N, cap, S, T)) return rc;
+    FR_REQUIRE(max_age >= 0, "fr_track_resolve_quality_i32: max_age %d below 0 (0: never carry)", max_age);
+    if (N == 0) return FR_OK;
+    FR_REQUIRE(entry && need && tid && verdict && slot && counts && tstate && tqual && action && need2 && entry2,
+               "fr_track_resolve_quality_i32: null pointer");
+    const int total = N * cap;                                      // <= 65535 * 64
+    track_resolve_quality<<<(unsigned)((total + 255) / 256), 256, 0, fr_stream(stream)>>>(
+        entry, need, tid, verdict, slot, counts, total, cap, S, T, tstate, tqual, max_age, action, need2, entry2);
+    FR_CHECK_LAUNCH("track_resolve_quality");
     return FR_OK;
 }

@@ -420,8 +420,13 @@ class FaceAnalysis:
         face counts carries the verdicts along (no second sync), and the embed net runs over the slots that hold a face AND are
         fit.  A rejected slot keeps the unit-vector placeholder of an empty one.  The dict gains ``quality`` i32 [N,cap,8],
         ``quality_f`` f32 [N,cap,4] and ``quality_verdict`` i32 [N,cap] (0: fit, -1: no face, else the reason bits of
-        include/frhip.h fr_face_quality_f16).  Quality together with ``tracks`` is left for later and raises ValueError: the
-        tracks' commit launch expects an embedded row for every face that needs one, and a rejected face has none."""
+        include/frhip.h fr_face_quality_f16).  ``quality`` beside ``tracks`` raises ValueError; the two combine through the tracks
+        object instead: ``tracks=FaceTracks(..., quality=q)`` with ``quality=None``.  Such tracks judge:
+        associate, align of every slot, the quality launch and one launch that decides embed / carry / reject per face run
+        ahead of the one copy, which carries counts, actions, entries and verdicts; the embed net runs for the faces to embed
+        and the commit launch stores their rows and fills the carried ones, so the bank holds fit embeddings only.  The dict then
+        carries ``track_id``, ``carried``, ``track_action`` i32 [N,cap] (0 no face, 1 embedded, 2 carried, 3 rejected) and the
+        three quality tensors; a rejected slot keeps the unit-vector placeholder."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         if tracks is not None:
@@ -458,6 +463,10 @@ class FaceAnalysis:
         if compact_embed:
             if quality is not None:
                 return self._embed_fit(frames, src, boxes, scores, kps, counts, N, cap, quality)
+            if tracks is not None and getattr(tracks, "quality", None) is not None:
+                if len(camera_ids) != N:
+                    raise ValueError(f"one camera id per frame: {N} frames, {len(camera_ids)} ids")
+                return self._embed_judged(frames, src, boxes, scores, kps, counts, N, cap, tracks, camera_ids)
             if tracks is None:
                 cnt = counts.cpu()                                        # the extra sync
                 sel = (torch.arange(cap)[None, :] < cnt[:, None]).reshape(-1).nonzero().squeeze(1).to(self.device)
@@ -546,6 +555,41 @@ class FaceAnalysis:
                 emb[sel], normed[sel] = e, nm
         return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
                 "quality": qi.view(N, cap, 8), "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict.view(N, cap)}
+
+    def _embed_judged(self, frames, src, boxes, scores, kps, counts, N, cap, tracks, camera_ids):
+        """The pass of ``detect_embed_slots`` for tracks that judge (``FaceTracks(..., quality=q)``): associate, align every slot,
+        judge the crops, one launch decides embed / carry / reject per face, the ONE copy carries counts, actions, entries and
+        verdicts, the embed net runs for the faces to embed, and the commit launch stores their rows and fills the carried ones."""
+        with torch.cuda.device(self.device):
+            entry, need, tid = tracks.associate_device(boxes, counts, camera_ids)
+            # the associate launch has moved the state: should anything below fail, the bank misses this turn's rows, and no
+            # track of these cameras may be carried from it
+            try:
+                kps = kps.contiguous()
+                crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
+                self._warp_slots(frames, src, kps, counts, cap, crops)
+                qi, qf, verdict = tracks.quality.measure_device(crops, kps, counts, cap)
+                verdict = verdict.view(N, cap)
+                action, need2, entry2 = tracks.resolve_device(entry, need, tid, verdict, counts, camera_ids)
+                both = torch.cat([counts.reshape(N, 1), action, entry, verdict], dim=1).cpu()   # the same one sync, a wider row
+                cnt, act = both[:, 0], both[:, 1:1 + cap]
+                tracks.count(cnt.numpy(), None, both[:, 1 + cap:1 + 2 * cap].numpy(), act.numpy())
+                sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (act == 1)).reshape(-1).nonzero().squeeze(1).to(self.device)
+                emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
+                emb[:, 0] = 1.0                                           # empty and rejected slots: a unit vector
+                normed = emb.clone()
+                if sel.numel():
+                    fit = crops.index_select(0, sel)                      # named, not inline (see detect_embed_slots)
+                    e, nm = self.rec.forward(fit)
+                    emb[sel], normed[sel] = e, nm
+                tracks.commit_device(entry2, need2, counts, camera_ids, emb, normed)
+                carried = (action == 2).to(torch.int32)
+            except BaseException:
+                tracks.reset(camera_ids)
+                raise
+        return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
+                "track_id": tid, "carried": carried, "track_action": action, "quality": qi.view(N, cap, 8),
+                "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict}
 
     def embed_slots(self, crops):
         """Second half of ``detect_embed_slots(..., crops_out=...)``: ONE embed forward over the aligned crops of several

@@ -69,16 +69,20 @@ def _tracked(face, tid, carried, f, j):
 
 
 def _quality_columns(r):
-    """Host copies of the slot results' ``quality`` [n,cap,8], ``quality_f`` [n,cap,4] and ``quality_verdict`` [n,cap]; None for
-    a call without quality."""
+    """Host copies of the slot results' ``quality`` [n,cap,8], ``quality_f`` [n,cap,4] and ``quality_verdict`` [n,cap], and of
+    ``track_action`` [n,cap] when the call's tracks judge (None otherwise); None for a call without quality."""
     if "quality" not in r:
         return None
-    return r["quality"].cpu().numpy(), r["quality_f"].cpu().numpy(), r["quality_verdict"].cpu().numpy()
+    action = r["track_action"].cpu().numpy() if "track_action" in r else None
+    return r["quality"].cpu().numpy(), r["quality_f"].cpu().numpy(), r["quality_verdict"].cpu().numpy(), action
 
 
 def _fit(q, f, j):
-    """True for a call without quality and for a face judged fit"""
-    return q is None or q[2][f, j] == 0
+    """True for a call without quality and for a face judged fit; under judging tracks for every face but a rejected one - a
+    carried face answers with its track's held fit row whatever this frame's verdict"""
+    if q is None:
+        return True
+    return q[2][f, j] == 0 if q[3] is None else q[3][f, j] != 3
 
 
 def _judged(face, q, f, j):
@@ -505,7 +509,8 @@ class FaceRecognitionProcessor:
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
         whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``,
-        ``gate`` / ``tracks`` / ``camera_ids`` / ``quality``: as ``recognize_batch``; a face judged unfit has no candidates."""
+        ``gate`` / ``tracks`` / ``camera_ids`` / ``quality``: as ``recognize_batch``; a face judged unfit has no candidates - under tracks that
+        judge, a REJECTED face has none and a carried one is ranked on its held row."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
@@ -578,7 +583,13 @@ class FaceRecognitionProcessor:
         ``quality`` (a ``quality.FaceQuality``): behind align one launch judges every aligned face (sharpness, exposure,
         contrast, size, pose: DESIGN.md 4.5e) and the embed net runs for the fit ones only.  Every face dict gains ``"quality"``
         (the dict of ``FaceQuality.describe``) and ``"quality_ok"``; a rejected face is reported as the Unknown dict whatever the
-        scan made of its placeholder row.  Not together with ``tracks`` (ValueError)."""
+        scan made of its placeholder row.  Not together with ``tracks`` (ValueError): the two combine through the tracks object.
+
+        ``tracks=FaceTracks(..., quality=q, max_age=8)`` with ``quality=None``: tracks that judge.  The bank
+        holds a track's last FIT embedding; an unfit face is never embedded, and where its track holds such a row (not older
+        than ``max_age`` turns, no other track touching the face, no re-embed due) it is carried on it through this call's scan.
+        Each face dict has ``"track_id"``, ``"tracked"``, ``"quality"`` (this frame's measurement) and ``"quality_ok"`` (this
+        frame's verdict); a face is the Unknown dict only when it was rejected: unfit and without a row to carry."""
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
         if quality is not None and tracks is not None:
             raise ValueError("quality together with tracks is not supported yet")

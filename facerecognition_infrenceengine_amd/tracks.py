@@ -7,6 +7,10 @@ align one launch decides per detection whether it is such a face (csrc/face_trac
 fr_track_associate_f32), the embed net runs for the others only, and a second launch moves rows between the
 batch's embeddings and the bank.  What is held is the embedding, never the identity: a carried face goes through the gallery
 scan of the current call like any other row, so syncs, evictions and per-company views act on it as on a fresh one.
+
+With ``quality=FaceQuality(...)`` the tracks judge: a third launch between the quality launch and the one host copy decides per
+face embed, carry or reject (include/frhip.h fr_track_resolve_quality_i32), the bank holds a track's last FIT
+embedding only, and a face that turns unfit for a few frames keeps that row for up to ``max_age`` turns.
 """
 import threading
 
@@ -16,6 +20,7 @@ import torch
 from . import _lib
 
 DIM = 512
+NO_FACE, EMBED, CARRY, REJECT = 0, 1, 2, 3   # the action column of judging tracks (fr_track_resolve_quality_i32)
 
 
 class FaceTracks:
@@ -31,17 +36,34 @@ class FaceTracks:
 
     Camera ids are any hashable values; a new id takes a free slot, ``forget`` gives it back.  One lock orders the launches and
     the state they move, in call order, on the calling thread's current stream.  The bank takes slots x entries x 4 KB of
-    device memory: 32 MB with the defaults."""
+    device memory: 32 MB with the defaults.
+
+    ``quality`` (a ``quality.FaceQuality``) makes the tracks judge; the object is then passed as ``tracks=`` alone (``quality=``
+    beside ``tracks=`` stays a ValueError everywhere): the bank belongs to the tracks, and the quality object is the rule for
+    what may enter it.  An unfit face is never embedded; where its track holds a fit row not older than ``max_age`` turns and the
+    associate launch does not ask for an embed, the face is carried on that row, otherwise it is rejected.  ``max_age=8`` bounds
+    how long one fit row may stand in for a face that never becomes fit again; it is a judgment, not a measurement, like the
+    other defaults.  The per-entry state ``tqual`` i32 [slots,entries,4] = (has, age, id, 0) exists only with ``quality``; an
+    entry holds a fit row iff ``has == 1`` and its id is the track's, so ``forget``, ``reset`` and the reuse of a retired entry -
+    which all end in a track with a fresh id - need no work on it.  Without ``quality`` nothing changes: no launch more, no
+    state more."""
 
     _CACHE = 64                              # slot arrays kept: one per tuple of camera ids, oldest dropped first
 
-    def __init__(self, device="cuda:0", slots=256, entries=32, iou_thr=0.5, max_reuse=4, max_misses=1):
+    def __init__(self, device="cuda:0", slots=256, entries=32, iou_thr=0.5, max_reuse=4, max_misses=1, quality=None,
+                 max_age=8):
         if int(slots) < 1:
             raise ValueError("slots must be positive")
         if not 1 <= int(entries) <= 64:
             raise ValueError("entries 1 .. 64 (one lane of a wave each)")
         if not 0.0 < float(iou_thr) <= 1.0 or int(max_reuse) < 0 or int(max_misses) < 0:
             raise ValueError("iou_thr in (0, 1], max_reuse >= 0, max_misses >= 0")
+        if int(max_age) < 0:
+            raise ValueError("max_age >= 0 (0: a held row never stands in for an unfit face)")
+        if quality is not None:
+            from .quality import FaceQuality
+            if not isinstance(quality, FaceQuality):
+                raise ValueError("quality must be a quality.FaceQuality or None")
         _lib.require_gpu()
         self.lib = _lib.load()
         self.device = torch.device(device)
@@ -54,6 +76,10 @@ class FaceTracks:
         self.next_id = torch.zeros(self.slots, dtype=torch.int32, device=self.device)
         self.bank = torch.zeros((self.slots, self.entries, 2, DIM), dtype=torch.float32, device=self.device)
         self.stats = {"faces": 0, "embedded": 0, "carried": 0, "untracked": 0}
+        self.quality, self.max_age = quality, int(max_age)
+        if quality is not None:                                  # the judging tracks' state and their count of rejected faces
+            self.tqual = torch.zeros((self.slots, self.entries, 4), dtype=torch.int32, device=self.device)
+            self.stats["rejected"] = 0
         self._slot_of, self._free = {}, list(range(self.slots - 1, -1, -1))
         self._slot_arrays = {}                                   # tuple of camera ids -> int32 [N] on the device
         self._lock = threading.Lock()
@@ -154,14 +180,51 @@ class FaceTracks:
             self.lib.fr_track_commit_f32(_lib.ptr(entry), _lib.ptr(need), _lib.ptr(slot), _lib.ptr(counts), n, cap, self.slots,
                                          self.entries, _lib.ptr(self.bank), _lib.ptr(emb), _lib.ptr(normed), _lib.stream_ptr())
 
-    def count(self, counts, need, entry):
+    def resolve_device(self, entry, need, tid, verdict, counts, camera_ids):
+        """The judging tracks' launch, between ``FaceQuality.measure_device`` and the host copy: ``entry``, ``need``, ``tid`` of
+        this turn's ``associate_device`` and ``verdict`` i32 [N,cap] (0: fit) -> ``(action, need2, entry2)`` i32 [N,cap]:
+        0 no face, 1 embed, 2 carry, 3 reject, and the (need, entry) pair ``commit_device`` takes this turn.  ``since`` of
+        ``tstate`` and ``tqual`` move with the call.  Runs on the current stream, no synchronisation."""
+        if self.quality is None:
+            raise ValueError("these tracks do not judge: FaceTracks(..., quality=FaceQuality(...))")
+        ids = list(camera_ids)
+        if not (torch.is_tensor(entry) and entry.dim() == 2):
+            raise ValueError("entry must be i32 [N,cap]")
+        n, cap = entry.shape
+        for t, what in ((entry, "entry"), (need, "need"), (tid, "tid"), (verdict, "verdict")):
+            self._check(t, torch.int32, (n, cap), what)
+        self._check(counts, torch.int32, (n,), "counts")
+        if len(ids) != n:
+            raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
+        with self._lock, torch.cuda.device(self.device):
+            slot = self._slots_for(ids)
+            action = torch.empty((n, cap), dtype=torch.int32, device=self.device)
+            need2 = torch.empty_like(action)
+            entry2 = torch.empty_like(action)
+            self.lib.fr_track_resolve_quality_i32(_lib.ptr(entry), _lib.ptr(need), _lib.ptr(tid), _lib.ptr(verdict), _lib.ptr(slot),
+                                                  _lib.ptr(counts), n, cap, self.slots, self.entries, _lib.ptr(self.tstate),
+                                                  _lib.ptr(self.tqual), self.max_age, _lib.ptr(action), _lib.ptr(need2),
+                                                  _lib.ptr(entry2), _lib.stream_ptr())
+        return action, need2, entry2
+
+    def count(self, counts, need, entry, action=None):
         """Add one batch to ``stats`` from host copies of its counts [N], need and entry [N,cap] (the batch path reads them
-        back anyway): faces = embedded + carried, untracked are the embedded ones no entry was free for."""
-        counts, need, entry = np.asarray(counts), np.asarray(need), np.asarray(entry)
-        valid = np.arange(need.shape[1])[None, :] < counts[:, None]
-        faces, embedded = int(valid.sum()), int((valid & (need != 0)).sum())
+        back anyway): faces = embedded + carried, untracked are the embedded ones no entry was free for.  With the ``action``
+        column of judging tracks (``need`` is then not read): faces = embedded + carried + rejected, untracked are the faces
+        without an entry, embedded or not."""
+        counts, entry = np.asarray(counts), np.asarray(entry)
+        valid = np.arange(entry.shape[1])[None, :] < counts[:, None]
+        faces = int(valid.sum())
+        if action is None:
+            embedded = int((valid & (np.asarray(need) != 0)).sum())
+            carried, rejected = faces - embedded, None
+        else:
+            action = np.asarray(action)
+            embedded, carried, rejected = (int((valid & (action == a)).sum()) for a in (1, 2, 3))
         with self._lock:
             self.stats["faces"] += faces
             self.stats["embedded"] += embedded
-            self.stats["carried"] += faces - embedded
+            self.stats["carried"] += carried
             self.stats["untracked"] += int((valid & (entry < 0)).sum())
+            if rejected is not None:
+                self.stats["rejected"] += rejected

@@ -47,6 +47,7 @@ typedef void* fr_stream_t;
  * and for fr_pnet23_coarse_f16 / fr_pnet23_coarse_workspace_bytes / fr_pnet_pyramid_p23_coarse (the P-Net's coarse pass),
  * and for fr_track_associate_f32 / fr_track_commit_f32 (face tracks: a face's embedding carried across a camera's frames),
  * and for fr_face_quality_f16 (face quality: which aligned faces are worth the embed net),
+ * and for fr_track_resolve_quality_i32 (judging face tracks: embed, carry or reject per face, only fit rows enter the bank),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -870,6 +871,36 @@ int fr_track_associate_f32(const float* boxes, const int32_t* counts, const int3
                            int32_t* entry, int32_t* need, int32_t* tid, fr_stream_t stream);
 int fr_track_commit_f32(const int32_t* entry, const int32_t* need, const int32_t* slot, const int32_t* counts, int N, int cap,
                         int S, int T, float* bank, float* emb, float* normed, fr_stream_t stream);
+
+/* fr_track_resolve_quality_i32: the judging tracks' decision, between fr_face_quality_f16 and the one host copy of a turn.  The
+ * bank then holds a track's last FIT embedding, and a face that turns unfit for a few frames keeps the row (and so whatever
+ * identity the current call's scan gives that row).  State beside tstate, the caller's, zeroed once:
+ *   tqual   i32 [S][T][4]        (has, age, id, 0): age = turns the held row has stood in since it was embedded
+ * Entry t of slot s HOLDS A FIT ROW FOR THE CURRENT TRACK iff has == 1 and tqual.id == tstate.id.  A retired entry taken by a new
+ * track, a slot given back and taken again, and tracks dropped after a failed embed pass all end in a track with a fresh id
+ * from next_id, so the id comparison alone keeps an entry from answering with the previous person's row: nothing zeroes tqual.
+ * Inputs i32 [N][cap]: entry, need, tid as fr_track_associate_f32 wrote them THIS turn, verdict as fr_face_quality_f16 wrote it
+ * (0: fit); slot, counts i32 [N] (counts clamped to 0 .. cap).  Per detection slot (i, j) with j < counts[i], s = slot[i]:
+ *   A. entry outside [0, T) (untracked) or s outside [0, S) (stateless):  action = EMBED if verdict == 0 else REJECT; no state
+ *      is touched.
+ *   B. otherwise, valid = holds a fit row for tid:
+ *        need == 0 and valid and age < max_age:  CARRY,  age += 1; tstate stays as the associate launch wrote it
+ *        else verdict == 0:                      EMBED,  tqual = (1, 0, tid, 0), tstate.since = 0
+ *        else:                                   REJECT, tstate.since = 0; valid and age < max_age: age += 1 (the row stays for
+ *                                                a later carry), else has = 0
+ * Outputs i32 [N][cap], EVERY slot written: action (0 no face, 1 EMBED, 2 CARRY, 3 REJECT) and need2 / entry2 for
+ * fr_track_commit_f32: EMBED (1, entry), CARRY (0, entry), REJECT and no face (0, -1) - commit then touches neither the bank nor
+ * the row.  A face the associate launch wants embedded (need == 1) is never given a held row in the same turn: the crossing
+ * guard stays exactly the associate launch's.  A blurred face of a crowded frame is REJECT; a blurred face standing alone is
+ * rejected on the turn its re-embed is due and carried from the next while age < max_age.
+ * One launch on `stream`, one thread per detection slot, plain vector stores; no atomics, LDS, allocation or synchronisation:
+ * each (slot, entry) is claimed by at most one detection per turn and a call must not name a slot twice, so no two threads
+ * touch one tqual / tstate row.  Refused before any launch: T or cap outside 1 .. 64, S < 1, N outside 0 .. 65535, max_age < 0,
+ * a null pointer with N > 0.  N == 0 returns FR_OK and touches nothing.  Added under ABI 106: no existing signature changed. */
+int fr_track_resolve_quality_i32(const int32_t* entry, const int32_t* need, const int32_t* tid, const int32_t* verdict,
+                                 const int32_t* slot, const int32_t* counts, int N, int cap, int S, int T, int32_t* tstate,
+                                 int32_t* tqual, int max_age, int32_t* action, int32_t* need2, int32_t* entry2,
+                                 fr_stream_t stream);
 
 /* ---------------------------------------------------------------- face quality ----
  * Between align and embed: is this aligned face worth the embed net and a gallery scan?  (The reference embeds every detected
