@@ -154,6 +154,7 @@ SIGNATURES = {
     "fr_track_associate_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P]),
     "fr_track_commit_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "fr_track_resolve_quality_i32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "fr_track_fuse_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P]),
     "fr_face_quality_f16": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _F, _I, _I, _I, _I, _I, _F, _F, _F, _P]),
     "fr_pyramid_resize_norm":(_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "fr_dconv_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),

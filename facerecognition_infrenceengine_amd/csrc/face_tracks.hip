@@ -28,7 +28,13 @@
 //    Safe without atomics or ordering for two reasons: each (slot, entry) is claimed by at most one detection per turn (the
 //    associate launch claims an entry once), and a call never names a slot twice (FaceTracks refuses repeats) - so no two
 //    threads touch one tqual / tstate row.  Plain vector loads and stores, no LDS, no synchronisation.
-#include "common.h"
+// 4. track_fuse (track templates; include/frhip.h fr_track_fuse_f32, DESIGN.md 4.5g, tests/helpers/track_template_ref.py is the
+//    definition): behind track_commit, one wave per (frame, detection slot) keeps a ring of the entry's last K unit rows
+//    and their unit mean, and hands that mean out as the scan query.  The dot, the mean and the unit row are the pinned forms
+//    of match_scan.h / fr_mean_rows_f32, so the wave holds the row in two lane layouts: eight consecutive floats per lane for
+//    the dot, 4 + 4 for everything else.  Safe without atomics for the reasons of 3.; the row written this turn is taken
+//    from the registers that hold `normed`, never read back.
+#include "match_scan.h"
 
 namespace {
 
@@ -224,6 +230,91 @@ __global__ __launch_bounds__(256) void track_resolve_quality(const int32_t* __re
     entry2[q] = (act == TQ_EMBED || act == TQ_CARRY) ? e : -1;
 }
 
+constexpr int TF_NONE = 0, TF_STARTED = 1, TF_JOINED = 2, TF_RESTARTED = 3, TF_READ = 4;
+
+// wave (detection slot j, frame f); lane l holds floats 4l .. 4l+3 and 256 + 4l .. 256 + 4l+3 of a row (unit_row_wave4's layout)
+__global__ __launch_bounds__(64) void track_fuse(const int32_t* __restrict__ entry, const int32_t* __restrict__ need,
+                                                 const int32_t* __restrict__ tid, const int32_t* __restrict__ slot,
+                                                 const int32_t* __restrict__ counts, const float* __restrict__ normed, int cap,
+                                                 int S, int T, int K, float join_thr, float* tring, int32_t* ttmpl, float* tmean,
+                                                 float* __restrict__ query, int32_t* __restrict__ shots,
+                                                 int32_t* __restrict__ event) {
+    const int j = blockIdx.x, f = blockIdx.y, lane = threadIdx.x;
+    const int64_t q = (int64_t)f * cap + j;
+    const float4v* __restrict__ n_row = reinterpret_cast<const float4v*>(normed + q * TR_DIM);
+    const float4v n0 = n_row[lane], n1 = n_row[64 + lane];
+    float4v o0 = n0, o1 = n1;                                   // the query: the row itself unless a template answers
+    int len = 0, ev = TF_NONE;
+    const int s = slot[f];
+    const int e = j < min(max(counts[f], 0), cap) ? entry[q] : -1;
+    if (s >= 0 && s < S && e >= 0 && e < T) {                   // wave-uniform, as every branch below
+        const int64_t row = (int64_t)s * T + e;
+        int4v* trow = reinterpret_cast<int4v*>(ttmpl) + row;
+        float4v* m_row = reinterpret_cast<float4v*>(tmean + row * TR_DIM);
+        int4v tt = *trow;
+        const int id = tid[q];
+        const bool holds = tt[0] >= 1 && tt[2] == id;
+        if (need[q] != 0) {
+            bool join = false;
+            if (holds) {                                        // c = dot(n, template), lane l on floats 8l .. 8l+7
+                const float4v a0 = n_row[2 * lane], a1 = n_row[2 * lane + 1];
+                const float4v g0 = m_row[2 * lane], g1 = m_row[2 * lane + 1];
+                const float qv[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                const float c = row_dot_wave8(qv, make_float4(g0.x, g0.y, g0.z, g0.w), make_float4(g1.x, g1.y, g1.z, g1.w));
+                join = c >= join_thr;                           // false for a NaN
+            }
+            ev = !holds ? TF_STARTED : (join ? TF_JOINED : TF_RESTARTED);
+            // state this rule did not write at this K (len > K, head outside [0, K)) stays inside the ring all the same
+            const int pos = join ? (int)((unsigned)tt[1] % (unsigned)K) : 0;
+            len = join ? min(tt[0], K - 1) + 1 : 1;
+            const int head = (pos + 1) % K;
+            float4v* ring = reinterpret_cast<float4v*>(tring + row * K * TR_DIM);
+            ring[pos * (TR_DIM / 4) + lane] = n0;
+            ring[pos * (TR_DIM / 4) + 64 + lane] = n1;
+            if (len > 1) {                                      // the rows oldest first: fr_mean_rows_f32's sum, then the unit row
+                const int start = len == K ? head : 0;
+                float4v s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+                for (int i = 0; i < len; ++i) {
+                    int r = start + i;
+                    if (r >= K) r -= K;
+                    float4v v0 = n0, v1 = n1;
+                    if (r != pos) {                             // never the row this launch wrote
+                        v0 = ring[r * (TR_DIM / 4) + lane];
+                        v1 = ring[r * (TR_DIM / 4) + 64 + lane];
+                    }
+                    s0 += v0;
+                    s1 += v1;
+                }
+                s0 /= (float)len;
+                s1 /= (float)len;
+                float4 u0 = make_float4(s0.x, s0.y, s0.z, s0.w), u1 = make_float4(s1.x, s1.y, s1.z, s1.w);
+                unit_row_wave4(u0, u1);
+                o0 = float4v{u0.x, u0.y, u0.z, u0.w};
+                o1 = float4v{u1.x, u1.y, u1.z, u1.w};
+            }                                                   // len == 1: the row's own bits, no arithmetic
+            m_row[lane] = o0;
+            m_row[64 + lane] = o1;
+            if (lane == 0) {
+                const int4v out = {len, head, id, 0};
+                *trow = out;
+            }
+        } else if (holds) {
+            ev = TF_READ;
+            len = tt[0];
+            o0 = m_row[lane];
+            o1 = m_row[64 + lane];
+        }
+    }
+    float4v* __restrict__ q_row = reinterpret_cast<float4v*>(query + q * TR_DIM);
+    q_row[lane] = o0;
+    q_row[64 + lane] = o1;
+    if (lane == 0) {
+        shots[q] = len;
+        event[q] = ev;
+    }
+}
+
 // the checks the entries share
 int track_check(const char* who, int N, int cap, int S, int T) {
     FR_REQUIRE(N >= 0 && N <= 65535, "%s: bad size (0 .. 65535 frames)", who);
@@ -275,5 +366,21 @@ extern "C" int fr_track_resolve_quality_i32(const int32_t* entry, const int32_t*
     track_resolve_quality<<<(unsigned)((total + 255) / 256), 256, 0, fr_stream(stream)>>>(
         entry, need, tid, verdict, slot, counts, total, cap, S, T, tstate, tqual, max_age, action, need2, entry2);
     FR_CHECK_LAUNCH("track_resolve_quality");
+    return FR_OK;
+}
+
+extern "C" int fr_track_fuse_f32(const int32_t* entry, const int32_t* need, const int32_t* tid, const int32_t* slot,
+                                 const int32_t* counts, const float* normed, int N, int cap, int S, int T, int K, float join_thr,
+                                 float* tring, int32_t* ttmpl, float* tmean, float* query, int32_t* shots, int32_t* event,
+                                 fr_stream_t stream) {
+    if (const int rc = track_check("fr_track_fuse_f32", N, cap, S, T)) return rc;
+    FR_REQUIRE(K >= 1 && K <= 16, "fr_track_fuse_f32: K %d outside 1 .. 16 shots per template", K);
+    FR_REQUIRE(join_thr >= -1.0f && join_thr <= 1.0f, "fr_track_fuse_f32: join_thr %g outside [-1, 1]", (double)join_thr);
+    if (N == 0) return FR_OK;
+    FR_REQUIRE(entry && need && tid && slot && counts && normed && tring && ttmpl && tmean && query && shots && event,
+               "fr_track_fuse_f32: null pointer");
+    track_fuse<<<dim3((unsigned)cap, (unsigned)N), 64, 0, fr_stream(stream)>>>(entry, need, tid, slot, counts, normed, cap, S, T, K,
+                                                                               join_thr, tring, ttmpl, tmean, query, shots, event);
+    FR_CHECK_LAUNCH("track_fuse");
     return FR_OK;
 }

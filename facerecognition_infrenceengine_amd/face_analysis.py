@@ -426,7 +426,13 @@ class FaceAnalysis:
         ahead of the one copy, which carries counts, actions, entries and verdicts; the embed net runs for the faces to embed
         and the commit launch stores their rows and fills the carried ones, so the bank holds fit embeddings only.  The dict then
         carries ``track_id``, ``carried``, ``track_action`` i32 [N,cap] (0 no face, 1 embedded, 2 carried, 3 rejected) and the
-        three quality tensors; a rejected slot keeps the unit-vector placeholder."""
+        three quality tensors; a rejected slot keeps the unit-vector placeholder.
+
+        Tracks that fuse (``FaceTracks(..., template=K)``, plain or judging) add one launch right behind the
+        commit launch and three keys: ``query`` f32 [N*cap,512], the row to scan with - the unit mean of the track's last shots
+        where the face's track holds a template, else its ``normed_embedding`` row - and ``template_shots`` /
+        ``template_event`` i32 [N,cap] (shots in the template, 0: none; 0 none, 1 started, 2 joined, 3 restarted, 4 read).
+        ``embedding`` and ``normed_embedding`` stay this frame's row, or the carried one."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         if tracks is not None:
@@ -487,11 +493,12 @@ class FaceAnalysis:
                     with torch.cuda.device(self.device):
                         tracks.commit_device(entry, need, counts, camera_ids, emb, normed)
                         carried = ((need == 0) & (entry >= 0)).to(torch.int32)   # a slot past the count has entry -1
+                        fused = self._fuse(tracks, entry, need, tid, counts, camera_ids, normed)
                 except BaseException:
                     tracks.reset(camera_ids)
                     raise
-                return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
-                        "normed_embedding": normed, "track_id": tid, "carried": carried}
+                return dict({"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
+                             "normed_embedding": normed, "track_id": tid, "carried": carried}, **fused)
             emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
             emb[:, 0] = 1.0                                               # empty slots: a unit vector, never NaN downstream
             normed = emb.clone()
@@ -584,12 +591,22 @@ class FaceAnalysis:
                     emb[sel], normed[sel] = e, nm
                 tracks.commit_device(entry2, need2, counts, camera_ids, emb, normed)
                 carried = (action == 2).to(torch.int32)
+                fused = self._fuse(tracks, entry2, need2, tid, counts, camera_ids, normed)
             except BaseException:
                 tracks.reset(camera_ids)
                 raise
-        return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
-                "track_id": tid, "carried": carried, "track_action": action, "quality": qi.view(N, cap, 8),
-                "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict}
+        return dict({"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
+                     "track_id": tid, "carried": carried, "track_action": action, "quality": qi.view(N, cap, 8),
+                     "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict}, **fused)
+
+    @staticmethod
+    def _fuse(tracks, entry, need, tid, counts, camera_ids, normed):
+        """The keys that tracks which fuse (``FaceTracks(..., template=K)``) add to the slot dict, right behind the commit launch
+        and over its (entry, need) pair; {} for tracks that do not: no launch, no tensor."""
+        if not getattr(tracks, "template", 0):
+            return {}
+        query, shots, event = tracks.fuse_device(entry, need, tid, counts, camera_ids, normed)
+        return {"query": query, "template_shots": shots, "template_event": event}
 
     def embed_slots(self, crops):
         """Second half of ``detect_embed_slots(..., crops_out=...)``: ONE embed forward over the aligned crops of several

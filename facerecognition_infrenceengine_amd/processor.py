@@ -61,11 +61,30 @@ def _track_columns(r):
     return r["track_id"].cpu().numpy(), r["carried"].cpu().numpy()
 
 
-def _tracked(face, tid, carried, f, j):
-    """The face dict with ``track_id`` (-1: untracked) and ``tracked`` (True: its embedding was carried); as it is without tracks."""
+def _template_columns(r, tracks):
+    """Host copy of the slot results' ``template_shots`` [n,cap] when the call's tracks fuse, else None; the joins
+    and restarts of the event column are added to ``tracks.stats`` from the same read-back."""
+    if "template_shots" not in r:
+        return None
+    tracks.count_events(r["template_event"].cpu().numpy())
+    return r["template_shots"].cpu().numpy()
+
+
+def _tracked(face, tid, carried, f, j, shots=None):
+    """The face dict with ``track_id`` (-1: untracked) and ``tracked`` (True: its embedding was carried), and with ``shots`` (the
+    column of tracks that fuse) ``template_shots``: the shots behind the row it was scanned with, 0: its own row; as it is
+    without tracks."""
     if tid is not None:
         face["track_id"], face["tracked"] = int(tid[f, j]), bool(carried[f, j])
+    if shots is not None:
+        face["template_shots"] = int(shots[f, j])
     return face
+
+
+def _scan_rows(r):
+    """The rows of the slot results that the gallery is asked with: the tracks' ``query`` (templates) when the
+    call's tracks fuse, else ``normed_embedding``."""
+    return r["query"] if "query" in r else r["normed_embedding"]
 
 
 def _quality_columns(r):
@@ -465,8 +484,8 @@ class FaceRecognitionProcessor:
 
         def scan(vs, of):
             if k is None:
-                return vs.match_device(r["normed_embedding"], of, counts=r["counts"], seg_len=cap)
-            return vs.match_topk_device(r["normed_embedding"], of, k, counts=r["counts"], seg_len=cap)
+                return vs.match_device(_scan_rows(r), of, counts=r["counts"], seg_len=cap)
+            return vs.match_topk_device(_scan_rows(r), of, k, counts=r["counts"], seg_len=cap)
         try:
             idx, score = scan(view_set, index_of)
         except StaleViewError:                    # a sync moved the slab on meanwhile: the current views, once
@@ -490,6 +509,7 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        shots = _template_columns(r, tracks)
         q = _quality_columns(r)
         out = []
         for f in range(n):
@@ -498,7 +518,7 @@ class FaceRecognitionProcessor:
                 continue
             ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
             out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
-                                                      score[f, j], ids, metadata), tid, carried, f, j), q, f, j)
+                                                      score[f, j], ids, metadata), tid, carried, f, j, shots), q, f, j)
                         for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
@@ -530,6 +550,7 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        shots = _template_columns(r, tracks)
         q = _quality_columns(r)
         out = []
         for f in range(n):
@@ -538,7 +559,7 @@ class FaceRecognitionProcessor:
                 continue
             pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
             out.append([_judged(_tracked(_face_candidates(bbox[f, j], dscore[f, j], idx[f, j] if _fit(q, f, j) else (), score[f, j],
-                                                          pids, metadata, min_score), tid, carried, f, j), q, f, j)
+                                                          pids, metadata, min_score), tid, carried, f, j, shots), q, f, j)
                         for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 
@@ -589,7 +610,13 @@ class FaceRecognitionProcessor:
         holds a track's last FIT embedding; an unfit face is never embedded, and where its track holds such a row (not older
         than ``max_age`` turns, no other track touching the face, no re-embed due) it is carried on it through this call's scan.
         Each face dict has ``"track_id"``, ``"tracked"``, ``"quality"`` (this frame's measurement) and ``"quality_ok"`` (this
-        frame's verdict); a face is the Unknown dict only when it was rejected: unfit and without a row to carry."""
+        frame's verdict); a face is the Unknown dict only when it was rejected: unfit and without a row to carry.
+
+        ``tracks=FaceTracks(..., template=K)``, plain or judging: tracks that fuse.  A tracked face is scanned
+        with its track's template - the unit mean of the track's last K embedded shots that agreed with one another - instead
+        of this frame's row alone; a shot that does not agree with the template restarts it and is scanned as it is.  Each face
+        dict gains ``"template_shots"`` (the shots behind the scanned row, 0: the face's own row), and ``tracks.stats`` counts
+        ``"joined"`` and ``"restarted"`` shots.  The same holds for ``identify_batch`` and for mixed-company batches."""
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
         if quality is not None and tracks is not None:
             raise ValueError("quality together with tracks is not supported yet")
@@ -605,8 +632,7 @@ class FaceRecognitionProcessor:
                                                quality)
         if r is None:                                                        # no frame active
             return [UNCHANGED] * len(frames)
-        matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
-                                                     r["normed_embedding"])
+        matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata, _scan_rows(r))
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
         cap = r["bbox"].shape[1]
         counts = r["counts"].cpu().numpy()                                   # the one synchronisation
@@ -614,11 +640,12 @@ class FaceRecognitionProcessor:
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         dscore = r["det_score"].cpu().numpy()
         tid, carried = _track_columns(r)
+        shots = _template_columns(r, tracks)
         q = _quality_columns(r)
         out = []
         for f in range(n):
             out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
-                                                      score[f, j], matcher.ids, metadata), tid, carried, f, j), q, f, j)
+                                                      score[f, j], matcher.ids, metadata), tid, carried, f, j, shots), q, f, j)
                         for j in range(int(counts[f]))])
         return _spread(out, keep, len(frames))
 

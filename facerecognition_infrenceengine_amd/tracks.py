@@ -11,6 +11,9 @@ scan of the current call like any other row, so syncs, evictions and per-company
 With ``quality=FaceQuality(...)`` the tracks judge: a third launch between the quality launch and the one host copy decides per
 face embed, carry or reject (include/frhip.h fr_track_resolve_quality_i32), the bank holds a track's last FIT
 embedding only, and a face that turns unfit for a few frames keeps that row for up to ``max_age`` turns.
+
+With ``template=K`` the tracks fuse: behind the commit launch one more launch keeps a ring of the track's last K unit embeddings
+and answers each tracked face with their unit mean, the scan ``query`` (include/frhip.h fr_track_fuse_f32).
 """
 import threading
 
@@ -21,6 +24,7 @@ from . import _lib
 
 DIM = 512
 NO_FACE, EMBED, CARRY, REJECT = 0, 1, 2, 3   # the action column of judging tracks (fr_track_resolve_quality_i32)
+T_NONE, T_STARTED, T_JOINED, T_RESTARTED, T_READ = 0, 1, 2, 3, 4   # the event column of fusing tracks (fr_track_fuse_f32)
 
 
 class FaceTracks:
@@ -46,12 +50,25 @@ class FaceTracks:
     other defaults.  The per-entry state ``tqual`` i32 [slots,entries,4] = (has, age, id, 0) exists only with ``quality``; an
     entry holds a fit row iff ``has == 1`` and its id is the track's, so ``forget``, ``reset`` and the reuse of a retired entry -
     which all end in a track with a fresh id - need no work on it.  Without ``quality`` nothing changes: no launch more, no
-    state more."""
+    state more.
+
+    ``template`` (0 .. 16; 0: off, nothing is allocated and no launch is added) makes the tracks fuse: each entry keeps the unit
+    embeddings of its track's last ``template`` shots and their unit mean, the template, and ``fuse_device`` hands that mean out
+    as the row the gallery scan is asked with.  A new shot joins the template only when its dot with it reaches ``join_thr``
+    (-1 .. 1); otherwise the template starts over from that shot alone, which is then returned unblended - the guard against
+    mixing two people into one row.  With ``template=1`` the template is always the last embedded row and the query equals the
+    normed embedding bit for bit.  The state ``tring`` f32 [slots,entries,template,512], ``ttmpl`` i32 [slots,entries,4] =
+    (len, head, id, 0) and ``tmean`` f32 [slots,entries,512] takes slots x entries x (template + 1) x 2 KB of device memory
+    (and 16 bytes per entry): 176 MB with the default slots and entries at ``template=10``.  An entry holds a template iff
+    ``len >= 1`` and its id is the track's, so ``forget``, ``reset`` and a reused entry need no work on it either.
+    ``join_thr=0.4`` is the reference's pose-consistency figure for "two shots of one person", and a depth of 10 is the ring
+    depth of its ``UnknownPerson`` (peopleCount.py:63); both are a judgment here, not a measurement: the weights of this tree are
+    synthetic, and neither the error rate of the join test nor the gain of any depth on real video is known."""
 
     _CACHE = 64                              # slot arrays kept: one per tuple of camera ids, oldest dropped first
 
     def __init__(self, device="cuda:0", slots=256, entries=32, iou_thr=0.5, max_reuse=4, max_misses=1, quality=None,
-                 max_age=8):
+                 max_age=8, template=0, join_thr=0.4):
         if int(slots) < 1:
             raise ValueError("slots must be positive")
         if not 1 <= int(entries) <= 64:
@@ -60,6 +77,10 @@ class FaceTracks:
             raise ValueError("iou_thr in (0, 1], max_reuse >= 0, max_misses >= 0")
         if int(max_age) < 0:
             raise ValueError("max_age >= 0 (0: a held row never stands in for an unfit face)")
+        if not 0 <= int(template) <= 16:
+            raise ValueError("template 0 .. 16 shots (0: off)")
+        if not -1.0 <= float(join_thr) <= 1.0:                   # false for a NaN
+            raise ValueError("join_thr in [-1, 1]")
         if quality is not None:
             from .quality import FaceQuality
             if not isinstance(quality, FaceQuality):
@@ -80,6 +101,12 @@ class FaceTracks:
         if quality is not None:                                  # the judging tracks' state and their count of rejected faces
             self.tqual = torch.zeros((self.slots, self.entries, 4), dtype=torch.int32, device=self.device)
             self.stats["rejected"] = 0
+        self.template, self.join_thr = int(template), float(join_thr)
+        if self.template:                                        # the fusing tracks' state and their counts of joins and restarts
+            self.tring = torch.zeros((self.slots, self.entries, self.template, DIM), dtype=torch.float32, device=self.device)
+            self.ttmpl = torch.zeros((self.slots, self.entries, 4), dtype=torch.int32, device=self.device)
+            self.tmean = torch.zeros((self.slots, self.entries, DIM), dtype=torch.float32, device=self.device)
+            self.stats["joined"] = self.stats["restarted"] = 0
         self._slot_of, self._free = {}, list(range(self.slots - 1, -1, -1))
         self._slot_arrays = {}                                   # tuple of camera ids -> int32 [N] on the device
         self._lock = threading.Lock()
@@ -206,6 +233,43 @@ class FaceTracks:
                                                   _lib.ptr(self.tqual), self.max_age, _lib.ptr(action), _lib.ptr(need2),
                                                   _lib.ptr(entry2), _lib.stream_ptr())
         return action, need2, entry2
+
+    def fuse_device(self, entry, need, tid, counts, camera_ids, normed):
+        """The fusing tracks' launch, right behind ``commit_device`` and over the same ``entry`` / ``need`` (``entry2`` /
+        ``need2`` under judging tracks), ``tid`` of this turn's ``associate_device`` and the slot-layout ``normed`` f32
+        [N*cap,512] the commit left -> ``(query, shots, event)``: f32 [N*cap,512], the row to scan with (the track's template
+        where it has one, else the ``normed`` row), and i32 [N,cap]: the shots the template holds (0: none) and 0 none,
+        1 started, 2 joined, 3 restarted, 4 read.  ``tring``, ``ttmpl`` and ``tmean`` move with the call.  Runs on the current
+        stream, no synchronisation."""
+        if not self.template:
+            raise ValueError("these tracks do not fuse: FaceTracks(..., template=K)")
+        ids = list(camera_ids)
+        if not (torch.is_tensor(entry) and entry.dim() == 2):
+            raise ValueError("entry must be i32 [N,cap]")
+        n, cap = entry.shape
+        for t, what in ((entry, "entry"), (need, "need"), (tid, "tid")):
+            self._check(t, torch.int32, (n, cap), what)
+        self._check(counts, torch.int32, (n,), "counts")
+        self._check(normed, torch.float32, (n * cap, DIM), "normed")
+        if len(ids) != n:
+            raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
+        with self._lock, torch.cuda.device(self.device):
+            slot = self._slots_for(ids)
+            query = torch.empty((n * cap, DIM), dtype=torch.float32, device=self.device)
+            shots = torch.empty((n, cap), dtype=torch.int32, device=self.device)
+            event = torch.empty_like(shots)
+            self.lib.fr_track_fuse_f32(_lib.ptr(entry), _lib.ptr(need), _lib.ptr(tid), _lib.ptr(slot), _lib.ptr(counts),
+                                       _lib.ptr(normed), n, cap, self.slots, self.entries, self.template, self.join_thr,
+                                       _lib.ptr(self.tring), _lib.ptr(self.ttmpl), _lib.ptr(self.tmean), _lib.ptr(query),
+                                       _lib.ptr(shots), _lib.ptr(event), _lib.stream_ptr())
+        return query, shots, event
+
+    def count_events(self, event):
+        """Add one batch's joins and restarts to ``stats`` from a host copy of its event column [N,cap]."""
+        event = np.asarray(event)
+        with self._lock:
+            self.stats["joined"] += int((event == T_JOINED).sum())
+            self.stats["restarted"] += int((event == T_RESTARTED).sum())
 
     def count(self, counts, need, entry, action=None):
         """Add one batch to ``stats`` from host copies of its counts [N], need and entry [N,cap] (the batch path reads them

@@ -48,6 +48,7 @@ typedef void* fr_stream_t;
  * and for fr_track_associate_f32 / fr_track_commit_f32 (face tracks: a face's embedding carried across a camera's frames),
  * and for fr_face_quality_f16 (face quality: which aligned faces are worth the embed net),
  * and for fr_track_resolve_quality_i32 (judging face tracks: embed, carry or reject per face, only fit rows enter the bank),
+ * and for fr_track_fuse_f32 (track templates: a track's last K shots fused into one scan query),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -901,6 +902,44 @@ int fr_track_resolve_quality_i32(const int32_t* entry, const int32_t* need, cons
                                  const int32_t* slot, const int32_t* counts, int N, int cap, int S, int T, int32_t* tstate,
                                  int32_t* tqual, int max_age, int32_t* action, int32_t* need2, int32_t* entry2,
                                  fr_stream_t stream);
+
+/* fr_track_fuse_f32: track templates, behind fr_track_commit_f32.  An entry keeps the unit embeddings of its track's last K shots
+ * and their unit mean, and that mean - not this frame's row alone - is what the gallery scan is asked with.  (The reference has
+ * this rule for unknown people only: UnknownPerson keeps a 10-deep ring and compares against its mean, peopleCount.py:63-79.)
+ * A shot joins a template only if it agrees with it; otherwise the template starts over from that shot alone, so a shot that
+ * fails the test is answered with the very bits the embed net gave.  State beside the bank, the caller's, zeroed once, K in 1 .. 16:
+ *   tring   f32 [S][T][K][512]   the unit (normed) embeddings of the entry's last shots
+ *   ttmpl   i32 [S][T][4]        (len, head, id, 0)
+ *   tmean   f32 [S][T][512]      the template, a unit row
+ * Entry t of slot s HOLDS A TEMPLATE FOR TRACK id iff len >= 1 and ttmpl.id == id; as with tqual, the id comparison alone covers a
+ * slot given back, dropped tracks and a retired entry taken by a new track: nothing zeroes this state.
+ * Inputs: entry, need i32 [N][cap] as fr_track_commit_f32 got them this turn (under judging tracks entry2 / need2), tid of the
+ * associate launch, slot, counts i32 [N] (clamped to 0 .. cap), normed f32 [N*cap][512] after the commit launch.  Per detection
+ * slot q = (i, j) with j < counts[i], s = slot[i] inside [0, S) and e = entry[q] inside [0, T), n = row q of normed:
+ *   need != 0 (embedded this turn):
+ *     the entry holds a template for tid[q]:  c = dot(n, tmean[s][e]), lane l of a wave taking floats 8l .. 8l+7: eight rounded
+ *         products summed left to right, then the xor-shuffle sum over offsets 32 .. 1 (the dot of fr_gallery_first_above_f32)
+ *       c >= join_thr:                JOINED     ring[head] = n, head = (head + 1) % K, len = min(len + 1, K)
+ *       else (a NaN included):        RESTARTED  ring[0] = n, head = 1 % K, len = 1
+ *     it does not hold one:           STARTED    as RESTARTED, and ttmpl.id = tid[q]
+ *     then tmean[s][e] = n's bits when len == 1 (no arithmetic), otherwise the ring rows OLDEST FIRST (from head when len == K,
+ *     else from 0) summed in that order from 0.f, divided by (float)len (fr_mean_rows_f32), then v / ||v|| in the arithmetic of
+ *     fr_l2norm_rows_f32;  query[q] = tmean[s][e], shots[q] = len
+ *   need == 0 (carried):
+ *     the entry holds a template for tid[q]:  READ  query[q] = tmean[s][e], shots[q] = len; no state moves
+ *     otherwise:                                    query[q] = n, shots[q] = 0, event NONE
+ * Every other slot (untracked, stateless, rejected, past the count): query[q] = normed[q], shots[q] = 0, event NONE.  Every row
+ * of query f32 [N*cap][512], shots and event i32 [N][cap] is written (0 NONE, 1 STARTED, 2 JOINED, 3 RESTARTED, 4 READ); no other
+ * row of the state is touched.  With K = 1 the template is the last embedded row: query == normed bit for bit.  State this rule
+ * did not write at this K (len > K, head outside [0, K)) gives an unspecified template, every access still inside the arrays.
+ * One launch on `stream`, one wave per (frame, detection slot), plain vector loads and stores; no atomics, LDS, allocation or
+ * synchronisation: each (slot, entry) is claimed by at most one detection per turn and a call must not name a slot twice.  The
+ * row written this turn is never read back from memory.  Refused before any launch: T or cap outside 1 .. 64, S < 1, N outside
+ * 0 .. 65535, K outside 1 .. 16, join_thr outside [-1, 1] (a NaN included), a null pointer with N > 0.  N == 0 returns FR_OK and
+ * touches nothing.  Added under ABI 106: no existing signature changed. */
+int fr_track_fuse_f32(const int32_t* entry, const int32_t* need, const int32_t* tid, const int32_t* slot, const int32_t* counts,
+                      const float* normed, int N, int cap, int S, int T, int K, float join_thr, float* tring, int32_t* ttmpl,
+                      float* tmean, float* query, int32_t* shots, int32_t* event, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- face quality ----
  * Between align and embed: is this aligned face worth the embed net and a gallery scan?  (The reference embeds every detected
