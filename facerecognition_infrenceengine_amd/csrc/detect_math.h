@@ -29,6 +29,19 @@ __device__ __forceinline__ float bilerp(float p00, float p01, float p10, float p
     return (1.0f - wy) * top + wy * bot;
 }
 
+// ------------------------------------------------------------------ max of raw MFMA sums (pools done in registers)
+// max(x, y) as v_med3_f32(x, y, +inf) with the +inf in a register the compiler cannot see through: ONE instruction - fmaxf (and
+// med3 with a literal +inf, which hipcc folds to it) puts a canonicalising self-max in front of every operand of unknown origin
+// (MFMA results; never NaN here).  NOT an inline-asm v_max_f32: the hazard recogniser does not see an asm statement's operands,
+// and an asm max placed right behind the MFMA that produces its operand read the register before the matrix pipe had written it
+// (round 4: the first of four maxima wrong, in interior tiles only - elsewhere a select sat in between).
+__device__ __forceinline__ float opaque_inf() {
+    float r;
+    asm("v_mov_b32 %0, 0x7f800000" : "=v"(r));
+    return r;
+}
+__device__ __forceinline__ float vmax(float x, float y, float pinf) { return __builtin_amdgcn_fmed3f(x, y, pinf); }
+
 // ------------------------------------------------------------------ split-precision operands: x = hi + lo in f16
 // Element e of hi and lo gets the split of x (hi and lo are f16 vectors or arrays).
 template <class V>

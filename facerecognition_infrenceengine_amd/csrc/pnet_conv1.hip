@@ -48,18 +48,6 @@ __device__ __forceinline__ float dpp_shr1(float v) {        // value of lane - 1
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, true));
 }
 
-// max(x, y) as v_med3_f32(x, y, +inf) with the +inf in a register the compiler cannot see through: ONE instruction - fmaxf (and
-// med3 with a literal +inf, which hipcc folds to it) puts a canonicalising self-max in front of every operand of unknown origin
-// (MFMA results; never NaN here).  NOT an inline-asm v_max_f32: the hazard recogniser does not see an asm statement's operands,
-// and an asm max placed right behind the MFMA that produces its operand read the register before the matrix pipe had written it
-// (round 4: the first of four maxima wrong, in interior tiles only - elsewhere a select sat in between).
-__device__ __forceinline__ float opaque_inf() {
-    float r;
-    asm("v_mov_b32 %0, 0x7f800000" : "=v"(r));
-    return r;
-}
-__device__ __forceinline__ float vmax(float x, float y, float pinf) { return __builtin_amdgcn_fmed3f(x, y, pinf); }
-
 // Lerp tables of a tile: the source rows / columns and weights of its (rows + 2) level rows and 66 level columns are
 // computed ONCE per tile by 84 threads (not once per pixel by everybody) and read back from LDS.
 //   row entry {i0 * FW * 3, i1 * FW * 3, wy, valid}    column entry {x0 * 3, wx, x1 != x0, valid}

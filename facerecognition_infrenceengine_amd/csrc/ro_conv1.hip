@@ -14,6 +14,11 @@
 // blocks fit a CU.  A block walks 8 / 4 consecutive slots and fetches the next valid slot's source bytes (raw, into
 // registers) under the current slot's conv.  When every PReLU slope is >= 0 the raw sums are pooled first and
 // activated after (the same bits, a ninth of the bias / PReLU work); otherwise every pixel is activated before the pool.
+// The O-Net's F16 form on the batch path is the STRIP form: the conv map never leaves registers.  Each of the block's four waves walks
+// a strip of 16 conv columns down the crop, pools a row's raw sums along the row with two DPP moves, keeps the running max of the
+// open 3-row window, and writes a pooled row as whole 128-byte pixels - no conv tile in LDS (33 of the tile form's 74 KB), no
+// barrier between "crop image in LDS" and "every wave done with it" (the tile form: 24 per crop).  The tile form stays as
+// conv_f16 = 2, for the R-Net (whose 22 columns fill two 16-column strips badly) and for launches of one slot per block.
 // Count-aware like the other R-/O-Net layers: a slot >= counts[frame] does no work and leaves its output unwritten.
 #include "detect_math.h"
 
@@ -22,6 +27,11 @@ constexpr int RC1_PB_R = 3;        // R-Net (64 x 512 random boxes): PB x RPB 4x
 constexpr int RC1_RPB_R = 16;
 constexpr int RC1_PB_O = 2;        // O-Net (64 x 64 boxes): 2x4 281, 2x8 279, 1x4 317, 3x4 446, 2x2 288
 constexpr int RC1_RPB_O = 4;
+// Strip form (O-Net, conv_f16 = 1): slots per block and waves per SIMD the registers are held to, us per 64 x 64 boxes beside the
+// tile form's 285 in the same interleaved rounds (profiles/crop_conv1_strip.txt): RPB x waves 4x3 266, 2x3 250, 1x3 254; 2x4 240 and
+// 1x4 237 (128 VGPRs, the 40 KB of LDS then fit four blocks a CU) only with 9 VGPRs spilled, so not taken
+constexpr int RC1_RPB_OS = 2;
+constexpr int RC1_OCC_OS = 3;
 
 namespace {
 
@@ -54,10 +64,12 @@ __device__ __forceinline__ float vmax_r(float x, float y) {        // no canonic
 // c' = 3: two K = 32 steps, a B fragment = 16 B (2 pixels) at an 8-byte aligned address.  6 MFMAs of 16 cycles per 16 pixels x
 // 16 couts against 27 x 4 = 108 4x4x1 MFMAs of 8 cycles per 64 pixels x 16 couts: ~2.8x fewer matrix cycles, and the work
 // splits in tiles of 16 pixels instead of units of 64.  The split format's error from the f32 form: DESIGN.md 4.3a (the exact pass covers the threshold).
-template <int S, int NG, int COUT, int PB, int RPB, bool SPLIT = false, bool LIST = false, bool F16 = false>
-__global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
+template <int S, int NG, int COUT, int PB, int RPB, bool SPLIT = false, bool LIST = false, bool F16 = false, bool STRIP = false>
+__global__ __launch_bounds__(256, STRIP ? RC1_OCC_OS : 1) void crop_conv1_kernel(RoArgs a) {
     constexpr int C = S - 2;                                     // conv map size
     constexpr int P = (C - 3 + 1) / 2 + 1;                       // ceil((C - 3) / 2) + 1 pooled size (ceil mode)
+    // STRIP: a wave per column strip of 7 pooled columns, so four strips cover the map (the O-Net's 23 = 7 + 7 + 7 + 2)
+    static_assert(!STRIP || (F16 && SPLIT && !LIST && (P + 6) / 7 == 4 && C % 2 == 0 && P == C / 2), "strip form");
     // conv tile pixel stride in floats: 16-B rows whose stride is NOT a multiple of 32 words, so that 8 consecutive lanes'
     // 16-byte accesses fall into 8 different bank groups (28 words for R-Net's 28 channels as they are; 32 + 4 for O-Net)
     constexpr int CS = (NG * 4) % 32 ? NG * 4 : NG * 4 + 4;
@@ -68,12 +80,14 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
     constexpr int NW = (27 * NG + 15) / 16;                      // weight registers
     constexpr int XPX = S * S + S + 8;                           // F16: pixels per plane incl. the zero slack behind the image (kh = 3, kw' = 3 read there)
     constexpr int XFLOATS = F16 ? (2 * XPX * 8 / 4 + 3) & ~3 : (S * S * 3 + 3) & ~3;
+    // F16: the last fragment read (conv row C - 1, column C - 1, kh = 3, kw' = 2..3) ends inside the zero slack
+    static_assert(!F16 || (C + 2) * S + C + 3 <= XPX, "slack behind the crop image");
     extern __shared__ __attribute__((aligned(16))) float lds_ro[];
     float* xin = lds_ro;                                         // [S*S][3] f32, or F16: hi | lo planes of [XPX][4] f16
     int4v* tab = reinterpret_cast<int4v*>(lds_ro + XFLOATS);     // [2][2 S] lerp tables (double-buffered)
     float4* sbox_mem = reinterpret_cast<float4*>(tab + 4 * S);  // [RPB] the block's boxes (one global read, off the per-slot path)
     int* sorig = reinterpret_cast<int*>(sbox_mem + RPB);         // [RPB] the slots' numbers in the cascade's slot space (LIST: list[s])
-    float* ot = reinterpret_cast<float*>(sorig + ((RPB + 3) & ~3));      // [BR * C][CS] conv tile
+    float* ot = reinterpret_cast<float*>(sorig + ((RPB + 3) & ~3));      // [BR * C][CS] conv tile (not in the STRIP form)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // a block's RPB consecutive slots lie in ONE frame (the host picks RPB | cap), and a frame's candidates are a prefix of
     // its slots: the block's valid slots are the interval [slot, s_end) - one read of the count, no search
@@ -109,7 +123,10 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int kh = 2 * st + (kq_ >> 1), kw = (kq_ & 1) * 2 + (j >> 2), c = j & 3, co = ct * 16 + li_;
+                    // A row li_ = the cout of output lane row li_ >> 2, element li_ & 3.  STRIP: that lane's 4 + 4 sums of the two
+                    // cout tiles are channels 8 kq .. 8 kq + 7 (16 contiguous bytes of the split map), not 4 kq .. and 16 + 4 kq ..
+                    const int kh = 2 * st + (kq_ >> 1), kw = (kq_ & 1) * 2 + (j >> 2), c = j & 3;
+                    const int co = STRIP ? 8 * (li_ >> 2) + 4 * ct + (li_ & 3) : ct * 16 + li_;
                     const float w = (kh < 3 && kw < 3 && c < 3 && co < NG * 4) ? a.w[((kh * 3 + kw) * 3 + c) * (NG * 4) + co] : 0.f;
                     split_f16(w, wfh[st][ct], wfl[st][ct], j);
                 }
@@ -130,6 +147,14 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
     //   two loads in bits (last bytes of the last frame); -1: the whole pixel is zero (empty box)
     unsigned long long rq0[NPF], rq1[NPF];
     int rfl[NPF];
+    // STRIP: the thread index behind a wall the optimiser cannot see through, taken anew in every slot's load / store.  Without it
+    // the per-pixel index arithmetic (NPF x row, column, table and image addresses) is hoisted out of the slot loop and held in
+    // registers across the conv (spills at the 168 VGPRs of three waves per SIMD; 144 and none with it).  Recomputing it is a few VALU ops.
+    auto strip_tid = [&]() __attribute__((always_inline)) {
+        int t = tid;
+        if constexpr (STRIP) asm volatile("" : "+v"(t));
+        return t;
+    };
     bool edge = true;                                            // wave-uniform: some pixel is not the plain two-column case
     auto make_tab = [&](int sl, int buf) __attribute__((always_inline)) {
         if (tid < 2 * S) {
@@ -154,9 +179,10 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
         const uint8_t* fr = a.frames + (int64_t)f * a.H * a.W * 3;
         const int lim = f == a.nframes - 1 ? a.H * a.W * 3 - 8 : 0x7fffffff;
         bool special = false;
+        const int tix = strip_tid();
 #pragma unroll
         for (int u = 0; u < NPF; ++u) {
-            const int t = min(tid + u * 256, S * S - 1);         // threads past the crop: any valid pixel, never stored
+            const int t = min(tix + u * 256, S * S - 1);         // threads past the crop: any valid pixel, never stored
             const int oy = t / S, ox = t - oy * S;
             const int4v re = tab[buf * 2 * S + oy], ce = tab[buf * 2 * S + S + ox];
             rq0[u] = rq1[u] = 0; rfl[u] = -1;
@@ -188,9 +214,10 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
     };
     auto store_crop_as = [&](int buf, auto EDGE) __attribute__((always_inline)) {
         constexpr bool E = decltype(EDGE)::value;
+        const int tix = strip_tid();
 #pragma unroll
         for (int u = 0; u < NPF; ++u) {
-            const int t = tid + u * 256;
+            const int t = tix + u * 256;
             if (t >= S * S) continue;
             const int oy = t / S, ox = t - oy * S;
             const float wy = __int_as_float(tab[buf * 2 * S + oy][2]), wx = __int_as_float(tab[buf * 2 * S + S + ox][2]);
@@ -238,6 +265,113 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
     __syncthreads();                                             // the crop and the next slot's tables are in LDS
     if (nslot >= 0) load_crop(nslot, buf ^ 1);                   // global loads fly under this slot's conv
 
+    if constexpr (STRIP) {
+        // ---- strip form: wave st walks the conv rows of the strip of 16 columns from c0 = 14 st, top to bottom, and pools the raw
+        // sums in registers: no conv map in LDS, no barrier between the rows.  Lane li holds column c0 + li, couts 8 kq + 4 ct .. + 3
+        // of cout tile ct.  The raw sums of a pixel are the tile form's bits (same fragments, same MFMA order; an output element
+        // depends on its own row and column operands only).
+        typedef half8 half8_a8 __attribute__((aligned(8)));
+        const int li_ = lane & 15, kq_ = lane >> 4, st = wave;
+        const int col = 14 * st + li_;
+        const bool incol = col < C;
+        // the read column is clamped into the map: the fragment reads stay where the tile form's go (image + slack)
+        const unsigned char* pb0 = reinterpret_cast<const unsigned char*>(xin) + ((kq_ >> 1) * S + min(col, C - 1) + 2 * (kq_ & 1)) * 8;
+        const float pinf = opaque_inf();
+        const int px = 7 * st + (li_ >> 1);                  // pooled column of lanes 2j, 2j + 1: max over lanes 2j, 2j + 1, 2j + 2
+        const bool odd = li_ & 1;
+        const bool emits = li_ < 14 && px < P;
+        // the slot's map: a wave-uniform base and the lane's 32-bit byte offset.  Even lanes store their 8 channels' hi, odd lanes
+        // the lo of the even lane before them: ONE 16-byte store per lane writes whole 128-byte pixels
+        unsigned char* os = a.ys + (int64_t)slot * (P * P * 128);
+        const int ol = min(px, P - 1) * 128 + (li_ & 1) * 64 + kq_ * 16;
+        // the lane's bias / slope quad of cout tile ct is read where it is used (cached), not held across the rows (16 VGPRs)
+        auto quad = [&](const float* q, int ct) __attribute__((always_inline)) {
+            int kq = kq_;
+            asm volatile("" : "+v"(kq));                     // the address is made here, not kept (a VGPR pair per quad)
+            return *reinterpret_cast<const float4v*>(q + min(8 * kq + 4 * ct, NG * 4 - 4));
+        };
+        // one conv row, pooled along the row: lane 2j of the 16-lane row hands `use` pooled column j's max of this row, per cout tile
+        auto conv_row = [&](int row, auto use) __attribute__((always_inline)) {
+            const unsigned char* pb = pb0 + row * S * 8;
+            const half8 h0 = *reinterpret_cast<const half8_a8*>(pb), l0 = *reinterpret_cast<const half8_a8*>(pb + XPX * 8);
+            const half8 h1 = *reinterpret_cast<const half8_a8*>(pb + 2 * S * 8), l1 = *reinterpret_cast<const half8_a8*>(pb + (XPX + 2 * S) * 8);
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                float4v d = {0.f, 0.f, 0.f, 0.f};
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfl[0][ct], h0, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfh[0][ct], l0, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfl[1][ct], h1, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfh[1][ct], l1, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfh[0][ct], h0, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_f32_16x16x32_f16(wfh[1][ct], h1, d, 0, 0, 0);
+                if (!mono) {                                 // any slope: activate every pixel, then pool
+                    d += quad(a.bias, ct);
+                    const float4v sv = quad(a.slope, ct);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d[e] = d[e] > 0.f ? d[e] : d[e] * sv[e];
+                }
+                float4v h;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    // a column past the map: -inf (the tile form clamps it onto column C - 1, which every such window holds)
+                    const float v = incol ? d[e] : -INFINITY;
+                    // lanes li + 1, li + 2 of the 16-lane row (row_shl:1, row_shl:2).  The moves are pinned here, where every
+                    // lane is enabled: sunk under the emitting lanes' EXEC mask their source lanes would read as 0
+                    // (pnet_conv1.hip).  The maxima are v_med3 (vmax), never an asm max behind the MFMA.
+                    float v1 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xf, 0xf, true));
+                    float v2 = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x102, 0xf, 0xf, true));
+                    asm volatile("" : "+v"(v1), "+v"(v2));
+                    h[e] = vmax(vmax(v, v1, pinf), v2, pinf);
+                }
+                use(ct, h);
+            }
+        };
+        // pooled row prow of the strip: the tile form's epilogue on the pooled quads (every lane computes, lanes 2j hold pixel j)
+        auto emit = [&](const float4v (&mx)[2], int prow) __attribute__((always_inline)) {
+            half8 hi, lo;
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                float4v m = mx[ct];
+                if (mono) {
+                    m += quad(a.bias, ct);
+                    const float4v sv = quad(a.slope, ct);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) m[e] = m[e] > 0.f ? m[e] : m[e] * sv[e];
+                }
+                const bool real = 8 * kq_ + 4 * ct < COUT;  // else: the K padding (channels COUT .. 31), zero
+#pragma unroll
+                for (int e = 0; e < 4; ++e) split_f16(real ? m[e] : 0.f, hi, lo, 4 * ct + e);
+            }
+            const int4v hv = __builtin_bit_cast(int4v, hi), lv = __builtin_bit_cast(int4v, lo);
+            int4v o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                // lane - 1's lo (row_shr:1), moved while every lane is enabled and pinned in front of the select (pnet_conv1.hip)
+                int t = __builtin_amdgcn_update_dpp(0, lv[e], 0x111, 0xf, 0xf, true);
+                asm volatile("" : "+v"(t));
+                o[e] = odd ? t : hv[e];
+            }
+            if (emits) *reinterpret_cast<int4v*>(os + (ol + prow * (P * 128))) = o;
+        };
+        auto max4 = [&](float4v x, float4v y) __attribute__((always_inline)) {
+            float4v r;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r[e] = vmax(x[e], y[e], pinf);
+            return r;
+        };
+        // conv rows 2p, 2p + 1, 2p + 2 make pooled row p (C is even: the last window holds rows C - 2, C - 1 only);
+        // row 2p + 2 also opens window p + 1.  rm: the open window's running max
+        float4v rm[2], t[2];
+        conv_row(0, [&](int ct, float4v h) { rm[ct] = h; });
+        conv_row(1, [&](int ct, float4v h) { rm[ct] = max4(rm[ct], h); });
+#pragma unroll 1
+        for (int rp = 1; rp < C / 2; ++rp) {
+            conv_row(2 * rp, [&](int ct, float4v h) { t[ct] = max4(rm[ct], h); rm[ct] = h; });
+            emit(t, rp - 1);
+            conv_row(2 * rp + 1, [&](int ct, float4v h) { rm[ct] = max4(rm[ct], h); });
+        }
+        emit(rm, P - 1);
+    } else {
     float* yo = a.y + (int64_t)slot * P * P * COUT;
     for (int band = 0; band < NBAND; ++band) {
         const int r0 = band * 2 * PB;                                         // first conv row of the band
@@ -368,19 +502,20 @@ __global__ __launch_bounds__(256) void crop_conv1_kernel(RoArgs a) {
         }
         if (band + 1 < NBAND) __syncthreads();                               // the next band overwrites the conv tile
     }
+    }
     __syncthreads();                                             // every wave is done with this slot's crop and conv tile
     slot = nslot;
     }
 }
 
-template <int S, int NG, int COUT, int PB, int RPB, bool SPLIT = false, bool LIST = false, bool F16 = false>
+template <int S, int NG, int COUT, int PB, int RPB, bool SPLIT = false, bool LIST = false, bool F16 = false, bool STRIP = false>
 int launch_ro(const RoArgs& a, int nslots, hipStream_t s) {
     constexpr int C = S - 2;
     constexpr int rows = 2 * PB + 1 < C ? 2 * PB + 1 : C;
     constexpr int CS = (NG * 4) % 32 ? NG * 4 : NG * 4 + 4;
     constexpr int XFLOATS = F16 ? (2 * (S * S + S + 8) * 8 / 4 + 3) & ~3 : (S * S * 3 + 3) & ~3;
-    const size_t lds = (size_t)(XFLOATS + 4 * S * 4 + RPB * 4 + ((RPB + 3) & ~3) + rows * C * CS) * sizeof(float);
-    auto kern = crop_conv1_kernel<S, NG, COUT, PB, RPB, SPLIT, LIST, F16>;
+    const size_t lds = (size_t)(XFLOATS + 4 * S * 4 + RPB * 4 + ((RPB + 3) & ~3) + (STRIP ? 0 : rows * C * CS)) * sizeof(float);
+    auto kern = crop_conv1_kernel<S, NG, COUT, PB, RPB, SPLIT, LIST, F16, STRIP>;
     if (lds > 64 * 1024) {
         static FrDevLatch latch;
         if (!fr_raise_lds(reinterpret_cast<const void*>(kern), lds, latch)) {
@@ -429,13 +564,21 @@ extern "C" int fr_crop_conv1_split(int net, const uint8_t* frames, int nframes, 
     hipStream_t s = fr_stream(stream);
     const int64_t nslots = (int64_t)nframes * cap;
     int rc;
-    if (conv_f16) {       // the conv itself on the f16 matrix cores (split precision)
-        if (net == 0) rc = cap % RC1_RPB_R == 0 && nslots >= 8192 ? launch_ro<24, 7, 28, RC1_PB_R, RC1_RPB_R, true, false, true>(a, nframes * cap, s) : launch_ro<24, 7, 28, 4, 1, true, false, true>(a, nframes * cap, s);
-        else if (net == 1) rc = cap % RC1_RPB_O == 0 && nslots >= 2048 ? launch_ro<48, 8, 32, RC1_PB_O, RC1_RPB_O, true, false, true>(a, nframes * cap, s) : launch_ro<48, 8, 32, 2, 1, true, false, true>(a, nframes * cap, s);
+    const int form = conv_f16 & 3;
+    FR_REQUIRE(form < 3 && (conv_f16 & ~(3 | FR_RC1_BATCH_SHAPE)) == 0, "fr_crop_conv1_split: conv_f16 must be 0, 1 or 2 (| 16)");
+    // several slots per block only when there are blocks to spare, or when the caller asks for that launch shape
+    const bool many_r = nslots >= 8192 || (conv_f16 & FR_RC1_BATCH_SHAPE), many_o = nslots >= 2048 || (conv_f16 & FR_RC1_BATCH_SHAPE);
+    if (form) {           // the conv itself on the f16 matrix cores (split precision)
+        // R-Net: the tile form under 1 and 2 alike.  Its strip form (two slots staged per block, two strips of 16 columns each) ran
+        // 447 us against 397: 32 conv columns computed for a map of 22, 22 % more MFMAs than the tile form's flat pixel tiles
+        if (net == 0) rc = cap % RC1_RPB_R == 0 && many_r ? launch_ro<24, 7, 28, RC1_PB_R, RC1_RPB_R, true, false, true>(a, nframes * cap, s) : launch_ro<24, 7, 28, 4, 1, true, false, true>(a, nframes * cap, s);
+        // O-Net: 1 the strip form, 2 the tile form (kept for the A/B and the bit-equality test); one slot per block: the tile form
+        else if (net == 1 && form == 1) rc = cap % RC1_RPB_OS == 0 && many_o ? launch_ro<48, 8, 32, RC1_PB_O, RC1_RPB_OS, true, false, true, true>(a, nframes * cap, s) : launch_ro<48, 8, 32, 2, 1, true, false, true>(a, nframes * cap, s);
+        else if (net == 1) rc = cap % RC1_RPB_O == 0 && many_o ? launch_ro<48, 8, 32, RC1_PB_O, RC1_RPB_O, true, false, true>(a, nframes * cap, s) : launch_ro<48, 8, 32, 2, 1, true, false, true>(a, nframes * cap, s);
         else { FR_REQUIRE(false, "fr_crop_conv1_split: net must be 0 (R-Net) or 1 (O-Net)"); }
     } else
-    if (net == 0) rc = cap % 8 == 0 && nslots >= 8192 ? launch_ro<24, 7, 28, 4, 8, true>(a, nframes * cap, s) : launch_ro<24, 7, 28, 4, 1, true>(a, nframes * cap, s);
-    else if (net == 1) rc = cap % 4 == 0 && nslots >= 2048 ? launch_ro<48, 8, 32, 2, 4, true>(a, nframes * cap, s) : launch_ro<48, 8, 32, 2, 1, true>(a, nframes * cap, s);
+    if (net == 0) rc = cap % 8 == 0 && many_r ? launch_ro<24, 7, 28, 4, 8, true>(a, nframes * cap, s) : launch_ro<24, 7, 28, 4, 1, true>(a, nframes * cap, s);
+    else if (net == 1) rc = cap % 4 == 0 && many_o ? launch_ro<48, 8, 32, 2, 4, true>(a, nframes * cap, s) : launch_ro<48, 8, 32, 2, 1, true>(a, nframes * cap, s);
     else { FR_REQUIRE(false, "fr_crop_conv1_split: net must be 0 (R-Net) or 1 (O-Net)"); }
     if (rc != FR_OK) return rc;
     FR_CHECK_LAUNCH("crop_conv1_kernel (split)");

@@ -576,7 +576,14 @@ int fr_crop_conv1_f32(int net, const uint8_t* frames, int nframes, int H, int W,
  * y_split [nframes*cap][P*P pixels][hi 32 channels | lo 32 channels], 128 B per pixel, channels >= Cout zero (P = 11 / 23) -
  * the operand format of fr_ro_conv2_split.  Same slots computed / left unwritten as fr_crop_conv1_f32.
  * conv_f16 = 0: the conv itself is the f32 form's (the map is hi + lo of fr_crop_conv1_f32's to 2^-21); 1: the conv runs on
- * the f16 matrix cores with split-precision operands too (the split format's error from the f32 form: DESIGN.md 4.3a). */
+ * the f16 matrix cores with split-precision operands too (the split format's error from the f32 form: DESIGN.md 4.3a); the
+ * O-Net's batch launch (several slots per block) then takes the STRIP form: a wave walks a strip of 16 conv columns down the
+ * crop and pools the raw sums in registers, no conv map in LDS; 2: the same arithmetic in the TILE form everywhere (bands of
+ * conv rows through an LDS tile, pooled from there) - the same bytes as 1, kept for the A/B and the bit-equality test.  The
+ * R-Net and every launch of one slot per block run the tile form under 1 as well (the R-Net's strip form measured slower).
+ * | FR_RC1_BATCH_SHAPE: take the several-slots-per-block launch whatever the slot count (by default only from 8192 / 2048
+ * slots on) - how a small test reaches the batch kernels. */
+#define FR_RC1_BATCH_SHAPE 16
 int fr_crop_conv1_split(int net, const uint8_t* frames, int nframes, int H, int W, const float* boxes,
                         const int32_t* counts, int cap, const float* w, const float* bias, const float* slope,
                         void* y_split, int conv_f16, fr_stream_t stream);
