@@ -9,6 +9,7 @@ detect (MTCNN, HIP) -> align (5-point warp, HIP) -> embed (IResNet on MFMA, HIP)
 step lives in ``gallery.GalleryMatcher``.  There is no CPU path: construction succeeds
 anywhere, ``prepare`` raises without a HIP device.
 """
+import contextlib
 import logging
 import os
 import threading
@@ -36,6 +37,19 @@ class Face(dict):
 
 def _model_dir(name, root):
     return os.path.join(os.path.expanduser(root), "models", name)
+
+
+@contextlib.contextmanager
+def _reset_on_failure(tracks, camera_ids):
+    """Round everything a pass runs behind ``tracks.associate_device`` (``tracks`` None: round nothing).  The associate launch
+    has moved the state: should anything behind it fail, the bank misses this turn's rows, and no track of these cameras may be
+    carried from it."""
+    try:
+        yield
+    except BaseException:
+        if tracks is not None:
+            tracks.reset(camera_ids)
+        raise
 
 
 class _Ragged:
@@ -467,54 +481,7 @@ class FaceAnalysis:
         N = src.n if src is not None else frames.shape[0]
         cap = boxes.shape[1]
         if compact_embed:
-            if quality is not None:
-                return self._embed_fit(frames, src, boxes, scores, kps, counts, N, cap, quality)
-            if tracks is not None and getattr(tracks, "quality", None) is not None:
-                if len(camera_ids) != N:
-                    raise ValueError(f"one camera id per frame: {N} frames, {len(camera_ids)} ids")
-                return self._embed_judged(frames, src, boxes, scores, kps, counts, N, cap, tracks, camera_ids)
-            if tracks is None:
-                cnt = counts.cpu()                                        # the extra sync
-                sel = (torch.arange(cap)[None, :] < cnt[:, None]).reshape(-1).nonzero().squeeze(1).to(self.device)
-            else:
-                if len(camera_ids) != N:
-                    raise ValueError(f"one camera id per frame: {N} frames, {len(camera_ids)} ids")
-                with torch.cuda.device(self.device):
-                    entry, need, tid = tracks.associate_device(boxes, counts, camera_ids)
-                    both = torch.cat([counts.reshape(N, 1), need, entry], dim=1).cpu()   # the same one sync, a wider row
-                cnt, need_h = both[:, 0], both[:, 1:1 + cap]
-                tracks.count(cnt.numpy(), need_h.numpy(), both[:, 1 + cap:].numpy())
-                sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (need_h != 0)).reshape(-1).nonzero().squeeze(1).to(self.device)
-            if tracks is not None:
-                # the associate launch has moved the state: should align or embed fail, the bank misses this turn's rows, and no
-                # track of these cameras may be carried from it
-                try:
-                    emb, normed = self._embed_selected(frames, src, kps, sel, N, cap)
-                    with torch.cuda.device(self.device):
-                        tracks.commit_device(entry, need, counts, camera_ids, emb, normed)
-                        carried = ((need == 0) & (entry >= 0)).to(torch.int32)   # a slot past the count has entry -1
-                        fused = self._fuse(tracks, entry, need, tid, counts, camera_ids, normed)
-                except BaseException:
-                    tracks.reset(camera_ids)
-                    raise
-                return dict({"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
-                             "normed_embedding": normed, "track_id": tid, "carried": carried}, **fused)
-            emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
-            emb[:, 0] = 1.0                                               # empty slots: a unit vector, never NaN downstream
-            normed = emb.clone()
-            if sel.numel():
-                with torch.cuda.device(self.device):
-                    F = sel.numel()
-                    crops = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
-                    # named, not inline: a temporary dies as soon as its pointer is taken and the next temporary
-                    # may be handed the same block before the kernel has read it
-                    kps_sel = kps.reshape(-1, 5, 2)[sel].contiguous()
-                    frame_idx = (sel // cap).to(torch.int32)
-                    self._warp_faces(frames, src, kps_sel, frame_idx, F, crops)
-                    e, nm = self.rec.forward(crops)
-                    emb[sel], normed[sel] = e, nm
-            return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
-                    "normed_embedding": normed}
+            return self._embed_compact(frames, src, boxes, scores, kps, counts, tracks, camera_ids, quality)
         with torch.cuda.device(self.device):
             if crops_out is not None:                  # the caller embeds several calls' slots in ONE forward (embed_slots)
                 assert crops_out.shape == (N * cap, 112, 112, 8) and crops_out.dtype == torch.float16 and crops_out.is_contiguous()
@@ -526,78 +493,96 @@ class FaceAnalysis:
         return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
                 "normed_embedding": normed}
 
-    def _embed_selected(self, frames, src, kps, sel, N, cap):
-        """The ``compact_embed`` pass of ``detect_embed_slots`` over the slots ``sel`` (a device index): slot-layout (embedding,
-        normed_embedding) f32 [N*cap,512], unit vectors in the rows that are not selected."""
+    def _embed_compact(self, frames, src, boxes, scores, kps, counts, tracks, camera_ids, quality):
+        """The ``compact_embed`` pass of ``detect_embed_slots`` behind the detector.  Its four forms are one sequence, of which
+        each runs its own steps ([]: only when a slot is selected; fuse: only tracks with a ``template``):
+
+          plain     copy -> [align the selected -> embed]
+          tracks    associate -> copy -> [align the selected -> embed] -> commit -> fuse
+          quality   align all -> judge -> copy -> [embed]
+          judging   associate -> align all -> judge -> resolve -> copy -> [embed] -> commit -> fuse      (tracks that judge)
+
+        The ONE copy is the sync on the face counts; its row widens to carry what selects the slots to embed: ``need`` and
+        ``entry`` (tracks), the verdicts (quality), or actions, entries and verdicts (tracks that judge)."""
+        N, cap = boxes.shape[:2]
+        judging = tracks is not None and getattr(tracks, "quality", None) is not None
+        if judging:
+            quality = tracks.quality
+        if tracks is not None and len(camera_ids) != N:
+            raise ValueError(f"one camera id per frame: {N} frames, {len(camera_ids)} ids")
+        crops, trk, qual, fused = None, {}, {}, {}
+        with torch.cuda.device(self.device):
+            if tracks is not None:
+                entry, need, tid = tracks.associate_device(boxes, counts, camera_ids)
+            with _reset_on_failure(tracks, camera_ids):
+                row = [counts.reshape(N, 1)]
+                if quality is not None:                                   # every slot aligned, sync-free, and judged
+                    kps = kps.contiguous()
+                    crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
+                    self._warp_slots(frames, src, kps, counts, cap, crops)
+                    qi, qf, verdict = quality.measure_device(crops, kps, counts, cap)
+                    verdict = verdict.view(N, cap)
+                    qual = {"quality": qi.view(N, cap, 8), "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict}
+                if judging:                                               # embed / carry / reject per face; the pair to commit
+                    action, need2, entry2 = tracks.resolve_device(entry, need, tid, verdict, counts, camera_ids)
+                    row += [action, entry, verdict]
+                elif tracks is not None:
+                    need2, entry2 = need, entry
+                    row += [need, entry]
+                elif quality is not None:
+                    row.append(verdict)
+                both = (torch.cat(row, dim=1) if len(row) > 1 else row[0]).cpu()   # the one sync, a wider row than the counts
+                cnt, first = both[:, 0], both[:, 1:1 + cap]
+                if judging:
+                    tracks.count(cnt.numpy(), None, both[:, 1 + cap:1 + 2 * cap].numpy(), first.numpy())
+                    mask = first == 1                                     # action: embed
+                elif tracks is not None:
+                    tracks.count(cnt.numpy(), first.numpy(), both[:, 1 + cap:].numpy())
+                    mask = first != 0                                     # need
+                else:
+                    mask = first == 0 if quality is not None else None    # verdict: fit
+                emb, normed = self._embed_selected(frames, src, kps, self._select(cnt, cap, mask), N, cap, crops)
+                if tracks is not None:
+                    tracks.commit_device(entry2, need2, counts, camera_ids, emb, normed)
+                    carried = action == 2 if judging else (need == 0) & (entry >= 0)   # a slot past the count has entry -1
+                    trk = {"track_id": tid, "carried": carried.to(torch.int32)}
+                    if judging:
+                        trk["track_action"] = action
+                    fused = self._fuse(tracks, entry2, need2, tid, counts, camera_ids, normed)
+        return dict({"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb,
+                     "normed_embedding": normed}, **trk, **qual, **fused)
+
+    def _select(self, cnt, cap, mask=None):
+        """The slots to embed as a device index, frame-major: below the frame's host count ``cnt`` [N] and, with a host
+        ``mask`` [N,cap], set in it."""
+        held = torch.arange(cap)[None, :] < cnt[:, None]
+        if mask is not None:
+            held = held & mask
+        return held.reshape(-1).nonzero().squeeze(1).to(self.device)
+
+    def _embed_selected(self, frames, src, kps, sel, N, cap, crops=None):
+        """Slot-layout (embedding, normed_embedding) f32 [N*cap,512] with the embed net's rows for the slots ``sel`` (a device
+        index) and unit vectors - never NaN downstream - in every other row: empty, carried or rejected.  ``crops``: the
+        aligned crops of all N*cap slots where the pass has them (``_warp_slots``); without, the selected slots are aligned
+        here."""
         emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
-        emb[:, 0] = 1.0                                                   # never NaN downstream
+        emb[:, 0] = 1.0
         normed = emb.clone()
         if sel.numel():
             with torch.cuda.device(self.device):
-                F = sel.numel()
-                crops = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
-                kps_sel = kps.reshape(-1, 5, 2)[sel].contiguous()         # named, not inline (see detect_embed_slots)
-                frame_idx = (sel // cap).to(torch.int32)
-                self._warp_faces(frames, src, kps_sel, frame_idx, F, crops)
-                e, nm = self.rec.forward(crops)
+                # named, not inline: a temporary dies as soon as its pointer is taken and the next temporary
+                # may be handed the same block before the kernel has read it
+                if crops is not None:
+                    faces = crops.index_select(0, sel)
+                else:
+                    F = sel.numel()
+                    faces = torch.empty((F, 112, 112, 8), dtype=torch.float16, device=self.device)
+                    kps_sel = kps.reshape(-1, 5, 2)[sel].contiguous()
+                    frame_idx = (sel // cap).to(torch.int32)
+                    self._warp_faces(frames, src, kps_sel, frame_idx, F, faces)
+                e, nm = self.rec.forward(faces)
                 emb[sel], normed[sel] = e, nm
         return emb, normed
-
-    def _embed_fit(self, frames, src, boxes, scores, kps, counts, N, cap, quality):
-        """The ``quality`` pass of ``detect_embed_slots``: align every slot, judge the crops, embed the fit faces."""
-        with torch.cuda.device(self.device):
-            kps = kps.contiguous()
-            crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
-            self._warp_slots(frames, src, kps, counts, cap, crops)
-            qi, qf, verdict = quality.measure_device(crops, kps, counts, cap)
-            both = torch.cat([counts.reshape(N, 1), verdict.view(N, cap)], dim=1).cpu()       # the same one sync, a wider row
-            cnt, ver = both[:, 0], both[:, 1:]
-            sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (ver == 0)).reshape(-1).nonzero().squeeze(1).to(self.device)
-            emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
-            emb[:, 0] = 1.0                                               # empty and rejected slots: a unit vector
-            normed = emb.clone()
-            if sel.numel():
-                fit = crops.index_select(0, sel)                          # named, not inline (see detect_embed_slots)
-                e, nm = self.rec.forward(fit)
-                emb[sel], normed[sel] = e, nm
-        return {"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
-                "quality": qi.view(N, cap, 8), "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict.view(N, cap)}
-
-    def _embed_judged(self, frames, src, boxes, scores, kps, counts, N, cap, tracks, camera_ids):
-        """The pass of ``detect_embed_slots`` for tracks that judge (``FaceTracks(..., quality=q)``): associate, align every slot,
-        judge the crops, one launch decides embed / carry / reject per face, the ONE copy carries counts, actions, entries and
-        verdicts, the embed net runs for the faces to embed, and the commit launch stores their rows and fills the carried ones."""
-        with torch.cuda.device(self.device):
-            entry, need, tid = tracks.associate_device(boxes, counts, camera_ids)
-            # the associate launch has moved the state: should anything below fail, the bank misses this turn's rows, and no
-            # track of these cameras may be carried from it
-            try:
-                kps = kps.contiguous()
-                crops = torch.empty((N * cap, 112, 112, 8), dtype=torch.float16, device=self.device)
-                self._warp_slots(frames, src, kps, counts, cap, crops)
-                qi, qf, verdict = tracks.quality.measure_device(crops, kps, counts, cap)
-                verdict = verdict.view(N, cap)
-                action, need2, entry2 = tracks.resolve_device(entry, need, tid, verdict, counts, camera_ids)
-                both = torch.cat([counts.reshape(N, 1), action, entry, verdict], dim=1).cpu()   # the same one sync, a wider row
-                cnt, act = both[:, 0], both[:, 1:1 + cap]
-                tracks.count(cnt.numpy(), None, both[:, 1 + cap:1 + 2 * cap].numpy(), act.numpy())
-                sel = ((torch.arange(cap)[None, :] < cnt[:, None]) & (act == 1)).reshape(-1).nonzero().squeeze(1).to(self.device)
-                emb = torch.zeros((N * cap, 512), dtype=torch.float32, device=self.device)
-                emb[:, 0] = 1.0                                           # empty and rejected slots: a unit vector
-                normed = emb.clone()
-                if sel.numel():
-                    fit = crops.index_select(0, sel)                      # named, not inline (see detect_embed_slots)
-                    e, nm = self.rec.forward(fit)
-                    emb[sel], normed[sel] = e, nm
-                tracks.commit_device(entry2, need2, counts, camera_ids, emb, normed)
-                carried = (action == 2).to(torch.int32)
-                fused = self._fuse(tracks, entry2, need2, tid, counts, camera_ids, normed)
-            except BaseException:
-                tracks.reset(camera_ids)
-                raise
-        return dict({"counts": counts, "bbox": boxes, "kps": kps, "det_score": scores, "embedding": emb, "normed_embedding": normed,
-                     "track_id": tid, "carried": carried, "track_action": action, "quality": qi.view(N, cap, 8),
-                     "quality_f": qf.view(N, cap, 4), "quality_verdict": verdict}, **fused)
 
     @staticmethod
     def _fuse(tracks, entry, need, tid, counts, camera_ids, normed):

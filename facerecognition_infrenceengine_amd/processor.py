@@ -11,6 +11,7 @@ Differences that are the point of this build:
   (infrenceServer.py:264,288); ties go to the lowest row (the reference iterates a ``set``, so its
   own tie order is random: infrenceServer.py:357-373).
 """
+import collections
 import logging
 import pickle
 import threading
@@ -37,9 +38,9 @@ class _Unchanged:
 UNCHANGED = _Unchanged()
 
 
-def _check_gate(gate, camera_ids, n, tracks=None):
-    """The camera ids of a gated or tracked call as a list (None without gate and tracks: one list serves both);
-    ValueError before anything runs."""
+def _check_gate(gate, camera_ids, n, tracks=None, quality=None):
+    """The argument rule of ``recognize_batch`` / ``identify_batch``: the camera ids of a gated or tracked call as a list (None
+    without gate and tracks: one list serves both), and no ``quality`` beside ``tracks``; ValueError before anything runs."""
     if gate is None and tracks is None:
         if camera_ids is not None:
             raise ValueError("camera_ids come with a gate (gate=ActivityGate(...)) or with tracks (tracks=FaceTracks(...))")
@@ -51,34 +52,9 @@ def _check_gate(gate, camera_ids, n, tracks=None):
         raise ValueError(f"one camera id per frame: {n} frames, {len(ids)} ids")
     if len(set(ids)) != len(ids):
         raise ValueError("a camera id is repeated in one call")
+    if quality is not None and tracks is not None:
+        raise ValueError("quality together with tracks is not supported yet")
     return ids
-
-
-def _track_columns(r):
-    """Host copies of the slot results' ``track_id`` and ``carried`` [n,cap], (None, None) for a call without tracks."""
-    if "track_id" not in r:
-        return None, None
-    return r["track_id"].cpu().numpy(), r["carried"].cpu().numpy()
-
-
-def _template_columns(r, tracks):
-    """Host copy of the slot results' ``template_shots`` [n,cap] when the call's tracks fuse, else None; the joins
-    and restarts of the event column are added to ``tracks.stats`` from the same read-back."""
-    if "template_shots" not in r:
-        return None
-    tracks.count_events(r["template_event"].cpu().numpy())
-    return r["template_shots"].cpu().numpy()
-
-
-def _tracked(face, tid, carried, f, j, shots=None):
-    """The face dict with ``track_id`` (-1: untracked) and ``tracked`` (True: its embedding was carried), and with ``shots`` (the
-    column of tracks that fuse) ``template_shots``: the shots behind the row it was scanned with, 0: its own row; as it is
-    without tracks."""
-    if tid is not None:
-        face["track_id"], face["tracked"] = int(tid[f, j]), bool(carried[f, j])
-    if shots is not None:
-        face["template_shots"] = int(shots[f, j])
-    return face
 
 
 def _scan_rows(r):
@@ -87,30 +63,68 @@ def _scan_rows(r):
     return r["query"] if "query" in r else r["normed_embedding"]
 
 
-def _quality_columns(r):
-    """Host copies of the slot results' ``quality`` [n,cap,8], ``quality_f`` [n,cap,4] and ``quality_verdict`` [n,cap], and of
-    ``track_action`` [n,cap] when the call's tracks judge (None otherwise); None for a call without quality."""
-    if "quality" not in r:
-        return None
-    action = r["track_action"].cpu().numpy() if "track_action" in r else None
-    return r["quality"].cpu().numpy(), r["quality_f"].cpu().numpy(), r["quality_verdict"].cpu().numpy(), action
+class _SlotFaces:
+    """The host side of one batch: every device-to-host copy the tails of ``recognize_batch`` / ``identify_batch`` make of the
+    slot results ``r`` (``n`` frames) and of their scan ``idx`` / ``score`` with its decision ``dec`` (None: a top-K scan, the
+    ``identify`` dicts), the counts first - the one synchronisation -, and the dict of each face.  ``track_id`` / ``carried``,
+    ``template_shots`` and the quality columns (``track_action`` beside them when the tracks judge) are None for a call without;
+    the joins and restarts of the tracks' event column are added to ``tracks.stats`` from the same read-back."""
+
+    def __init__(self, r, n, idx, score, tracks, dec=None):
+        shape = (n, r["bbox"].shape[1]) + (() if dec is not None else (-1,))
+        self.counts = r["counts"].cpu().numpy()                              # the one synchronisation
+        self.idx, self.score = idx.cpu().numpy().reshape(shape), score.cpu().numpy().reshape(shape)
+        self.dec = dec.cpu().numpy().reshape(shape) if dec is not None else None
+        self.bbox = r["bbox"].cpu().numpy().astype(int)                      # :531 truncation
+        self.det_score = r["det_score"].cpu().numpy()
+        self.tid = self.carried = self.shots = self.action = self.quality = None
+        if "track_id" in r:
+            self.tid, self.carried = r["track_id"].cpu().numpy(), r["carried"].cpu().numpy()
+        if "template_shots" in r:
+            tracks.count_events(r["template_event"].cpu().numpy())
+            self.shots = r["template_shots"].cpu().numpy()
+        if "quality" in r:
+            if "track_action" in r:
+                self.action = r["track_action"].cpu().numpy()
+            self.quality = tuple(r[key].cpu().numpy() for key in ("quality", "quality_f", "quality_verdict"))
+
+    def fit(self, f, j):
+        """True for a call without quality and for a face judged fit; under judging tracks for every face but a rejected one - a
+        carried face answers with its track's held fit row whatever this frame's verdict"""
+        if self.quality is None:
+            return True
+        return self.quality[2][f, j] == 0 if self.action is None else self.action[f, j] != 3
+
+    def face(self, f, j, ids, metadata, min_score=None):
+        """The dict of face ``j`` of frame ``f`` through the gallery (``ids``, ``metadata``) of its frame: a face that is not fit
+        is the Unknown dict / has no candidates.  With tracks it gains ``track_id`` (-1: untracked), ``tracked`` (True: its
+        embedding was carried) and, when they fuse, ``template_shots`` (the shots behind the row it was scanned with, 0: its own
+        row); with quality, ``quality`` (``FaceQuality.describe``) and ``quality_ok``: this frame's verdict."""
+        at = (self.bbox[f, j], self.det_score[f, j])
+        if self.dec is not None:
+            face = _face_result(*at, self.dec[f, j] if self.fit(f, j) else 0, self.idx[f, j], self.score[f, j], ids, metadata)
+        else:
+            face = _face_candidates(*at, self.idx[f, j] if self.fit(f, j) else (), self.score[f, j], ids, metadata, min_score)
+        if self.tid is not None:
+            face["track_id"], face["tracked"] = int(self.tid[f, j]), bool(self.carried[f, j])
+        if self.shots is not None:
+            face["template_shots"] = int(self.shots[f, j])
+        if self.quality is not None:
+            from .quality import FaceQuality
+            face["quality"] = FaceQuality.describe(*(c[f, j] for c in self.quality))
+            face["quality_ok"] = face["quality"]["ok"]
+        return face
+
+    def frames(self, galleries, keep, total, min_score=None):
+        """What a batch call returns: per frame the list of its faces' dicts through ``galleries[f]`` = (ids, metadata), None for
+        a frame without a gallery; with ``keep`` (the active frames of a gated call) spread over ``total`` frames."""
+        out = [None if g is None else [self.face(f, j, *g, min_score) for j in range(int(self.counts[f]))]
+               for f, g in enumerate(galleries)]
+        return _spread(out, keep, total)
 
 
-def _fit(q, f, j):
-    """True for a call without quality and for a face judged fit; under judging tracks for every face but a rejected one - a
-    carried face answers with its track's held fit row whatever this frame's verdict"""
-    if q is None:
-        return True
-    return q[2][f, j] == 0 if q[3] is None else q[3][f, j] != 3
-
-
-def _judged(face, q, f, j):
-    """The face dict with ``quality`` (``FaceQuality.describe``) and ``quality_ok``; as it is without quality."""
-    if q is not None:
-        from .quality import FaceQuality
-        face["quality"] = FaceQuality.describe(q[0][f, j], q[1][f, j], q[2][f, j])
-        face["quality_ok"] = face["quality"]["ok"]
-    return face
+# What ``_scan_mixed`` returns (there: what each field holds)
+_Scan = collections.namedtuple("_Scan", "n r keep view_set galleries idx score")
 
 
 def _spread(out, keep, n):
@@ -398,8 +412,9 @@ class FaceRecognitionProcessor:
                                               providers=["CUDAExecutionProvider", "CPUExecutionProvider"])
             self.face_detector.prepare(ctx_id=0)
 
-    def recognize(self, frame, company_id):
-        """Structured form: list of dicts {bbox int[4], person_info, det_score, recognition_score, person_id}."""
+    def _scan_frame(self, frame, company_id, k=None):
+        """The prelude ``recognize`` and ``identify`` share: None when the company has no gallery, else the frame's faces
+        (``detect_embed_device``), then the matcher and metadata its rows went through and the scan's idx / score (top-``k``)."""
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
@@ -407,16 +422,20 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", company_id)
             return None
         r = _detect_embed(self.face_detector, frame)
-        matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
-                                                     r["normed_embedding"])  # renormalise + scan (:532-542)
+        return (r,) + _match_fresh(self.embedding_manager, company_id, matcher, metadata, r["normed_embedding"],
+                                   k)                                        # renormalise + scan (:532-542)
+
+    def recognize(self, frame, company_id):
+        """Structured form: list of dicts {bbox int[4], person_info, det_score, recognition_score, person_id}."""
+        got = self._scan_frame(frame, company_id)
+        if got is None:
+            return None
+        r, matcher, metadata, idx, score = got
         dec = matcher.decide_device(idx, score, self.recognition_threshold)  # :545
         idx, score, dec = idx.cpu().numpy(), score.cpu().numpy(), dec.cpu().numpy()
         bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
         det = r["det_score"].cpu().numpy()
-        out = []
-        for f in range(len(idx)):
-            out.append(_face_result(bbox[f], det[f], dec[f], idx[f], score[f], matcher.ids, metadata))
-        return out
+        return [_face_result(bbox[f], det[f], dec[f], idx[f], score[f], matcher.ids, metadata) for f in range(len(idx))]
 
     def identify(self, frame, company_id, k=5, min_score=None):
         """Ranked candidate list per face (1 <= k <= 16): a list of dicts {bbox int[4], det_score, candidates}, where
@@ -426,22 +445,14 @@ class FaceRecognitionProcessor:
         gallery, as ``recognize``."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
-        if self.face_detector is None:
-            self.initialize_detector()
-        matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
-        if len(matcher) == 0:
-            logger.warning("No embeddings found for company %s", company_id)
+        got = self._scan_frame(frame, company_id, int(k))
+        if got is None:
             return None
-        r = _detect_embed(self.face_detector, frame)
-        matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata,
-                                                     r["normed_embedding"], k=int(k))
+        r, matcher, metadata, idx, score = got
         idx, score = idx.cpu().numpy(), score.cpu().numpy()
         bbox = r["bbox"].cpu().numpy().astype(int)
         det = r["det_score"].cpu().numpy()
-        out = []
-        for f in range(len(idx)):
-            out.append(_face_candidates(bbox[f], det[f], idx[f], score[f], matcher.ids, metadata, min_score))
-        return out
+        return [_face_candidates(bbox[f], det[f], idx[f], score[f], matcher.ids, metadata, min_score) for f in range(len(idx))]
 
     @property
     def accepts_mixed_sizes(self):
@@ -455,11 +466,11 @@ class FaceRecognitionProcessor:
                     tracks=None, quality=None):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
-        no company has a gallery (nothing is run, a gate is not consulted), else (n, slot results, view_set, metadatas,
-        index_of, idx, score, keep); device tensors, no synchronisation beyond the engine's own.  With a ``gate``, ``keep``
-        lists the active frames and everything else describes exactly those n = len(keep) frames, in order (``keep`` None:
-        all frames, the ungated call's tensors); with none active the slot results are None, and idx / score are None when
-        no active frame's company has a gallery."""
+        no company has a gallery (nothing is run, a gate is not consulted), else a ``_Scan``: n, the slot results r, keep, the
+        view_set, per frame its gallery (ids, metadata) - None without one -, idx, score; device tensors, no synchronisation
+        beyond the engine's own.  With a ``gate``, ``keep`` lists the active frames and everything else describes exactly those
+        n = len(keep) frames, in order (``keep`` None: all frames, the ungated call's tensors); with none active the slot
+        results are None, and galleries / idx / score are None when no active frame's company has a gallery."""
         from .gallery import StaleViewError
         company_ids = list(company_ids)
         if len(company_ids) != len(frames):
@@ -479,7 +490,7 @@ class FaceRecognitionProcessor:
             if r is not None:
                 view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
             if r is None or all(v is None for v in index_of):
-                return n, r, view_set, metadatas, index_of, None, None, keep
+                return _Scan(n, r, keep, view_set, None, None, None)
         cap = r["bbox"].shape[1]
 
         def scan(vs, of):
@@ -491,36 +502,19 @@ class FaceRecognitionProcessor:
         except StaleViewError:                    # a sync moved the slab on meanwhile: the current views, once
             view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
             idx, score = scan(view_set, index_of)
-        return n, r, view_set, metadatas, index_of, idx, score, keep
+        galleries = [None if v is None else (view_set.views[v].ids, metadatas[v]) for v in index_of]
+        return _Scan(n, r, keep, view_set, galleries, idx, score)
 
-    def _recognize_batch_mixed(self, frames, company_ids, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
-                               tracks=None, quality=None):
-        got = self._scan_mixed(frames, company_ids, pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
-                               tracks=tracks, quality=quality)
+    def _serve_mixed(self, frames, company_ids, k, min_score, pixel_format, matrix, gate, camera_ids, tracks, quality):
+        """``recognize_batch`` with one company id per frame (``k`` None) and ``identify_batch`` (top-``k``): the grouped scan,
+        the decision launch of the former, the shared read-back."""
+        got = self._scan_mixed(frames, company_ids, k, pixel_format, matrix, gate, camera_ids, tracks, quality)
         if got is None:
             return [None] * len(frames)
-        n, r, view_set, metadatas, index_of, idx, score, keep = got
-        if idx is None:                           # no frame active, or none of the active ones has a gallery
-            return _spread([None] * n, keep, len(frames))
-        dec = view_set.decide_device(idx, score, self.recognition_threshold)
-        cap = r["bbox"].shape[1]
-        counts = r["counts"].cpu().numpy()                                   # the one synchronisation
-        idx, score, dec = (t.cpu().numpy().reshape(n, cap) for t in (idx, score, dec))
-        bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
-        dscore = r["det_score"].cpu().numpy()
-        tid, carried = _track_columns(r)
-        shots = _template_columns(r, tracks)
-        q = _quality_columns(r)
-        out = []
-        for f in range(n):
-            if index_of[f] is None:
-                out.append(None)
-                continue
-            ids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
-                                                      score[f, j], ids, metadata), tid, carried, f, j, shots), q, f, j)
-                        for j in range(int(counts[f]))])
-        return _spread(out, keep, len(frames))
+        if got.idx is None:                       # no frame active, or none of the active ones has a gallery
+            return _spread([None] * got.n, got.keep, len(frames))
+        dec = got.view_set.decide_device(got.idx, got.score, self.recognition_threshold) if k is None else None
+        return _SlotFaces(got.r, got.n, got.idx, got.score, tracks, dec).frames(got.galleries, got.keep, len(frames), min_score)
 
     def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601", gate=None,
                        camera_ids=None, tracks=None, quality=None):
@@ -533,35 +527,9 @@ class FaceRecognitionProcessor:
         judge, a REJECTED face has none and a carried one is ranked on its held row."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
-        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
-        if quality is not None and tracks is not None:
-            raise ValueError("quality together with tracks is not supported yet")
+        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks, quality)
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
-        got = self._scan_mixed(frames, ids, k=int(k), pixel_format=pixel_format, matrix=matrix, gate=gate, camera_ids=camera_ids,
-                               tracks=tracks, quality=quality)
-        if got is None:
-            return [None] * len(frames)
-        n, r, view_set, metadatas, index_of, idx, score, keep = got
-        if idx is None:
-            return _spread([None] * n, keep, len(frames))
-        cap = r["bbox"].shape[1]
-        counts = r["counts"].cpu().numpy()                                   # the one synchronisation
-        idx, score = idx.cpu().numpy().reshape(n, cap, -1), score.cpu().numpy().reshape(n, cap, -1)
-        bbox = r["bbox"].cpu().numpy().astype(int)
-        dscore = r["det_score"].cpu().numpy()
-        tid, carried = _track_columns(r)
-        shots = _template_columns(r, tracks)
-        q = _quality_columns(r)
-        out = []
-        for f in range(n):
-            if index_of[f] is None:
-                out.append(None)
-                continue
-            pids, metadata = view_set.views[index_of[f]].ids, metadatas[index_of[f]]
-            out.append([_judged(_tracked(_face_candidates(bbox[f, j], dscore[f, j], idx[f, j] if _fit(q, f, j) else (), score[f, j],
-                                                          pids, metadata, min_score), tid, carried, f, j, shots), q, f, j)
-                        for j in range(int(counts[f]))])
-        return _spread(out, keep, len(frames))
+        return self._serve_mixed(frames, ids, int(k), min_score, pixel_format, matrix, gate, camera_ids, tracks, quality)
 
     def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
                         quality=None):
@@ -617,11 +585,9 @@ class FaceRecognitionProcessor:
         of this frame's row alone; a shot that does not agree with the template restarts it and is scanned as it is.  Each face
         dict gains ``"template_shots"`` (the shots behind the scanned row, 0: the face's own row), and ``tracks.stats`` counts
         ``"joined"`` and ``"restarted"`` shots.  The same holds for ``identify_batch`` and for mixed-company batches."""
-        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks)
-        if quality is not None and tracks is not None:
-            raise ValueError("quality together with tracks is not supported yet")
+        camera_ids = _check_gate(gate, camera_ids, len(frames), tracks, quality)
         if isinstance(company_id, (list, tuple)):
-            return self._recognize_batch_mixed(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks, quality)
+            return self._serve_mixed(frames, company_id, None, None, pixel_format, matrix, gate, camera_ids, tracks, quality)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
@@ -634,20 +600,7 @@ class FaceRecognitionProcessor:
             return [UNCHANGED] * len(frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata, _scan_rows(r))
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
-        cap = r["bbox"].shape[1]
-        counts = r["counts"].cpu().numpy()                                   # the one synchronisation
-        idx, score, dec = (t.cpu().numpy().reshape(n, cap) for t in (idx, score, dec))
-        bbox = r["bbox"].cpu().numpy().astype(int)                           # :531 truncation
-        dscore = r["det_score"].cpu().numpy()
-        tid, carried = _track_columns(r)
-        shots = _template_columns(r, tracks)
-        q = _quality_columns(r)
-        out = []
-        for f in range(n):
-            out.append([_judged(_tracked(_face_result(bbox[f, j], dscore[f, j], dec[f, j] if _fit(q, f, j) else 0, idx[f, j],
-                                                      score[f, j], matcher.ids, metadata), tid, carried, f, j, shots), q, f, j)
-                        for j in range(int(counts[f]))])
-        return _spread(out, keep, len(frames))
+        return _SlotFaces(r, n, idx, score, tracks, dec).frames([(matcher.ids, metadata)] * n, keep, len(frames))
 
     def annotate(self, frame, results):
         """Draw ``recognize`` / ``recognize_batch`` results onto a frame (colours of infrenceServer.py:546-553)."""
@@ -924,34 +877,8 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
     ``quality`` (``quality.FaceQuality``): handed to the engine pass, which then embeds the faces judged fit only; a call
     without it passes no such argument on, and runs the code it always ran."""
     import torch
-    from .colour import check_pixel_format, check_yuv_shape
-    from .ingest import FrameIngest, RaggedIngest
-    arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
-    det_size = getattr(det, "det_size", None)
-    yuv = check_pixel_format(pixel_format, matrix)[0] is not None
-    if yuv:
-        if any(a.ndim != 2 or a.dtype != np.uint8 for a in arr):
-            raise ValueError(f"{pixel_format} frames of a batch must be uint8 [H*3/2, W]")
-        shapes = tuple(check_yuv_shape(a.shape) for a in arr)
-    else:
-        if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr):
-            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
-        shapes = tuple(a.shape[:2] for a in arr)
-    n, (h, w) = len(arr), shapes[0]
-    if det_size is None and any(s != (h, w) for s in shapes):
-        raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
-    stages = owner.__dict__.setdefault("_stages", {})
-    key = (n, h, w) if det_size is None else (shapes, det_size)
-    fmt = {"pixel_format": pixel_format, "matrix": matrix} if yuv else {}
-    if yuv:                                           # the BGR rings keep the keys they always had
-        key += (pixel_format, matrix)
-    if key not in stages:
-        while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
-            stages.pop(next(iter(stages)))
-        stages[key] = [FrameIngest(n, h, w, det.device, depth=2, **fmt) if det_size is None else
-                       RaggedIngest(key[0], det_size, det.device, depth=2, **fmt), 0]
-    ring, turn = stages[key]
-    stages[key][1] = turn + 1
+    arr, ring, turn = _ring_turn(owner, det, frames, pixel_format, matrix)
+    n, det_size = len(arr), getattr(det, "det_size", None)
     with det._lock, torch.cuda.device(det.device):
         if det_size is None:
             host = ring.host_buffer(turn)
@@ -987,6 +914,41 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
         r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, **ragged)    # results go to the host anyway
         ring.release(turn)
     return n, r, keep
+
+
+def _ring_turn(owner, det, frames, pixel_format, matrix):
+    """The frames of a batch as validated contiguous arrays, the pinned staging ring of their batch shape and pixel format (kept
+    on ``owner``, made on first use, the oldest of 8 dropped) and the turn of that ring the batch takes.  Host work only, outside
+    the engine's lock."""
+    from .colour import check_pixel_format, check_yuv_shape
+    from .ingest import FrameIngest, RaggedIngest
+    arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
+    det_size = getattr(det, "det_size", None)
+    yuv = check_pixel_format(pixel_format, matrix)[0] is not None
+    if yuv:
+        if any(a.ndim != 2 or a.dtype != np.uint8 for a in arr):
+            raise ValueError(f"{pixel_format} frames of a batch must be uint8 [H*3/2, W]")
+        shapes = tuple(check_yuv_shape(a.shape) for a in arr)
+    else:
+        if any(a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8 for a in arr):
+            raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
+        shapes = tuple(a.shape[:2] for a in arr)
+    n, (h, w) = len(arr), shapes[0]
+    if det_size is None and any(s != (h, w) for s in shapes):
+        raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
+    stages = owner.__dict__.setdefault("_stages", {})
+    key = (n, h, w) if det_size is None else (shapes, det_size)
+    fmt = {"pixel_format": pixel_format, "matrix": matrix} if yuv else {}
+    if yuv:                                           # the BGR rings keep the keys they always had
+        key += (pixel_format, matrix)
+    if key not in stages:
+        while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
+            stages.pop(next(iter(stages)))
+        stages[key] = [FrameIngest(n, h, w, det.device, depth=2, **fmt) if det_size is None else
+                       RaggedIngest(key[0], det_size, det.device, depth=2, **fmt), 0]
+    ring, turn = stages[key]
+    stages[key][1] = turn + 1
+    return arr, ring, turn
 
 
 def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):

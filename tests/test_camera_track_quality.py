@@ -69,23 +69,25 @@ def test_annotate_takes_the_judged_tracked_dicts():
 
 def _columns():
     """slot results of one frame, cap 4: embedded, carried though unfit, rejected, carried and fit"""
-    from facerecognition_infrenceengine_amd.processor import _quality_columns, _track_columns
     qi = torch.zeros((1, 4, 8), dtype=torch.int32)
     qi[0, :, 2] = torch.tensor([80, 3, 2, 90])                               # sharp
-    r = {"track_id": torch.tensor([[5, 6, -1, 8]], dtype=torch.int32), "carried": torch.tensor([[0, 1, 0, 1]], dtype=torch.int32),
-         "track_action": torch.tensor([[EMBED, CARRY, REJECT, CARRY]], dtype=torch.int32), "quality": qi,
-         "quality_f": torch.full((1, 4, 4), 400.0), "quality_verdict": torch.tensor([[0, BLUR, BLUR, 0]], dtype=torch.int32)}
-    return r, _track_columns(r), _quality_columns(r)
+    return {"counts": torch.tensor([4], dtype=torch.int32), "bbox": torch.arange(4.0).repeat(1, 4, 1),
+            "det_score": torch.full((1, 4), 0.9),
+            "track_id": torch.tensor([[5, 6, -1, 8]], dtype=torch.int32), "carried": torch.tensor([[0, 1, 0, 1]], dtype=torch.int32),
+            "track_action": torch.tensor([[EMBED, CARRY, REJECT, CARRY]], dtype=torch.int32), "quality": qi,
+            "quality_f": torch.full((1, 4, 4), 400.0), "quality_verdict": torch.tensor([[0, BLUR, BLUR, 0]], dtype=torch.int32)}
 
 
 def test_recognize_dicts_for_each_action():
-    from facerecognition_infrenceengine_amd.processor import _face_result, _fit, _judged, _tracked
-    r, (tid, carried), q = _columns()
-    assert [bool(_fit(q, 0, j)) for j in range(4)] == [True, True, False, True]
+    from facerecognition_infrenceengine_amd.processor import _SlotFaces
+    idx, score = torch.arange(4), torch.tensor([0.5 + j / 10 for j in range(4)])
+    host = _SlotFaces(_columns(), 1, idx, score, None, dec=torch.ones(4, dtype=torch.int32))
+    assert [bool(host.fit(0, j)) for j in range(4)] == [True, True, False, True]
     ids, meta = ["a", "b", "c", "d"], {k: {"name": k.upper(), "type": "employee"} for k in "abcd"}
-    faces = [_judged(_tracked(_face_result(np.arange(4), 0.9, 1 if _fit(q, 0, j) else 0, j, np.float32(0.5 + j / 10), ids, meta),
-                              tid, carried, 0, j), q, 0, j) for j in range(4)]
+    faces = host.frames([(ids, meta)], None, 1)[0]
+    assert len(faces) == 4 and all(np.array_equal(f["bbox"], np.arange(4)) and f["det_score"] == np.float32(0.9) for f in faces)
     assert [f["person_id"] for f in faces] == ["a", "b", None, "d"]          # the carried unfit face keeps its row's answer
+    assert [f["recognition_score"] for f in faces] == [np.float32(0.5), np.float32(0.6), 0, np.float32(0.8)]
     assert faces[2]["person_info"] == {"name": "Unknown", "type": "unknown"} and faces[2]["recognition_score"] == 0
     assert [f["tracked"] for f in faces] == [False, True, False, True] and [f["track_id"] for f in faces] == [5, 6, -1, 8]
     assert [f["quality_ok"] for f in faces] == [True, False, False, True]    # this frame's verdict, whatever the action
@@ -93,23 +95,26 @@ def test_recognize_dicts_for_each_action():
 
 
 def test_identify_dicts_for_each_action():
-    from facerecognition_infrenceengine_amd.processor import _face_candidates, _fit, _judged, _tracked
-    r, (tid, carried), q = _columns()
+    from facerecognition_infrenceengine_amd.processor import _SlotFaces
     ids, meta = ["a", "b"], {k: {"name": k.upper(), "type": "employee"} for k in "ab"}
-    rows, scores = np.array([1, 0]), np.array([0.8, 0.6], np.float32)
-    faces = [_judged(_tracked(_face_candidates(np.arange(4), 0.9, rows if _fit(q, 0, j) else (), scores, ids, meta, None),
-                              tid, carried, 0, j), q, 0, j) for j in range(4)]
+    rows, scores = torch.tensor([1, 0]).repeat(4, 1), torch.tensor([0.8, 0.6]).repeat(4, 1)
+    faces = _SlotFaces(_columns(), 1, rows, scores, None).frames([(ids, meta)], None, 1)[0]
     assert [len(f["candidates"]) for f in faces] == [2, 2, 0, 2]
+    assert [c["person_id"] for c in faces[0]["candidates"]] == ["b", "a"]
     assert all({"track_id", "tracked", "quality", "quality_ok"} <= set(f) for f in faces)
 
 
 def test_plain_quality_and_plain_tracks_columns_are_as_they_were():
-    from facerecognition_infrenceengine_amd.processor import _fit, _quality_columns
-    r, _, _ = _columns()
+    from facerecognition_infrenceengine_amd.processor import _SlotFaces
+    scan = (1, torch.arange(4), torch.zeros(4), None, torch.ones(4, dtype=torch.int32))
+    r = _columns()
     del r["track_action"]                                                    # the quality-only call: the verdict decides
-    q = _quality_columns(r)
-    assert q[3] is None and [bool(_fit(q, 0, j)) for j in range(4)] == [True, False, False, True]
-    assert _quality_columns({"track_id": r["track_id"]}) is None and _fit(None, 0, 0) is True
+    host = _SlotFaces(r, *scan)
+    assert host.action is None and [bool(host.fit(0, j)) for j in range(4)] == [True, False, False, True]
+    host = _SlotFaces({k: v for k, v in r.items() if not k.startswith("quality")}, *scan)    # the tracks-only call
+    assert host.quality is None and host.fit(0, 0) is True
+    assert set(host.face(0, 0, ["a"] * 4, {"a": {}})) == {"bbox", "person_id", "person_info", "det_score", "recognition_score",
+                                                            "track_id", "tracked"}
 
 
 def test_the_two_argument_form_keeps_raising():
