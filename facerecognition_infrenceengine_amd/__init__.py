@@ -5,4 +5,5 @@ from .face_analysis import Face, FaceAnalysis, FaceEngine  # noqa: E402,F401
 from .activity import ActivityGate  # noqa: E402,F401
 from .tracks import FaceTracks  # noqa: E402,F401
 from .quality import FaceQuality  # noqa: E402,F401
+from .hud import Hud  # noqa: E402,F401
 from .gallery import DuplicateOverflowError, DuplicatePairs, GalleryMatcher  # noqa: E402,F401

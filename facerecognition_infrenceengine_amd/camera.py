@@ -26,7 +26,7 @@ logger = logging.getLogger(__name__)
 
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
-                 dead_after=200, gate=None, tracks=None, quality=None):
+                 dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601"):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
         ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
         frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
@@ -37,6 +37,11 @@ class CameraManager:
         Unknown with ``quality_ok`` False.  None: no face is judged, as ever.  Not beside ``tracks`` (ValueError): the two
         combine as ``tracks=FaceTracks(..., quality=q)``, tracks that judge - only fit embeddings enter their bank, and a face
         that turns unfit for a few frames is carried on its track's held row; no further argument is needed here.
+        ``hud``: a ``hud.Hud``; the processed frames are then drawn on the DEVICE (``recognize_faces_batch``: the full HUD, on the
+        frames or on ``hud.out_size`` previews) and what is queued are the frames that call returns.  None: the plain box drawn
+        on the host frame by ``annotate``, as ever.
+        ``pixel_format`` / ``matrix``: what the captures deliver - ``"nv12"`` / ``"i420"`` frames (``uint8 [H*3/2, W]``) need a
+        ``hud``, since the host never holds a BGR picture of them to draw on (ValueError without one).
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
         waits for slow cameras once it holds a frame (latency stays that of the slowest *present* frame).
         ``reopen_after`` / ``dead_after``: consecutive failed reads before a capture is re-opened / given up."""
@@ -61,6 +66,9 @@ class CameraManager:
         if quality is not None and tracks is not None:
             raise ValueError("quality together with tracks is not supported yet")
         self.quality = quality
+        if pixel_format != "bgr" and hud is None:
+            raise ValueError(f"pixel_format={pixel_format!r} needs a hud: the host holds no BGR frame to annotate")
+        self.hud, self.pixel_format, self.matrix = hud, pixel_format, matrix
 
     def _forget(self, source):
         """A source that is gone: its gate slot and its track slot are freed and its held results dropped."""
@@ -167,7 +175,10 @@ class CameraManager:
         companies still go through the engine together: the processor call gets the per-frame list then, and the plain
         id whenever all its frames share one.  With a gate the processor also gets ``gate=`` and the frames' sources as
         ``camera_ids=``; where it answers ``UNCHANGED`` the source's held results stand in (here and in the returned list) and
-        ``stats["gated_frames"]`` counts the frame."""
+        ``stats["gated_frames"]`` counts the frame.  With a ``hud`` the processor call is ``recognize_faces_batch(..., hud,
+        return_results=True, held=self._held)`` with the same arguments (and the manager's pixel format when it is YUV): the frames
+        it returns - drawn on the device, an unchanged frame with its held results - are what is queued, and ``annotate`` is not
+        called."""
         mixed_ids = isinstance(company_id, (list, tuple))
         if mixed_ids and len(company_id) != len(batch):
             raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
@@ -175,7 +186,7 @@ class CameraManager:
         mixed = getattr(self.processor, "accepts_mixed_sizes", False)
         for k, (_, f) in enumerate(batch):
             by_shape.setdefault(None if mixed else tuple(f.shape), []).append(k)
-        results = [None] * len(batch)
+        results, pictures = [None] * len(batch), [None] * len(batch)
         for ks in by_shape.values():
             ids = [company_id[k] for k in ks] if mixed_ids else [company_id]
             one = all(c == ids[0] for c in ids[1:])
@@ -184,9 +195,17 @@ class CameraManager:
                 gated = dict(gated, tracks=self.tracks, camera_ids=[batch[k][0] for k in ks])
             if self.quality is not None:
                 gated = dict(gated, quality=self.quality)
-            res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids, **gated)
+            if self.hud is None:
+                res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids, **gated)
+            else:                                     # the same call, then the HUD drawn on the device frames
+                if self.pixel_format != "bgr":
+                    gated = dict(gated, pixel_format=self.pixel_format, matrix=self.matrix)
+                drawn, res = self.processor.recognize_faces_batch([batch[k][1] for k in ks], ids[0] if one else ids, self.hud,
+                                                                  return_results=True, held=self._held, **gated)
             for j, k in enumerate(ks):
                 results[k] = None if res is None else res[j]
+                if self.hud is not None:
+                    pictures[k] = drawn[j]
         if self.gate is not None:
             from .processor import UNCHANGED
             for k, (source, _) in enumerate(batch):
@@ -198,8 +217,11 @@ class CameraManager:
         self.stats["batches"] += 1
         self.stats["frames"] += len(batch)
         self.stats["largest_batch"] = max(self.stats["largest_batch"], len(batch))
-        for (source, frame), res in zip(batch, results):
-            out = frame if res is None else self.processor.annotate(frame, res)
+        for (source, frame), res, picture in zip(batch, results, pictures):
+            if self.hud is not None:
+                out = picture
+            else:
+                out = frame if res is None else self.processor.annotate(frame, res)
             try:
                 self.result_queue.put_nowait((source, out))   # skip when the consumer is behind (:614-617)
             except queue.Full:

@@ -5,7 +5,7 @@ The reference hands every camera frame to ``FaceAnalysis.get`` as a pageable Num
 synchronous host-to-device copy per frame.  Here the capture/decoder side writes BGR frames straight into
 page-locked ring slots (``host_buffer``), ``upload`` starts an asynchronous copy of a whole batch on a
 dedicated HIP copy stream and returns an event; the detector stream waits for that event only, so the copy of
-batch i+1 runs under the kernels of batch i.  The HUD overlay stays on the CPU (out of scope).
+batch i+1 runs under the kernels of batch i.  The HUD is drawn into the ring's device frames (hud.py).
 
 ``pixel_format="nv12"`` / ``"i420"``: the ring's pinned slots hold YUV 4:2:0 frames (``uint8 [H*3/2, W]``, what a video decoder
 produces: colour.py) - half the bytes on the link and in the pinned ring.  ``upload`` copies them to a device staging arena and

@@ -463,7 +463,7 @@ class FaceRecognitionProcessor:
         return getattr(self.face_detector, "det_size", None) is not None
 
     def _scan_mixed(self, frames, company_ids, k=None, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None,
-                    tracks=None, quality=None):
+                    tracks=None, quality=None, hold=None):
         """One engine pass over ``frames`` and ONE grouped scan in which frame i is matched through the view of
         ``company_ids[i]`` (top-1, or top-``k``), padding slots marked by the device face counts.  Returns None when
         no company has a gallery (nothing is run, a gate is not consulted), else a ``_Scan``: n, the slot results r, keep, the
@@ -484,7 +484,7 @@ class FaceRecognitionProcessor:
         if all(v is None for v in index_of):
             return None
         n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks,
-                                               quality)
+                                               quality, hold)
         if keep is not None:                      # the views of the active frames' companies, as a call on those frames has them
             company_ids = [company_ids[f] for f in keep]
             if r is not None:
@@ -505,10 +505,10 @@ class FaceRecognitionProcessor:
         galleries = [None if v is None else (view_set.views[v].ids, metadatas[v]) for v in index_of]
         return _Scan(n, r, keep, view_set, galleries, idx, score)
 
-    def _serve_mixed(self, frames, company_ids, k, min_score, pixel_format, matrix, gate, camera_ids, tracks, quality):
+    def _serve_mixed(self, frames, company_ids, k, min_score, pixel_format, matrix, gate, camera_ids, tracks, quality, hold=None):
         """``recognize_batch`` with one company id per frame (``k`` None) and ``identify_batch`` (top-``k``): the grouped scan,
-        the decision launch of the former, the shared read-back."""
-        got = self._scan_mixed(frames, company_ids, k, pixel_format, matrix, gate, camera_ids, tracks, quality)
+        the decision launch of the former, the shared read-back.  ``hold``: as ``_detect_embed_batch_gated``."""
+        got = self._scan_mixed(frames, company_ids, k, pixel_format, matrix, gate, camera_ids, tracks, quality, hold)
         if got is None:
             return [None] * len(frames)
         if got.idx is None:                       # no frame active, or none of the active ones has a gallery
@@ -585,9 +585,15 @@ class FaceRecognitionProcessor:
         of this frame's row alone; a shot that does not agree with the template restarts it and is scanned as it is.  Each face
         dict gains ``"template_shots"`` (the shots behind the scanned row, 0: the face's own row), and ``tracks.stats`` counts
         ``"joined"`` and ``"restarted"`` shots.  The same holds for ``identify_batch`` and for mixed-company batches."""
+        return self._recognize_batch(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks, quality)
+
+    def _recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
+                         quality=None, hold=None):
+        """``recognize_batch``; with ``hold`` (a list) the ring turn the call took is left to the caller to release
+        (``_detect_embed_batch_gated``): ``recognize_faces_batch`` draws on the ring's device frames first."""
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks, quality)
         if isinstance(company_id, (list, tuple)):
-            return self._serve_mixed(frames, company_id, None, None, pixel_format, matrix, gate, camera_ids, tracks, quality)
+            return self._serve_mixed(frames, company_id, None, None, pixel_format, matrix, gate, camera_ids, tracks, quality, hold)
         if self.face_detector is None:
             self.initialize_detector()
         matcher, metadata = self.embedding_manager.get_matcher_for_company(company_id)
@@ -595,12 +601,74 @@ class FaceRecognitionProcessor:
             logger.warning("No embeddings found for company %s", company_id)
             return None
         n, r, keep = _detect_embed_batch_gated(self, self.face_detector, frames, pixel_format, matrix, gate, camera_ids, tracks,
-                                               quality)
+                                               quality, hold)
         if r is None:                                                        # no frame active
             return [UNCHANGED] * len(frames)
         matcher, metadata, idx, score = _match_fresh(self.embedding_manager, company_id, matcher, metadata, _scan_rows(r))
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
         return _SlotFaces(r, n, idx, score, tracks, dec).frames([(matcher.ids, metadata)] * n, keep, len(frames))
+
+    def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, **kw):
+        """The reference's ``recognize_faces`` for a batch, with the HUD drawn on the DEVICE (``hud``: a ``hud.Hud``): runs
+        exactly what ``recognize_batch(frames, company_id, **kw)`` runs (``kw``: ``pixel_format``, ``matrix``, ``gate``,
+        ``camera_ids``, ``tracks``, ``quality``), then draws every frame's results into the ring's device frames - the BGR frames
+        the ring uploaded or converted from YUV, so a YUV call has a picture too - while it still holds the ring turn, queues the
+        device-to-host copy of the drawn frames and only then releases the turn.  Returns one annotated BGR ``uint8`` array per
+        frame, the caller's to keep: the frame's own size, or ``hud.out_size`` previews (``[h, w, 3]``: the frame resized to
+        fit, top-left, zero padded) - then only the previews cross the link.  ``return_results=True``: ``(frames, results)``
+        with ``results`` what ``recognize_batch`` returns.
+
+        A frame without results (no gallery, no face) comes back undrawn.  A frame answered ``UNCHANGED`` is drawn with
+        ``held[camera_id]`` when ``held`` (a dict: camera id -> the results of its last processed frame) is given, else undrawn.
+        Calls with a HUD are serialised per processor; while one holds its turn, no more than one further batch of the same
+        shape should be started on this processor from other threads (the ring is two slots deep)."""
+        import torch
+        if hud is None:
+            raise ValueError("recognize_faces_batch draws with a hud.Hud; without one call recognize_batch")
+        lock = self.__dict__.setdefault("_hud_lock", threading.Lock())
+        hold = []
+        with lock:
+            try:
+                results = self._recognize_batch(frames, company_id, hold=hold, **kw)
+                if self.face_detector is None:
+                    self.initialize_detector()
+                det = self.face_detector
+                if not hold:                                  # no gallery: nothing ran, the frames still owe a picture
+                    hold.append(_upload_turn(self, det, frames, kw.get("pixel_format", "bgr"), kw.get("matrix", "bt601")))
+                turn = hold[0]
+                per_frame = list(results) if isinstance(results, list) else [None] * len(turn.arr)
+                if held is not None and kw.get("camera_ids") is not None:
+                    per_frame = [held.get(c) if r is UNCHANGED else r for r, c in zip(per_frame, kw["camera_ids"])]
+                yuv = kw.get("pixel_format", "bgr") != "bgr"
+                shapes = [(a.shape[0] * 2 // 3, a.shape[1]) if yuv else a.shape[:2] for a in turn.arr]
+                with torch.cuda.device(det.device):
+                    stream = torch.cuda.current_stream(det.device)
+                    stream.wait_event(turn.ready)
+                    drawn = hud.draw(turn.dev if turn.table is None else (turn.dev, turn.table), per_frame, shapes=shapes)
+                    stage = self._hud_stage(tuple(drawn.shape))
+                    stage.copy_(drawn, non_blocking=True)
+                    turn.ring.release(turn.turn)              # behind the queued copy: the next upload into the slot waits
+                    hold.clear()
+                    stream.synchronize()
+                host = stage.numpy()
+                if drawn.dim() == 4:
+                    out = [host[i].copy() for i in range(len(shapes))]
+                else:                                         # the arena of a det_size engine: the frames at the ring's offsets
+                    out = [host[o:o + h * w * 3].reshape(h, w, 3).copy() for o, (h, w) in zip(turn.ring.offsets, shapes)]
+            finally:
+                for t in hold:                                # an error on the way: the slot is not left waiting
+                    t.ring.release(t.turn)
+        return (out, results) if return_results else out
+
+    def _hud_stage(self, shape):
+        """Pinned host buffer the drawn frames land in (one per shape, the oldest of 4 dropped)."""
+        import torch
+        stages = self.__dict__.setdefault("_hud_stages", collections.OrderedDict())
+        if shape not in stages:
+            while len(stages) >= 4:
+                stages.popitem(last=False)
+            stages[shape] = torch.empty(shape, dtype=torch.uint8).pin_memory()
+        return stages[shape]
 
     def annotate(self, frame, results):
         """Draw ``recognize`` / ``recognize_batch`` results onto a frame (colours of infrenceServer.py:546-553)."""
@@ -856,7 +924,7 @@ def _detect_embed_batch(owner, det, frames, pixel_format="bgr", matrix="bt601", 
 
 
 def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
-                              quality=None):
+                              quality=None, hold=None):
     """One pass of the sync-free slot pipeline over a batch of host frames (``recognize_batch`` and
     ``CameraProcessor.process_batch``): pinned staging ring (kept on ``owner``, one per batch shape and pixel format) -> copy
     stream -> ``detect_embed_slots(compact_embed=True)`` under the engine's lock.  Frames of one size, or of any sizes when the
@@ -875,7 +943,12 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
     reach it - all of them, or with a gate the kept ones, so a frame judged inactive never moves its camera's tracks.
 
     ``quality`` (``quality.FaceQuality``): handed to the engine pass, which then embeds the faces judged fit only; a call
-    without it passes no such argument on, and runs the code it always ran."""
+    without it passes no such argument on, and runs the code it always ran.
+
+    ``hold`` (a list): the ring turn is NOT released here.  A ``_HeldTurn`` is appended instead - the ring, the turn, the host
+    frames, the ring's device frames of the WHOLE batch (and their frame table under ``det_size``) and the upload's event - and
+    the caller releases it (``ring.release(turn)``) once its own work on those device frames is queued: until then the next
+    upload into that slot waits.  None: released here, as ever."""
     import torch
     arr, ring, turn = _ring_turn(owner, det, frames, pixel_format, matrix)
     n, det_size = len(arr), getattr(det, "det_size", None)
@@ -891,6 +964,8 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
                 ring.host_frame(turn, i)[...] = a
             dev, table, ready = ring.upload(turn)
             ragged = {"table": table, "det_scale": ring.det_scale}
+        if hold is not None:
+            hold.append(_HeldTurn(ring, turn, arr, dev, ragged.get("table"), ready))
         keep = None
         if gate is not None:
             torch.cuda.current_stream(det.device).wait_event(ready)
@@ -899,7 +974,8 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
                 keep = [int(f) for f in np.flatnonzero(active)]
                 n = len(keep)
                 if n == 0:
-                    ring.release(turn)
+                    if hold is None:
+                        ring.release(turn)
                     return 0, None, keep
                 sel = torch.tensor(keep, dtype=torch.int64).to(det.device)
                 if det_size is None:
@@ -912,8 +988,32 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
         if quality is not None:
             ragged = dict(ragged, quality=quality)
         r = det.detect_embed_slots(dev, ready_event=ready, compact_embed=True, **ragged)    # results go to the host anyway
-        ring.release(turn)
+        if hold is None:
+            ring.release(turn)
     return n, r, keep
+
+
+# A ring turn whose release is the caller's (``_detect_embed_batch_gated(hold=...)``): ``dev`` is the ring's device batch
+# uint8 [n,H,W,3] - or its arena, with ``table`` the frame table - of ALL the call's frames, ``ready`` the upload's event
+_HeldTurn = collections.namedtuple("_HeldTurn", "ring turn arr dev table ready")
+
+
+def _upload_turn(owner, det, frames, pixel_format, matrix):
+    """The front of ``_detect_embed_batch_gated`` alone: the frames into their ring and up to the device (a YUV ring converts
+    them there); the turn is the caller's to release.  For a call that has nothing to run the engine on, but a picture to return."""
+    import torch
+    arr, ring, turn = _ring_turn(owner, det, frames, pixel_format, matrix)
+    with det._lock, torch.cuda.device(det.device):
+        if getattr(det, "det_size", None) is None:
+            host = ring.host_buffer(turn)
+            for i, a in enumerate(arr):
+                host[i] = a
+            dev, ready = ring.upload(turn)
+            return _HeldTurn(ring, turn, arr, dev, None, ready)
+        for i, a in enumerate(arr):
+            ring.host_frame(turn, i)[...] = a
+        dev, table, ready = ring.upload(turn)
+        return _HeldTurn(ring, turn, arr, dev, table, ready)
 
 
 def _ring_turn(owner, det, frames, pixel_format, matrix):

@@ -49,6 +49,7 @@ typedef void* fr_stream_t;
  * and for fr_face_quality_f16 (face quality: which aligned faces are worth the embed net),
  * and for fr_track_resolve_quality_i32 (judging face tracks: embed, carry or reject per face, only fit rows enter the bank),
  * and for fr_track_fuse_f32 (track templates: a track's last K shots fused into one scan query),
+ * and for fr_hud_draw_u8 / fr_hud_draw_refs_u8 (the device HUD: recognition results drawn into the frames),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -835,6 +836,48 @@ int fr_frame_activity_u8(const uint8_t* frames, int N, int H, int W, const int32
 int fr_frame_activity_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* slot, int S, uint8_t* grid, int32_t* geom,
                               int32_t* idle, int C, uint8_t* cur, int32_t* changed, int32_t* active, int thr, int min_cells,
                               int max_idle, fr_stream_t stream);
+
+/* Device HUD: the last stage of the live path (the reference's recognize_faces returns the frame with a HUD drawn on every face,
+ * infrenceServer.py:418-513), drawn IN PLACE into BGR u8 frames on the device.  The picture is defined by
+ * tests/helpers/hud_ref.py and reproduced byte for byte (32-bit integer arithmetic only): per pixel a fold over the frame's faces
+ * in slot order and, within a face, over its layers.  Rectangles are inclusive on both ends; pixels outside the frame do not
+ * exist.  With s = scale (every length constant is multiplied by it) and c the face's colour:
+ *   1. box     [x1,x2] x [y1,y2] minus [x1+2s,x2-2s] x [y1+2s,y2-2s]:  p = (102 c + 154 p + 128) >> 8
+ *   2. ticks   p = c; L = 15 s, h = s; per corner (cx, cy) of (x1,y1) (x2,y1) (x1,y2) (x2,y2), u = x - cx, v = y - cy:
+ *              [cx,cx+L] x [cy-h,cy+h],  [cx-h,cx+h] x [cy,cy+L],  0 <= u,v <= L and |u + v - L| <= h
+ *   3. bars    bx = x2 + 10 s.  Detection: outline [bx,bx+6s] x [y1,y2], s thick inward, (100,100,100); fill [bx,bx+6s] x
+ *              [y2-dh,y2] in (255,140,0); glyph 'D', white, glyph scale s, top-left (bx-2s, y1-12s).  Recognition: the same at
+ *              bx + 12 s, filled in c over rh rows, glyph 'R'.  A height of 0 still fills one row.
+ *   4. panel   g = 2 s; pw = maxlen 6 g + 20 s, ph = nlines 18 s + 10 s; px = max(0, min(x1, W - pw)); py = max(0, y2 + 10 s),
+ *              and py = max(0, y1 - ph - 10 s) if py + ph > H.  Background [px,px+pw] x [py,py+ph]:
+ *              p = (205 * 30 + 51 p + 128) >> 8; border s thick inward in c; line i in white, glyph scale g, top-left
+ *              (px + 10 s, py + s + 18 s i).
+ * Text: font is a DEVICE table u8 [95][7], glyph (ch - 0x20) as seven row masks, bit 4 the leftmost of 5 columns (the host's
+ * one table: hud_font.py; the library holds no copy).  A glyph pixel covers g x g pixels, a character cell is 6 g wide; a byte
+ * outside 0x20 .. 0x7E is drawn as '?'.
+ *
+ * counts i32 [n]; faces i32 [n][cap][FR_HUD_K], one record per face:
+ *   [0..3] x1 y1 x2 y2 (ordered by the host)   [4..6] B G R   [7] dh   [8] rh   [9] nlines (0 .. 4)
+ *   [10..13] the lengths of the lines in bytes   [14..15] reserved, 0
+ * text u8 [n][cap][4][max_chars].  Slots j >= counts[f] are never read (counts is clamped to 0 .. cap).  What a record holds is
+ * normalised before it is drawn: coordinates clamped to +-2^20, colours modulo 256, dh / rh clamped to [0, max(y2 - y1, 0)],
+ * nlines to 0 .. 4, lengths to 0 .. max_chars.
+ * One launch, a gather over output pixels in tiles of 16 x 64; a tile that no face's extent (the bounding rectangle of its
+ * layers) meets is neither read nor written, and a pixel no layer hits is not written.  Any byte alignment of the frames.
+ *
+ * fr_hud_draw_u8: a uniform batch u8 [N,H,W,3].  fr_hud_draw_refs_u8: a DEVICE frame table (data - written here, the const of
+ * the struct notwithstanding -, H and W are read; the table a RaggedIngest hands out serves as it is); an entry with a
+ * non-positive side, of 2 GiB or more or with a null pointer is skipped as a whole.  Refused before any launch: more than 65535
+ * frames or a negative count of them, cap outside 1 .. FR_HUD_MAX_CAP, max_chars outside 1 .. FR_HUD_MAX_CHARS, scale outside
+ * 1 .. 8, non-positive H or W, a frame of 2 GiB or more (H*W*3 >= 2^31), a null pointer with n > 0.  n == 0 returns FR_OK and
+ * reads nothing.  Added under ABI 106: no existing signature changed. */
+#define FR_HUD_K 16
+#define FR_HUD_MAX_CAP 64
+#define FR_HUD_MAX_CHARS 64
+int fr_hud_draw_u8(uint8_t* frames, int N, int H, int W, const int32_t* counts, int cap, const int32_t* faces,
+                   const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
+int fr_hud_draw_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* counts, int cap, const int32_t* faces,
+                        const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- face tracks ----
  * Between detect and align: is this detection a face the camera's previous frame already showed, so that the embedding held
