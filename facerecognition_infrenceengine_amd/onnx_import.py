@@ -13,8 +13,12 @@ the exporter (then the conv carries a bias and the state dict gets ``<conv>.bias
 the oracle treat a missing BN as the identity).  The pre-activation ``bn1`` of a block can never be folded by an
 exporter (zero padding sits between it and the conv) and must be present.
 
-No file of this kind exists in the image: the mapping is tested on graphs written by tests/helpers/onnx_write.py
-from seeded state dicts (both styles), not on a real pack - DESIGN.md says so.
+No real pack exists in the image.  The mapping is tested on two independent writers: graphs written by
+tests/helpers/onnx_write.py from seeded state dicts, and files written by torch's own TorchScript exporter (the exporter
+family insightface's packs came from) from plain nn.Modules, over its export styles: tests/test_onnx_torch_export.py.
+Constants that reach their reader through Identity / Unsqueeze / Squeeze / Reshape / Transpose / Cast nodes are resolved
+once, in front of all three mappers (``_fold_constant_views``; the SCRFD mapper evaluates the same ops, ``_const_eval``,
+while it walks the shape arithmetic of a dynamic-shape export).
 """
 import struct
 
@@ -215,6 +219,97 @@ def read_onnx(path):
     return OnnxGraph([n for n in nodes if n.op != "Constant"], inits, [i for i in inputs if i not in inits], outputs, vshapes)
 
 
+# --------------------------------------------------------------------------- constants behind nodes
+
+_CAST = {1: np.float32, 6: np.int32, 7: np.int64, 11: np.float64}
+
+
+def _who(n):
+    return f"node {n.name or (n.outputs[0] if n.outputs else '?')!r} ({n.op})"
+
+
+def _const_eval(n, a):
+    """The value of node n on the constant inputs a (None for an omitted one): the shape arithmetic of dynamic-shape
+    exports, and the views (Identity, Unsqueeze, Squeeze, Reshape, Transpose, Cast) an exporter may leave between an
+    initialiser and its reader.  Raises ValueError naming the node for any other op."""
+    op = n.op
+    if op == "Gather":
+        return np.take(a[0], np.asarray(a[1]).astype(np.int64), axis=int(n.attrs.get("axis", 0)))
+    if op == "Slice":
+        data = np.asarray(a[0])
+        if len(a) > 1:
+            starts, ends = a[1], a[2]
+            axes = a[3] if len(a) > 3 and a[3] is not None else np.arange(len(starts))
+            stp = a[4] if len(a) > 4 and a[4] is not None else np.ones(len(starts), np.int64)
+        else:
+            starts, ends = n.attrs["starts"], n.attrs["ends"]
+            axes, stp = n.attrs.get("axes", list(range(len(starts)))), [1] * len(starts)
+        sl = [slice(None)] * data.ndim
+        for s, e, ax, sp in zip(np.ravel(starts), np.ravel(ends), np.ravel(axes), np.ravel(stp)):
+            sl[int(ax)] = slice(int(s), int(min(e, 2 ** 62)), int(sp))
+        return data[tuple(sl)]
+    if op == "Concat":
+        return np.concatenate([np.atleast_1d(x) for x in a], axis=int(n.attrs.get("axis", 0)))
+    if op in ("Unsqueeze", "Squeeze"):
+        axes = n.attrs.get("axes")
+        if axes is None and len(a) > 1 and a[1] is not None:
+            axes = [int(x) for x in np.ravel(a[1])]
+        x = np.asarray(a[0])
+        if op == "Squeeze":
+            return np.squeeze(x, axis=tuple(axes) if axes else None)
+        if axes is None:
+            raise ValueError(f"{_who(n)}: Unsqueeze without axes")
+        rank = x.ndim + len(axes)
+        for ax in sorted(ax + rank if ax < 0 else ax for ax in axes):
+            x = np.expand_dims(x, ax)
+        return x
+    if op == "Reshape":
+        x = np.asarray(a[0])
+        tgt = [int(v) for v in (np.ravel(a[1]) if len(a) > 1 and a[1] is not None else n.attrs.get("shape", []))]
+        if not n.attrs.get("allowzero", 0):
+            if any(v == 0 and i >= x.ndim for i, v in enumerate(tgt)):
+                raise ValueError(f"{_who(n)}: Reshape of a {x.shape} constant to {tgt}")
+            tgt = [x.shape[i] if v == 0 else v for i, v in enumerate(tgt)]
+        return x.reshape(tgt)
+    if op == "Transpose":
+        x = np.asarray(a[0])
+        return np.transpose(x, n.attrs.get("perm", list(range(x.ndim))[::-1]))
+    if op == "Cast":
+        to = n.attrs.get("to")
+        if to not in _CAST:
+            raise ValueError(f"{_who(n)}: cast to ONNX data type {to} not supported")
+        return np.asarray(a[0]).astype(_CAST[to])
+    if op in ("Mul", "Add", "Sub"):
+        return {"Mul": np.multiply, "Add": np.add, "Sub": np.subtract}[op](a[0], a[1])
+    if op == "Div":
+        x, y = np.asarray(a[0]), np.asarray(a[1])
+        return x // y if x.dtype.kind in "iu" and y.dtype.kind in "iu" else x / y
+    if op in ("Floor", "Ceil"):
+        return (np.floor if op == "Floor" else np.ceil)(a[0])
+    if op == "Identity":
+        return a[0]
+    raise ValueError(f"{_who(n)}: op {n.op} is not supported (on constant inputs)")
+
+
+_CONST_VIEWS = ("Identity", "Unsqueeze", "Squeeze", "Reshape", "Transpose", "Cast")
+
+
+def _fold_constant_views(g):
+    """-> the graph with every Identity / Unsqueeze / Squeeze / Reshape / Transpose / Cast that reads constants only
+    evaluated: its output becomes an initialiser and the node goes.  Exporters leave such chains between a parameter
+    and its reader - a PReLU slope behind an Unsqueeze when constant folding is off, one initialiser shared by equal
+    parameters through Identity nodes, the transposed weight of a matmul(x, W.t()) - and the mappers below then meet an
+    initialiser like any other.  The values are views or casts of the stored ones: no arithmetic happens here."""
+    init, nodes = dict(g.initializers), []
+    for n in g.nodes:
+        ins = [t for t in n.inputs if t]
+        if n.op in _CONST_VIEWS and ins and n.outputs and all(t in init for t in ins):
+            init[n.outputs[0]] = _const_eval(n, [init[t] if t else None for t in n.inputs])
+        else:
+            nodes.append(n)
+    return OnnxGraph(nodes, init, g.inputs, g.outputs, g.value_shapes)
+
+
 # --------------------------------------------------------------------------- IResNet graph -> state dict
 
 _ARCH_BY_BLOCKS = {(2, 2, 2, 2): "r18", (3, 4, 6, 3): "r34", (3, 4, 14, 3): "r50", (3, 13, 30, 3): "r100"}
@@ -224,7 +319,7 @@ def iresnet_state_from_onnx(path_or_graph):
     """-> (state dict of numpy float32 arrays in the naming of weights.py, arch).  Raises ValueError with the node
     it stopped at when the graph is not an ArcFace IResNet (conv-bn-prelu stem, pre-activation residual blocks,
     bn-flatten-fc-bn head)."""
-    g = path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph)
+    g = _fold_constant_views(path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph))
     init = g.initializers
     consumers = {}
     producer = {}
@@ -389,7 +484,6 @@ class ScrfdPlan:
                          for s in steps if s["op"] in ("conv", "dwconv"))
 
 
-_CAST = {1: np.float32, 6: np.int32, 7: np.int64, 11: np.float64}
 _NEAREST_OK = {("asymmetric", "floor"), ("asymmetric", "round_prefer_floor"), ("half_pixel", "round_prefer_floor"),
                ("pytorch_half_pixel", "round_prefer_floor")}
 
@@ -422,8 +516,7 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
     resized = {}                         # tensor name -> (source tensor id, factor): a Resize waiting for its Add
     nhwc, flat, sigm = {}, {}, {}        # tail views: name -> tensor id / (tensor id, K) / (tensor id, K)
 
-    def who(n):
-        return f"node {n.name or (n.outputs[0] if n.outputs else '?')!r} ({n.op})"
+    who = _who
 
     def new(shape):
         tid = len(shapes)
@@ -450,52 +543,6 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             raise ValueError(f"{who(n)}: {key} {v} is not square")
         return int(v[0])
 
-    def host_eval(n):
-        a = [host[t] if t else None for t in n.inputs]
-        op = n.op
-        if op == "Gather":
-            return np.take(a[0], np.asarray(a[1]).astype(np.int64), axis=int(n.attrs.get("axis", 0)))
-        if op == "Slice":
-            data = np.asarray(a[0])
-            if len(a) > 1:
-                starts, ends = a[1], a[2]
-                axes = a[3] if len(a) > 3 and a[3] is not None else np.arange(len(starts))
-                stp = a[4] if len(a) > 4 and a[4] is not None else np.ones(len(starts), np.int64)
-            else:
-                starts, ends = n.attrs["starts"], n.attrs["ends"]
-                axes, stp = n.attrs.get("axes", list(range(len(starts)))), [1] * len(starts)
-            sl = [slice(None)] * data.ndim
-            for s, e, ax, sp in zip(np.ravel(starts), np.ravel(ends), np.ravel(axes), np.ravel(stp)):
-                sl[int(ax)] = slice(int(s), int(min(e, 2 ** 62)), int(sp))
-            return data[tuple(sl)]
-        if op == "Concat":
-            return np.concatenate([np.atleast_1d(x) for x in a], axis=int(n.attrs.get("axis", 0)))
-        if op in ("Unsqueeze", "Squeeze"):
-            axes = n.attrs.get("axes")
-            if axes is None and len(a) > 1:
-                axes = [int(x) for x in np.ravel(a[1])]
-            x = np.asarray(a[0])
-            if op == "Squeeze":
-                return np.squeeze(x, axis=tuple(axes) if axes else None)
-            for ax in sorted(axes):
-                x = np.expand_dims(x, ax)
-            return x
-        if op == "Cast":
-            to = n.attrs.get("to")
-            if to not in _CAST:
-                raise ValueError(f"{who(n)}: cast to ONNX data type {to} not supported")
-            return np.asarray(a[0]).astype(_CAST[to])
-        if op in ("Mul", "Add", "Sub"):
-            return {"Mul": np.multiply, "Add": np.add, "Sub": np.subtract}[op](a[0], a[1])
-        if op == "Div":
-            x, y = np.asarray(a[0]), np.asarray(a[1])
-            return x // y if x.dtype.kind in "iu" and y.dtype.kind in "iu" else x / y
-        if op in ("Floor", "Ceil"):
-            return (np.floor if op == "Floor" else np.ceil)(a[0])
-        if op == "Identity":
-            return a[0]
-        raise ValueError(f"{who(n)}: op {n.op} is not supported (on constant inputs)")
-
     for n in g.nodes:
         ins = [t for t in n.inputs if t]
         if not n.outputs:
@@ -506,7 +553,7 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             host[out] = np.array([1, c, h, w], dtype=np.int64)
             continue
         if ins and all(t in host for t in ins):
-            host[out] = host_eval(n)
+            host[out] = _const_eval(n, [host[t] if t else None for t in n.inputs])
             continue
         if n.op == "Conv":
             if ins[0] not in dev or ins[1] not in host:
@@ -702,7 +749,10 @@ def scrfd_plan_from_onnx(path_or_graph, canvas_hw=(640, 640)):
             e[5]["f32"] = True
             outputs[e[0]] = (li, kind)
         levels.append({"stride": s, "score": ent[0][1], "bbox": ent[1][1], "kps": ent[2][1]})
-    outputs = {t: outputs[t] for t in outs}
+    # graph order: the declared outputs' where the file declares them (an exporter lists them as the module returned them,
+    # which need not be the order of the nodes), else the nodes'
+    declared = g.outputs if g.outputs and sorted(g.outputs) == sorted(outs) else outs
+    outputs = {t: outputs[t] for t in declared}
     used = {s[k] for s in steps for k in ("x", "res", "coarse", "lateral") if s.get(k) is not None}
     used |= {lv[k] for lv in levels for k in ("score", "bbox", "kps")}
     for s in steps:
@@ -739,7 +789,7 @@ def recognition_plan_from_onnx(path_or_graph):
     (``w600k_mbf.onnx``) is the shape this is written for - onto device steps by following the data flow: widths and block
     counts are the graph's own.  One input [*,3,112,112], one output [*,512].  Raises ValueError naming the node and op it
     cannot map; a graph is mapped whole or not at all."""
-    g = path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph)
+    g = _fold_constant_views(path_or_graph if isinstance(path_or_graph, OnnxGraph) else read_onnx(path_or_graph))
     if len(g.inputs) != 1:
         raise ValueError(f"expected one graph input, found {g.inputs}")
     ishape = g.value_shapes.get(g.inputs[0])
@@ -758,8 +808,7 @@ def recognition_plan_from_onnx(path_or_graph):
     flat = {}                            # tensor name -> tensor id of the 1 x 1 map it flattens
     made_by = {}                         # tensor name -> node
 
-    def who(n):
-        return f"node {n.name or (n.outputs[0] if n.outputs else '?')!r} ({n.op})"
+    who = _who
 
     def sole(n, t):
         return len(consumers.get(t, [])) == 1 and consumers[t][0] is n
