@@ -183,7 +183,7 @@ class ShardedGalleryMatcher:
         self.force_exchange = force_exchange
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.timing = None          # a list: every exchange appends its five HIP events (bench.py's exchange_ms; diagnostics)
+        self.timing = None          # a list: every exchange, top-1 or top-K, appends its five HIP events (bench.py's exchange_ms)
 
     def _stamp(self, marks, dev):
         if marks is not None and dev.type == "cuda":
@@ -195,21 +195,23 @@ class ShardedGalleryMatcher:
         """Median milliseconds of the exchange's four parts over the matches timed since ``timing = []`` was set (the caller
         synchronises first): gather_q = pack + the all-gather of the query rows (includes waiting for the slowest rank's
         embedder), scan = count row + this rank's shard scan, gather_c = pack + the all-gather of the candidates,
-        reduce.  None when nothing was timed."""
+        reduce.  ``match`` and ``match_topk`` are one exchange and both are stamped: time them apart by resetting ``timing``
+        between them.  None when nothing was timed."""
         rows = [[m[k].elapsed_time(m[k + 1]) for k in range(4)] for m in (self.timing or []) if len(m) == 5]
         if not rows:
             return None
         med = torch.tensor(rows, dtype=torch.float64).median(dim=0).values.tolist()
         return {k: round(v, 4) for k, v in zip(("gather_q", "scan", "gather_c", "reduce"), med)} | {"samples": len(rows)}
 
-    def match(self, Q):
-        """Q f32 [F_local,dim] ``normed_embedding`` rows on this rank's device (F_local <= q_max).
-        Returns (idx i64[F_local] global rows, score f32[F_local]) for the local queries."""
+    def _exchange(self, Q, k=None):
+        """The best global row (``k`` None) or the ``k`` best of every local query: the steps of the module docstring."""
         F = Q.shape[0]
         assert F <= self.q_max, "more local queries than q_max"
+        kk = () if k is None else (k,)
+        scan, reduce = (self.ops.scan, self.ops.reduce) if k is None else (self.ops.scan_topk, self.ops.reduce_topk)
         Qn = self.ops.renormalise(Q.to(torch.float32).contiguous())
         if self.world == 1 and not self.force_exchange:
-            return self.ops.scan(Qn)
+            return scan(Qn, *kk)
         dev = Q.device
         seg = self.q_max + 1
         marks = [] if self.timing is not None else None
@@ -222,38 +224,27 @@ class ShardedGalleryMatcher:
         counts = self.ops.gathered_counts(allq, self.world, self.q_max)   # gathered face counts, on the device
         # (2) scan the local shard for every gathered query slot IN PLACE: a rank's segment is its q_max query slots +
         # the count row, which is slot q_max >= count, i.e. padding like every slot past the count (skipped by the scan)
-        idx, score = self.ops.scan(allq, counts=counts, seg_len=seg)
+        idx, score = scan(allq, *kk, counts=counts, seg_len=seg)       # [n], or [n,k]: this shard's k best per slot
         self._stamp(marks, dev)
         # (3) gather the per-shard candidates and reduce those of the local queries
         n = score.shape[0]
-        pair = self.ops.pack(idx, score)
-        allp = torch.empty((self.world * n, 3), dtype=torch.int32, device=dev)
+        pair = self.ops.pack(idx.reshape(-1), score.reshape(-1))       # element-wise: a flat list of n (n*k) candidates
+        allp = torch.empty((self.world * pair.shape[0], 3), dtype=torch.int32, device=dev)
         dist.all_gather_into_tensor(allp, pair, group=self.group)
         self._stamp(marks, dev)
-        out = self.ops.reduce(allp, self.world, n, self.rank * seg, F)
+        out = reduce(allp, self.world, n, *kk, self.rank * seg, F)
         self._stamp(marks, dev)
         if marks:
             self.timing.append(marks)
         return out
 
+    def match(self, Q):
+        """Q f32 [F_local,dim] ``normed_embedding`` rows on this rank's device (F_local <= q_max).
+        Returns (idx i64[F_local] global rows, score f32[F_local]) for the local queries."""
+        return self._exchange(Q)
+
     def match_topk(self, Q, k):
         """The k best global rows per local query: (idx i64[F_local,k], score f32[F_local,k]), ranked by score
         descending, global row ascending; empty slots (-1, -1.0).  The same two collectives as ``match``; the second
         carries k candidates per query slot (int32 [n*k, 3]: n * k * 12 bytes per rank)."""
-        F = Q.shape[0]
-        assert F <= self.q_max, "more local queries than q_max"
-        Qn = self.ops.renormalise(Q.to(torch.float32).contiguous())
-        if self.world == 1 and not self.force_exchange:
-            return self.ops.scan_topk(Qn, k)
-        dev = Q.device
-        seg = self.q_max + 1
-        send = self.ops.pack_queries(Qn, self.q_max)
-        allq = torch.empty((self.world * seg, self.dim), dtype=torch.float32, device=dev)
-        dist.all_gather_into_tensor(allq, send, group=self.group)
-        counts = self.ops.gathered_counts(allq, self.world, self.q_max)
-        idx, score = self.ops.scan_topk(allq, k, counts=counts, seg_len=seg)       # [n,k]: this shard's k best per slot
-        n = score.shape[0]
-        pair = self.ops.pack(idx.reshape(-1), score.reshape(-1))                   # element-wise: a flat n*k list
-        allp = torch.empty((self.world * n * k, 3), dtype=torch.int32, device=dev)
-        dist.all_gather_into_tensor(allp, pair, group=self.group)
-        return self.ops.reduce_topk(allp, self.world, n, k, self.rank * seg, F)
+        return self._exchange(Q, k)

@@ -3,7 +3,7 @@
 Mirrors /root/reference/trainingServer.py:170-247,328,355-358,393 (largest face -> pose consistency ->
 mean -> duplicate check -> pickled float32[512] row) and /root/reference/peopleCount.py:52-91,432-449
 (10-deep running mean, first cluster with dot >= 0.65).  The O(N) per-row GridFS read + cosine loop of
-the reference's duplicate check becomes one `fr_gallery_first_above_f32` scan of the device gallery.
+the reference's duplicate check becomes one first-above scan of the device gallery (``first_above``).
 
 ``Enroller.enrol`` is the one-job form; ``Enroller.enrol_batch`` / ``enrol_slots`` run a whole batch of jobs with one
 engine pass and one `fr_enrol_batch_f32` call, giving job for job what enrolling them one after the other gives
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .gallery import GalleryView, StaleViewError
+from .gallery import GalleryView, StaleViewError, read_back  # noqa: F401  (StaleViewError: what a stale view raises here)
 
 DIM = 512
 # include/frhip.h FR_ENROL_* (tests/test_enrol_batch_abi.py compares)
@@ -147,7 +147,7 @@ class Enroller:
         order = [int(i) for im in job_images for i in im]
         if any(not 0 <= i < len(firsts) for i in order):
             raise ValueError("job_images names an image the slots do not hold")
-        G, view, N = _gallery_args(gallery)
+        src = gallery.row_source()
         dev, I = self.device, len(order)
         job_first = np.cumsum([0] + [len(im) for im in job_images])
         # one pinned staging block, one asynchronous copy: image order, first rows, job_first
@@ -170,9 +170,9 @@ class Enroller:
             counts = torch.cat([p["counts"].reshape(-1) for p in parts]).to(dev, torch.int32)
             img_first, jf = meta[I:2 * I], meta[2 * I:]
             img_count = counts.index_select(0, meta[:I].to(torch.int64)).contiguous()     # the detector's counts, never read here
-            ws = torch.empty(int(self.lib.fr_enrol_batch_workspace(J, N)), dtype=torch.uint8, device=dev)
+            ws = torch.empty(int(self.lib.fr_enrol_batch_workspace(J, src.N)), dtype=torch.uint8, device=dev)
             self.lib.fr_enrol_batch_f32(_lib.ptr(E), _lib.ptr(bbox), E.shape[0], _lib.ptr(img_first), _lib.ptr(img_count),
-                                        I, _lib.ptr(jf), J, max_poses, DIM, _lib.ptr(G), _lib.ptr(view), N,
+                                        I, _lib.ptr(jf), J, max_poses, DIM, _lib.ptr(src.G), _lib.ptr(src.view), src.N,
                                         float(self.similarity_threshold), float(self.duplicate_threshold),
                                         _lib.ptr(status), _lib.ptr(pair), _lib.ptr(face), _lib.ptr(avg), _lib.ptr(row),
                                         _lib.ptr(dup_pos), _lib.ptr(dup_score), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
@@ -226,7 +226,7 @@ class Enroller:
             raise ValueError("ids and jobs disagree")
         if commit and not (isinstance(gallery, GalleryView) and ids is not None):
             raise ValueError("commit=True needs a GalleryView and ids")
-        _gallery_args(gallery)                                       # a stale view: before the engine runs
+        N = gallery.row_source().N                                   # a stale view raises: before the engine runs
         result = EnrolBatchResult()
         if not jobs:
             result.view = gallery if commit else None
@@ -245,13 +245,8 @@ class Enroller:
                 job_images.append(index[k:k + len(job)])
                 k += len(job)
             out = self.enrol_slots(parts, job_images, gallery)
-            names = ("status", "pair", "avg", "dup_pos")
-            host = [torch.empty(out[n].shape, dtype=out[n].dtype).pin_memory() for n in names]
-            for h, n in zip(host, names):
-                h.copy_(out[n], non_blocking=True)
-            torch.cuda.current_stream().synchronize()                # the one synchronisation of the batch
-        status, pair, avg, dup_pos = (h.numpy() for h in host)
-        N = len(gallery.ids) if isinstance(gallery, GalleryView) else gallery.G.shape[0]
+            # the one synchronisation of the batch
+            status, pair, avg, dup_pos = read_back(self.device, out["status"], out["pair"], out["avg"], out["dup_pos"])
         for j in range(len(jobs)):
             st = int(status[j])
             r = {"status": STATUS_NAMES[st]}
@@ -277,19 +272,10 @@ class Enroller:
         return result
 
 
-def _gallery_args(gallery):
-    """(rows, view slots or None, number of positions) of a GalleryMatcher or a GalleryView (which must be current)."""
-    if isinstance(gallery, GalleryView):
-        if gallery.generation != gallery.gallery.generation:
-            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
-        return gallery.gallery.G, gallery.slots, len(gallery.ids)
-    return gallery.G, None, gallery.G.shape[0]
-
-
 def first_above(lib, matcher, embedding, thr, inclusive):
     """Lowest gallery row whose dot with the L2-normalised query passes the threshold.  ``matcher``: a GalleryMatcher, or
-    a GalleryView (position in the view's order; scanned through its slot list by fr_gallery_first_above_blocked_f32)."""
-    G, view, N = _gallery_args(matcher)
+    a GalleryView (position in the view's order; scanned through its slot list by the blocked entry)."""
+    src = matcher.row_source()
     q = torch.from_numpy(np.asarray(embedding, np.float32).reshape(1, DIM)).to(matcher.device)
     qn = torch.empty_like(q)
     idx = torch.empty(1, dtype=torch.int64, device=matcher.device)
@@ -298,13 +284,11 @@ def first_above(lib, matcher, embedding, thr, inclusive):
     with torch.cuda.device(matcher.device):
         s = _lib.stream_ptr()
         lib.fr_l2norm_rows_f32(_lib.ptr(q), _lib.ptr(qn), 1, DIM, s)
-        if view is None:
-            lib.fr_gallery_first_above_f32(_lib.ptr(qn), _lib.ptr(G), 1, N, DIM, float(thr),
-                                           1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), 8, s)
+        tail = (1, src.N, DIM, float(thr), 1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), 8, s)
+        if src.view is None:
+            lib.fr_gallery_first_above_f32(_lib.ptr(qn), _lib.ptr(src.G), *tail)
         else:
-            lib.fr_gallery_first_above_blocked_f32(_lib.ptr(qn), _lib.ptr(G), _lib.ptr(view), None, 1, N, DIM, float(thr),
-                                                   1 if inclusive else 0, 0, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws),
-                                                   8, s)
+            lib.fr_gallery_first_above_blocked_f32(_lib.ptr(qn), _lib.ptr(src.G), _lib.ptr(src.view), None, *tail)
     return int(idx.item()), float(score.item())
 
 

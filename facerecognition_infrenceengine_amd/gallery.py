@@ -5,7 +5,11 @@ Replaces the per-face Python loop over ``dict[id -> float32[512]]`` at
 of a row-indexed ``[N,512]`` matrix.  Row order = insertion order of the reference's
 dict (employees in cursor order, then visitors: infrenceServer.py:264,288); the winner is
 the maximum score, lowest row on exact ties (strict ``>`` in the reference loop).
+
+Every scan of plain rows or of a view goes through ``_scan``: one prelude, one table (``_ENTRIES``) that names the
+entry point and its arguments.  What is scanned is a ``RowSource``.
 """
+import collections
 import threading
 
 import numpy as np
@@ -17,11 +21,16 @@ DIM = 512
 TOPK_MAX = 16                  # include/frhip.h FR_TOPK_MAX
 SCANS = ("f32", "f16", "f8")
 _SHADOW_KIND = {"f16": 1, "f8": 2}      # include/frhip.h FR_SHADOW_F16 / FR_SHADOW_F8
-_PIN = threading.local()       # pinned host buffers of GalleryMatcher.match, per thread and query count
+_PIN = threading.local()       # pinned host buffers of read_back, per thread, shapes and dtypes
 _TLS = threading.local()       # .topk: what this thread's last top-K call ran (last_topk())
 # Rows from which an f16-coarse gallery answers top-K by the certified coarse pass instead of the exact scan.  Not yet
 # measured on hardware for the top-K path: the size where the top-1 coarse view scan won (profiles/view_scan.txt).
 COARSE_TOPK_MIN_ROWS = 100_000
+
+# What a scan reads: the f32 rows ``G``; ``view``, the int64 slot list the positions go through (None: row = position);
+# ``N`` positions; the ``capacity`` of the slab ``G``; the ``coarse`` copy of ``G`` and its ``kind`` "f16" / "f8" (both
+# None without one); ``gmax``, the bound on the row norms that goes with an f16 copy (else None).
+RowSource = collections.namedtuple("RowSource", "G view N capacity coarse kind gmax")
 
 
 def last_topk():
@@ -57,31 +66,135 @@ class DuplicatePairs:
         return len(self.pairs)
 
 
-def _pairs_device(owner, G, view, N, thr, inclusive, max_pairs, max_ranges=0):
-    """fr_gallery_pairs_above_f16 on the current stream of ``owner.device``: (keys int64 [max_pairs], scores float32
-    [max_pairs], counts int32 [4]), device tensors, no synchronisation."""
-    lib, dev = owner.lib, owner.device
+def _workspace(device, need):
+    """Scratch for ONE scan, taken from torch's caching allocator under the current stream: the block is
+    owned by that stream, so concurrent matches on different streams never share (or free) each other's
+    partial results.  (A per-object buffer did: two pipes driving one matcher overwrote ws_score/ws_idx.)"""
+    return torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+
+
+def read_back(device, *tensors):
+    """Several device results, ONE synchronisation: asynchronous copies into pinned host memory, then a sync of the
+    current stream of ``device``.  Returns the NumPy copies.  The pinned buffers are kept per thread (several may read
+    back at once), keyed by the results' shapes and dtypes, 16 sets at the most."""
+    pin = _PIN.__dict__.setdefault("bufs", {})
+    key = tuple((t.shape, t.dtype) for t in tensors)
+    host = pin.get(key)
+    if host is None:
+        if len(pin) >= 16:
+            pin.clear()
+        host = pin[key] = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in tensors]
+    with torch.cuda.device(device):
+        for dst, src in zip(host, tensors):
+            dst.copy_(src, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    return [h.numpy().copy() for h in host]
+
+
+def _check_k(k):
+    if not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError(f"k must be 1..{TOPK_MAX} (got {k})")
+    return int(k)
+
+
+def _queries(lib, device, Q, renormalise, counts, seg_len):
+    """The query half of every scan's prelude: (Q as float32 [F,512] on ``device`` - L2-normalised by one launch with
+    ``renormalise``, infrenceServer.py:532 -, F); ``counts`` / ``seg_len`` are checked against F.  Called under
+    ``torch.cuda.device(device)``."""
+    Q = Q.to(device, torch.float32).contiguous().reshape(-1, DIM)
+    F = Q.shape[0]
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
+    if renormalise and F:
+        Qn = torch.empty_like(Q)
+        lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, _lib.stream_ptr())
+        Q = Qn
+    return Q, F
+
+
+def _outputs(device, F, k, path="exact"):
+    """(idx int64, score float32) of a top-1 ([F]) or top-``k`` ([F,k]) scan; the latter is what ``last_topk`` reports."""
+    if k is not None:
+        _TLS.topk = {"path": path, "flags": None}
+    shape = (F,) if k is None else (F, k)
+    return torch.empty(shape, dtype=torch.int64, device=device), torch.empty(shape, dtype=torch.float32, device=device)
+
+
+# (top-K, through a slot list, coarse kind used): the workspace entry, the scan entry, and its arguments between Q and
+# the outputs; ``p`` is the RowSource with pointers for tensors.  Every entry then takes idx, score, (flags: coarse
+# top-K,) workspace, bytes, (counts, seg_len: plain rows only,) stream.
+_WS, _WS_TOPK = "fr_gallery_match_workspace", "fr_gallery_topk_workspace"       # the exact scans share theirs
+_ENTRIES = {
+    (False, False, None): (_WS, "fr_gallery_match_f32", lambda p, F, k, off: (p.G, F, p.N, DIM, off)),
+    (False, False, "f16"): ("fr_gallery_match_f16_workspace", "fr_gallery_match_f16",
+                            lambda p, F, k, off: (p.coarse, p.G, F, p.N, DIM, off)),
+    (False, False, "f8"): ("fr_gallery_match_f8_workspace", "fr_gallery_match_f8",
+                           lambda p, F, k, off: (p.coarse, p.G, F, p.N, DIM, off)),
+    (False, True, None): (_WS, "fr_gallery_match_view_f32", lambda p, F, k, off: (p.G, p.view, F, p.N, DIM)),
+    (False, True, "f16"): ("fr_gallery_match_view_f16_workspace", "fr_gallery_match_view_f16",
+                           lambda p, F, k, off: (p.coarse, p.G, p.view, F, p.N, p.capacity, DIM)),
+    (False, True, "f8"): ("fr_gallery_match_view_f8_workspace", "fr_gallery_match_view_f8",
+                          lambda p, F, k, off: (p.coarse, p.G, p.view, F, p.N, p.capacity, DIM)),
+    (True, False, None): (_WS_TOPK, "fr_gallery_topk_f32", lambda p, F, k, off: (p.G, F, p.N, DIM, k, off)),
+    (True, False, "f16"): ("fr_gallery_topk_f16_workspace", "fr_gallery_topk_f16",
+                           lambda p, F, k, off: (p.coarse, p.G, F, p.N, DIM, k, off, p.gmax)),
+    (True, True, None): (_WS_TOPK, "fr_gallery_topk_view_f32", lambda p, F, k, off: (p.G, p.view, F, p.N, DIM, k)),
+    (True, True, "f16"): ("fr_gallery_topk_view_f16_workspace", "fr_gallery_topk_view_f16",
+                          lambda p, F, k, off: (p.coarse, p.G, p.view, F, p.N, p.capacity, DIM, k, p.gmax)),
+}
+
+
+def _scan(lib, device, src, Q, k, renormalise, kind, row_offset=0, counts=None, seg_len=0):
+    """The scan of ``src`` (a RowSource) for the rows of ``Q`` on the current stream of ``device``: the best row per query
+    (``k`` None: idx int64 [F], score float32 [F]) or the ``k`` best ([F,k]; records ``last_topk()``).  ``kind``: the
+    coarse copy to scan in one pass before the exact f32 re-scoring ("f16" / "f8"; top-K: "f16", the certified pass), or
+    None for the exact f32 scan.  ``row_offset`` / ``counts`` / ``seg_len`` go to the scans of plain rows only."""
+    with torch.cuda.device(device):
+        Q, F = _queries(lib, device, Q, renormalise, counts, seg_len)
+        idx, score = _outputs(device, F, k, "coarse" if kind else "exact")
+        if F == 0:
+            return idx, score
+        wsz, entry, head = _ENTRIES[k is not None, src.view is not None, kind]
+        kk = () if k is None else (k,)
+        flags = None
+        if kk and kind:
+            flags = _TLS.topk["flags"] = torch.empty(F, dtype=torch.int32, device=device)
+        # pointers of tensors that src, flags and counts keep alive until the call returns (_lib.ptr)
+        p = RowSource(_lib.ptr(src.G), _lib.ptr(src.view), src.N, src.capacity, _lib.ptr(src.coarse), src.kind,
+                      _lib.ptr(src.gmax))
+        certified = () if flags is None else (_lib.ptr(flags),)
+        padding = (_lib.ptr(counts), seg_len) if src.view is None else ()
+        ws = _workspace(device, getattr(lib, wsz)(F, src.N, *kk))
+        getattr(lib, entry)(_lib.ptr(Q), *head(p, F, k, row_offset), _lib.ptr(idx), _lib.ptr(score), *certified,
+                            _lib.ptr(ws), ws.numel(), *padding, _lib.stream_ptr())
+    return idx, score
+
+
+def _topk_kind(src, min_rows):
+    """The coarse kind a top-K scan of ``src`` uses: the certified pass over an f16 copy of at least ``min_rows`` rows."""
+    return "f16" if src.kind == "f16" and src.N >= min_rows else None
+
+
+def _pairs_device(lib, device, src, thr, inclusive, max_pairs, max_ranges=0):
+    """fr_gallery_pairs_above_f16 over ``src`` on the current stream of ``device``: (keys int64 [max_pairs], scores
+    float32 [max_pairs], counts int32 [4]), device tensors, no synchronisation."""
     max_pairs = int(max_pairs)
     if max_pairs < 1:
         raise ValueError("max_pairs must be at least 1")
-    keys = torch.empty(max_pairs, dtype=torch.int64, device=dev)
-    scores = torch.empty(max_pairs, dtype=torch.float32, device=dev)
-    counts = torch.empty(4, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = GalleryMatcher._workspace(owner, lib.fr_gallery_pairs_workspace(N, max_pairs))
-        lib.fr_gallery_pairs_above_f16(_lib.ptr(G), _lib.ptr(view) if view is not None else None, N, DIM, float(thr),
-                                       1 if inclusive else 0, max_pairs, int(max_ranges), _lib.ptr(keys), _lib.ptr(scores),
-                                       _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
+    keys = torch.empty(max_pairs, dtype=torch.int64, device=device)
+    scores = torch.empty(max_pairs, dtype=torch.float32, device=device)
+    counts = torch.empty(4, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        ws = _workspace(device, lib.fr_gallery_pairs_workspace(src.N, max_pairs))
+        lib.fr_gallery_pairs_above_f16(_lib.ptr(src.G), _lib.ptr(src.view), src.N, DIM, float(thr), 1 if inclusive else 0,
+                                       max_pairs, int(max_ranges), _lib.ptr(keys), _lib.ptr(scores), _lib.ptr(counts),
+                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
     return keys, scores, counts
 
 
-def _pairs_host(owner, ids, keys, scores, counts):
+def _pairs_host(device, ids, keys, scores, counts):
     """One synchronisation to read the counts, then the P pairs found travel and are sorted on the host."""
-    counts_h = torch.empty(4, dtype=torch.int32).pin_memory()
-    with torch.cuda.device(owner.device):
-        counts_h.copy_(counts, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    seen, found, flags = (int(v) for v in counts_h[:3])
+    seen, found, flags = (int(v) for v in read_back(device, counts)[0][:3])
     if flags & PAIRS_NONFINITE:
         raise ValueError("find_duplicates: a row holds NaN, an infinity or an element beyond the f16 range (+-65504)")
     if flags & PAIRS_OVERFLOW:
@@ -95,7 +208,63 @@ def _pairs_host(owner, ids, keys, scores, counts):
     return DuplicatePairs(pairs, s, [(ids[a], ids[b]) for a, b in pairs], seen)
 
 
-class GalleryMatcher:
+class _Decides:
+    """What everything that scans shares: the decision launch and ``last_topk``.  Needs ``lib`` and ``device``."""
+
+    last_topk = property(lambda self: last_topk())
+
+    def decide_device(self, idx, score, thr, unknown_thr=None):
+        """1 recognised / 0 unknown / 2 dropped (peopleCount.py:876-887 band)."""
+        d = torch.empty(idx.shape[0], dtype=torch.int32, device=self.device)
+        if idx.shape[0]:
+            with torch.cuda.device(self.device):
+                self.lib.fr_match_decide(_lib.ptr(idx), _lib.ptr(score), idx.shape[0], float(thr),
+                                         float(thr if unknown_thr is None else unknown_thr), _lib.ptr(d),
+                                         _lib.stream_ptr())
+        return d
+
+
+class _Rows(_Decides):
+    """The host-facing forms and the audit of an object with ``ids``, ``row_source()``, ``match_device`` and
+    ``match_topk_device``: GalleryMatcher (rows are positions) and GalleryView (positions in ``ids`` go through slots)."""
+
+    def match(self, Q, thr=0.4, unknown_thr=None):
+        """Host-facing: returns (ids list (None = unknown), scores float32[F], idx int64[F])."""
+        Q = torch.as_tensor(np.asarray(Q, np.float32)) if not torch.is_tensor(Q) else Q
+        idx, score = self.match_device(Q)
+        dec = self.decide_device(idx, score, thr, unknown_thr)
+        idx_h, score_h, dec_h = read_back(self.device, idx, score, dec)
+        ids = [self.ids[i] if (d == 1 and i >= 0) else None for i, d in zip(idx_h, dec_h)]
+        return ids, score_h, idx_h
+
+    def match_topk(self, Q, k, min_score=None):
+        """Host-facing: (ids, scores float32[F,k], idx int64[F,k]); ``ids[f]`` is a list of k entries in rank order,
+        None for empty slots and for slots whose score is below ``min_score``."""
+        k = _check_k(k)
+        Q = torch.as_tensor(np.asarray(Q, np.float32)) if not torch.is_tensor(Q) else Q
+        idx_h, score_h = read_back(self.device, *self.match_topk_device(Q, k))
+        ids = [[self.ids[i] if i >= 0 and (min_score is None or s >= min_score) else None for i, s in zip(ri, rs)]
+               for ri, rs in zip(idx_h, score_h)]
+        return ids, score_h, idx_h
+
+    def find_duplicates_device(self, thr=0.4, inclusive=False, max_pairs=1 << 20, max_ranges=0):
+        """The audit of ``find_duplicates`` without a synchronisation: device tensors (keys int64 [max_pairs]: a << 32 | b,
+        scores float32 [max_pairs], counts int32 [4]: candidates seen, pairs written, flags (1: more candidates than
+        ``max_pairs``, 2: a non-finite row), row ranges used).  The first counts[1] entries hold the pairs, in no order.
+        a and b are positions in ``self.ids``.  The f32 rows are read (a view's through its slot list) whatever ``scan``
+        the object was built with; the coarse copy is not."""
+        return _pairs_device(self.lib, self.device, self.row_source(), thr, inclusive, max_pairs, max_ranges)
+
+    def find_duplicates(self, thr=0.4, inclusive=False, max_pairs=1 << 20):
+        """Every pair of rows a < b the enrolment duplicate check would refuse: dot(row a, row b) > ``thr`` (``inclusive``:
+        >=) with the dot of ``first_above`` on the rows as stored, bit for bit - one pass over the pairs on the f16 matrix
+        cores as a filter, the exact dot for every candidate (DESIGN.md 4.6f).  Exact, not approximate, for finite rows
+        inside the f16 range; a row outside it raises ValueError.  More than ``max_pairs`` candidates raise
+        ``DuplicateOverflowError`` whose ``needed`` is the ``max_pairs`` to retry with.  Returns ``DuplicatePairs``."""
+        return _pairs_host(self.device, self.ids, *self.find_duplicates_device(thr, inclusive, max_pairs))
+
+
+class GalleryMatcher(_Rows):
     """``G[N,512]`` float32 unit rows on the device + the id table."""
 
     def __init__(self, device="cuda:0", f16_scan=False, scan=None):
@@ -119,8 +288,6 @@ class GalleryMatcher:
 
     def __len__(self):
         return self.G.shape[0]
-
-    last_topk = property(lambda self: last_topk())
 
     def set_rows(self, ids, rows, normalise=True):
         """rows: float32 [N,512] (host or device).  ``normalise`` applies v/||v|| on the
@@ -149,43 +316,18 @@ class GalleryMatcher:
                     self.G16 = torch.empty(rows.shape, dtype=torch.uint8, device=self.device)
                     self.lib.fr_f32_to_f8(_lib.ptr(rows), _lib.ptr(self.G16), rows.numel(), _lib.stream_ptr())
 
-    def _workspace(self, need):
-        """Scratch for ONE scan, taken from torch's caching allocator under the current stream: the block is
-        owned by that stream, so concurrent matches on different streams never share (or free) each other's
-        partial results.  (A per-object buffer did: two pipes driving one matcher overwrote ws_score/ws_idx.)"""
-        return torch.empty(max(int(need), 16), dtype=torch.uint8, device=self.device)
+    def row_source(self):
+        """The rows a scan of this matcher reads (``RowSource``)."""
+        N = self.G.shape[0]
+        return RowSource(self.G, None, N, N, self.G16, self.scan if self.G16 is not None else None, self.gmax)
 
     def match_device(self, Q, renormalise=True, row_offset=0, counts=None, seg_len=0):
         """Q: float32 [F,512] device tensor of ``normed_embedding`` rows.
         Returns device tensors (idx int64[F] (-1: empty gallery), score float32[F]).
         ``counts`` (device int32 [F / seg_len]) marks padding slots of a gathered batch (sharded match): slot f
         is real iff f % seg_len < counts[f // seg_len]; padding costs no scan work and reports (-1, -1)."""
-        Q = Q.to(self.device, torch.float32).contiguous().reshape(-1, DIM)
-        F = Q.shape[0]
-        idx = torch.empty(F, dtype=torch.int64, device=self.device)
-        score = torch.empty(F, dtype=torch.float32, device=self.device)
-        if F == 0:
-            return idx, score
-        with torch.cuda.device(self.device):
-            s = _lib.stream_ptr()
-            if renormalise:                      # infrenceServer.py:532
-                Qn = torch.empty_like(Q)
-                self.lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
-                Q = Qn
-            cp = _lib.ptr(counts) if counts is not None else None
-            if counts is not None:
-                assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
-            if self.G16 is not None:
-                wsz, fn = ((self.lib.fr_gallery_match_f16_workspace, self.lib.fr_gallery_match_f16) if self.scan == "f16"
-                           else (self.lib.fr_gallery_match_f8_workspace, self.lib.fr_gallery_match_f8))
-                ws = self._workspace(wsz(F, self.G.shape[0]))
-                fn(_lib.ptr(Q), _lib.ptr(self.G16), _lib.ptr(self.G), F, self.G.shape[0], DIM, row_offset,
-                   _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), cp, seg_len, s)
-                return idx, score
-            ws = self._workspace(self.lib.fr_gallery_match_workspace(F, self.G.shape[0]))
-            self.lib.fr_gallery_match_f32(_lib.ptr(Q), _lib.ptr(self.G), F, self.G.shape[0], DIM, row_offset,
-                                          _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), cp, seg_len, s)
-        return idx, score
+        src = self.row_source()
+        return _scan(self.lib, self.device, src, Q, None, renormalise, src.kind, row_offset, counts, seg_len)
 
     def match_topk_device(self, Q, k, renormalise=True, row_offset=0, counts=None, seg_len=0):
         """The ``k`` best rows per query (1 <= k <= 16): device tensors (idx int64[F,k], score float32[F,k]), ranked by
@@ -197,124 +339,9 @@ class GalleryMatcher:
         galleries run the exact scan.  ``last_topk`` tells which.  ``row_offset`` / ``counts`` / ``seg_len``: as
         ``match_device``."""
         k = _check_k(k)
-        coarse = None
-        if self.scan == "f16" and self.G16 is not None and self.G.shape[0] >= self.coarse_topk_min_rows:
-            coarse = (self.G16, self.gmax, 0)
-        return _topk_device(self, Q, k, renormalise, None, self.G, self.G.shape[0], row_offset, counts, seg_len, coarse)
-
-    def match_topk(self, Q, k, min_score=None):
-        """Host-facing: (ids, scores float32[F,k], idx int64[F,k]); ``ids[f]`` is a list of k entries in rank order,
-        None for empty slots and for slots whose score is below ``min_score``."""
-        k = _check_k(k)
-        Q = torch.as_tensor(np.asarray(Q, np.float32)) if not torch.is_tensor(Q) else Q
-        idx, score = self.match_topk_device(Q, k)
-        # two results, ONE synchronisation: asynchronous copies into pinned host memory, then a stream sync
-        idx_h = torch.empty(idx.shape, dtype=torch.int64).pin_memory()
-        score_h = torch.empty(score.shape, dtype=torch.float32).pin_memory()
-        with torch.cuda.device(self.device):
-            idx_h.copy_(idx, non_blocking=True)
-            score_h.copy_(score, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-        idx_h, score_h = idx_h.numpy().copy(), score_h.numpy().copy()
-        ids = [[self.ids[i] if i >= 0 and (min_score is None or s >= min_score) else None for i, s in zip(ri, rs)]
-               for ri, rs in zip(idx_h, score_h)]
-        return ids, score_h, idx_h
-
-    def find_duplicates_device(self, thr=0.4, inclusive=False, max_pairs=1 << 20, max_ranges=0):
-        """The audit of ``find_duplicates`` without a synchronisation: device tensors (keys int64 [max_pairs]: a << 32 | b,
-        scores float32 [max_pairs], counts int32 [4]: candidates seen, pairs written, flags (1: more candidates than
-        ``max_pairs``, 2: a non-finite row), row ranges used).  The first counts[1] entries hold the pairs, in no order."""
-        return _pairs_device(self, self.G, None, self.G.shape[0], thr, inclusive, max_pairs, max_ranges)
-
-    def find_duplicates(self, thr=0.4, inclusive=False, max_pairs=1 << 20):
-        """Every pair of rows a < b the enrolment duplicate check would refuse: dot(row a, row b) > ``thr`` (``inclusive``:
-        >=) with the dot of ``first_above`` on the rows as stored, bit for bit - one pass over the pairs on the f16 matrix
-        cores as a filter, the exact dot for every candidate (DESIGN.md 4.6f).  Exact, not approximate, for finite rows
-        inside the f16 range; a row outside it raises ValueError.  More than ``max_pairs`` candidates raise
-        ``DuplicateOverflowError`` whose ``needed`` is the ``max_pairs`` to retry with.  Returns ``DuplicatePairs``."""
-        return _pairs_host(self, self.ids, *self.find_duplicates_device(thr, inclusive, max_pairs))
-
-    def decide_device(self, idx, score, thr, unknown_thr=None):
-        """1 recognised / 0 unknown / 2 dropped (peopleCount.py:876-887 band)."""
-        d = torch.empty(idx.shape[0], dtype=torch.int32, device=self.device)
-        if idx.shape[0]:
-            with torch.cuda.device(self.device):
-                self.lib.fr_match_decide(_lib.ptr(idx), _lib.ptr(score), idx.shape[0], float(thr),
-                                         float(thr if unknown_thr is None else unknown_thr), _lib.ptr(d),
-                                         _lib.stream_ptr())
-        return d
-
-    def match(self, Q, thr=0.4, unknown_thr=None):
-        """Host-facing: returns (ids list (None = unknown), scores float32[F], idx int64[F])."""
-        Q = torch.as_tensor(np.asarray(Q, np.float32)) if not torch.is_tensor(Q) else Q
-        idx, score = self.match_device(Q)
-        dec = self.decide_device(idx, score, thr, unknown_thr)
-        # three results, ONE synchronisation: asynchronous copies into pinned host memory, then a stream sync
-        F = idx.shape[0]
-        pin = _PIN.__dict__.setdefault("bufs", {})          # per thread: match() may be called by several on one matcher
-        h = pin.get(F)
-        if h is None:
-            if len(pin) >= 16:
-                pin.clear()
-            h = pin[F] = (torch.empty(F, dtype=torch.int64).pin_memory(), torch.empty(F, dtype=torch.float32).pin_memory(),
-                          torch.empty(F, dtype=torch.int32).pin_memory())
-        with torch.cuda.device(self.device):
-            for dst, src in zip(h, (idx, score, dec)):
-                dst.copy_(src, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-        idx_h, score_h, dec_h = h[0].numpy().copy(), h[1].numpy().copy(), h[2].numpy().copy()
-        ids = [self.ids[i] if (d == 1 and i >= 0) else None for i, d in zip(idx_h, dec_h)]
-        return ids, score_h, idx_h
-
-
-def _check_k(k):
-    if not 1 <= int(k) <= TOPK_MAX:
-        raise ValueError(f"k must be 1..{TOPK_MAX} (got {k})")
-    return int(k)
-
-
-def _topk_device(owner, Q, k, renormalise, view, G, N, row_offset=0, counts=None, seg_len=0, coarse=None):
-    """fr_gallery_topk_f32 (``view`` None) / fr_gallery_topk_view_f32 on the current stream of ``owner.device``;
-    ``coarse`` = (f16 rows, gmax, capacity): fr_gallery_topk_f16 / _view_f16 instead.  Records ``last_topk()``."""
-    lib, dev = owner.lib, owner.device
-    Q = Q.to(dev, torch.float32).contiguous().reshape(-1, DIM)
-    F = Q.shape[0]
-    idx = torch.empty((F, k), dtype=torch.int64, device=dev)
-    score = torch.empty((F, k), dtype=torch.float32, device=dev)
-    _TLS.topk = {"path": "exact" if coarse is None else "coarse", "flags": None}
-    if F == 0:
-        return idx, score
-    with torch.cuda.device(dev):
-        s = _lib.stream_ptr()
-        if renormalise:
-            Qn = torch.empty_like(Q)
-            lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
-            Q = Qn
-        cp = _lib.ptr(counts) if counts is not None else None
-        if counts is not None:
-            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
-        if coarse is not None:
-            G16, gmax, capacity = coarse
-            flags = _TLS.topk["flags"] = torch.empty(F, dtype=torch.int32, device=dev)
-            if view is not None:
-                ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_view_f16_workspace(F, N, k))
-                lib.fr_gallery_topk_view_f16(_lib.ptr(Q), _lib.ptr(G16), _lib.ptr(G), _lib.ptr(view), F, N, capacity, DIM, k,
-                                             _lib.ptr(gmax), _lib.ptr(idx), _lib.ptr(score), _lib.ptr(flags), _lib.ptr(ws),
-                                             ws.numel(), s)
-            else:
-                ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_f16_workspace(F, N, k))
-                lib.fr_gallery_topk_f16(_lib.ptr(Q), _lib.ptr(G16), _lib.ptr(G), F, N, DIM, k, row_offset, _lib.ptr(gmax),
-                                        _lib.ptr(idx), _lib.ptr(score), _lib.ptr(flags), _lib.ptr(ws), ws.numel(), cp,
-                                        seg_len, s)
-            return idx, score
-        ws = GalleryMatcher._workspace(owner, lib.fr_gallery_topk_workspace(F, N, k))
-        if view is not None:
-            lib.fr_gallery_topk_view_f32(_lib.ptr(Q), _lib.ptr(G), _lib.ptr(view), F, N, DIM, k, _lib.ptr(idx),
-                                         _lib.ptr(score), _lib.ptr(ws), ws.numel(), s)
-            return idx, score
-        lib.fr_gallery_topk_f32(_lib.ptr(Q), _lib.ptr(G), F, N, DIM, k, row_offset, _lib.ptr(idx), _lib.ptr(score),
-                                _lib.ptr(ws), ws.numel(), cp, seg_len, s)
-    return idx, score
+        src = self.row_source()
+        kind = _topk_kind(src, self.coarse_topk_min_rows)
+        return _scan(self.lib, self.device, src, Q, k, renormalise, kind, row_offset, counts, seg_len)
 
 
 class DeviceGallery:
@@ -438,7 +465,13 @@ class DeviceGallery:
         return GalleryViewSet(views, gallery=self)
 
 
-class GalleryView:
+def _check_current(obj, what="view"):
+    """``obj``: a GalleryView or a GalleryViewSet (``what``: "set"), which is good for one generation of its gallery."""
+    if obj.generation != obj.gallery.generation:
+        raise StaleViewError(f"{type(obj).__name__} is stale: the gallery's membership changed after the {what} was made")
+
+
+class GalleryView(_Rows):
     """Ordered subset of a ``DeviceGallery``: the rows one company's frames are matched against."""
 
     def __init__(self, gallery, ids):
@@ -454,37 +487,17 @@ class GalleryView:
         """The view's rows as a [N,512] device tensor (a copy; for tests / export)."""
         return self.gallery.G[self.slots]
 
+    def row_source(self):
+        """The rows a scan of this view reads (``RowSource``); a view whose gallery has moved on raises StaleViewError."""
+        _check_current(self)
+        g = self.gallery
+        return RowSource(g.G, self.slots, len(self.ids), g.capacity, g.S, g.scan if g.S is not None else None, g.gmax)
+
     def match_device(self, Q, renormalise=True):
         """As ``GalleryMatcher.match_device``; idx is the position in ``self.ids`` (-1: empty view).  On a gallery built
         with scan="f16" / "f8": the coarse scan of the shadow slab through the slot list, re-ranked exactly in f32."""
-        if self.generation != self.gallery.generation:
-            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
-        Q = Q.to(self.device, torch.float32).contiguous().reshape(-1, DIM)
-        F = Q.shape[0]
-        idx = torch.empty(F, dtype=torch.int64, device=self.device)
-        score = torch.empty(F, dtype=torch.float32, device=self.device)
-        if F == 0:
-            return idx, score
-        with torch.cuda.device(self.device):
-            s = _lib.stream_ptr()
-            if renormalise:
-                Qn = torch.empty_like(Q)
-                self.lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, s)
-                Q = Qn
-            g = self.gallery
-            if g.S is not None:
-                wsz, fn = ((self.lib.fr_gallery_match_view_f16_workspace, self.lib.fr_gallery_match_view_f16)
-                           if g.scan == "f16" else
-                           (self.lib.fr_gallery_match_view_f8_workspace, self.lib.fr_gallery_match_view_f8))
-                ws = GalleryMatcher._workspace(self, wsz(F, len(self.ids)))
-                fn(_lib.ptr(Q), _lib.ptr(g.S), _lib.ptr(g.G), _lib.ptr(self.slots), F, len(self.ids), g.capacity, DIM,
-                   _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), s)
-                return idx, score
-            ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_match_workspace(F, len(self.ids)))
-            self.lib.fr_gallery_match_view_f32(_lib.ptr(Q), _lib.ptr(self.gallery.G), _lib.ptr(self.slots), F,
-                                               len(self.ids), DIM, _lib.ptr(idx), _lib.ptr(score),
-                                               _lib.ptr(ws), ws.numel(), s)
-        return idx, score
+        src = self.row_source()
+        return _scan(self.lib, self.device, src, Q, None, renormalise, src.kind)
 
     def match_topk_device(self, Q, k, renormalise=True):
         """As ``GalleryMatcher.match_topk_device``; idx are positions in ``self.ids``.  The bits of the exact f32 scan
@@ -492,33 +505,15 @@ class GalleryView:
         ``gallery.coarse_topk_min_rows`` rows of a scan="f16" gallery gets them from the certified coarse pass through
         the slot list, every other view from the exact scan (``last_topk`` tells which)."""
         k = _check_k(k)
-        if self.generation != self.gallery.generation:
-            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
-        g, coarse = self.gallery, None
-        if g.scan == "f16" and len(self.ids) >= g.coarse_topk_min_rows:
-            coarse = (g.S, g.gmax, g.capacity)
-        return _topk_device(self, Q, k, renormalise, self.slots, g.G, len(self.ids), coarse=coarse)
-
-    last_topk = property(lambda self: last_topk())
-
-    def find_duplicates_device(self, thr=0.4, inclusive=False, max_pairs=1 << 20, max_ranges=0):
-        """As ``GalleryMatcher.find_duplicates_device``; a and b are positions in ``self.ids``.  The f32 rows are read
-        through the slot list whatever ``scan`` the gallery was built with; the coarse slab is not."""
-        if self.generation != self.gallery.generation:
-            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
-        return _pairs_device(self, self.gallery.G, self.slots, len(self.ids), thr, inclusive, max_pairs, max_ranges)
-
-    find_duplicates = GalleryMatcher.find_duplicates
-    decide_device = GalleryMatcher.decide_device
-    match = GalleryMatcher.match
-    match_topk = GalleryMatcher.match_topk
+        src = self.row_source()
+        return _scan(self.lib, self.device, src, Q, k, renormalise, _topk_kind(src, self.gallery.coarse_topk_min_rows))
 
 
 GROUP = 32                     # queries per scan group (csrc/match_scan.h QG)
 
 
 def build_group_tables(view_of, F, seg_len, offsets, lengths):
-    """The host side of the grouped scan's tables (include/frhip.h fr_gallery_match_grouped_f32), a pure function.
+    """The host side of the grouped scan's tables (include/frhip.h, the grouped entries), a pure function.
 
     ``view_of``: the view index of every query slot (``seg_len`` == 0: F entries) or of every segment of ``seg_len``
     slots (F / seg_len entries); None or -1: no view - such slots are grouped under an empty view and report
@@ -549,10 +544,10 @@ def build_group_tables(view_of, F, seg_len, offsets, lengths):
     return gtab, qmap, longest
 
 
-class GalleryViewSet:
+class GalleryViewSet(_Decides):
     """Several views of ONE ``DeviceGallery`` generation, matched together: each query of a batch through its own view,
-    in one grouped scan (fr_gallery_match_grouped_f32 / fr_gallery_topk_grouped_f32) - the frames of a camera batch
-    that belong to different companies.  The concatenated slot lists are uploaded once, here.
+    in one grouped scan - the frames of a camera batch that belong to different companies.  The concatenated slot
+    lists are uploaded once, here.
 
     The grouped scan is the EXACT f32 scan over the f32 slab, also on a gallery built with scan="f16" / "f8" (there is
     no grouped coarse scan): the ids are those the coarse view scan promises - the f32 scan's - and the scores are
@@ -568,8 +563,8 @@ class GalleryViewSet:
             gallery = views[0].gallery
         if any(v.gallery is not gallery for v in views):
             raise ValueError("the views of a GalleryViewSet must belong to one gallery")
-        if any(v.generation != gallery.generation for v in views):
-            raise StaleViewError("GalleryView is stale: the gallery's membership changed after the view was made")
+        for v in views:
+            _check_current(v)
         self.gallery, self.views, self.generation = gallery, views, gallery.generation
         self.lib, self.device = gallery.lib, gallery.device
         self.lengths = [len(v) for v in views]
@@ -598,20 +593,23 @@ class GalleryViewSet:
                                            gtab.shape[0], longest)
         return hit
 
-    def _prepare(self, Q, view_of, renormalise, counts, seg_len):
-        if self.generation != self.gallery.generation:
-            raise StaleViewError("GalleryViewSet is stale: the gallery's membership changed after the set was made")
-        Q = Q.to(self.device, torch.float32).contiguous().reshape(-1, DIM)
-        F = Q.shape[0]
-        if counts is not None:
-            assert counts.dtype == torch.int32 and counts.is_contiguous() and seg_len > 0 and F == counts.numel() * seg_len
-        tabs = self.tables(view_of, F, seg_len)
-        if renormalise and F:
-            Qn = torch.empty_like(Q)
-            with torch.cuda.device(self.device):
-                self.lib.fr_l2norm_rows_f32(_lib.ptr(Q), _lib.ptr(Qn), F, DIM, _lib.stream_ptr())
-            Q = Qn
-        return Q, F, tabs
+    def _scan(self, Q, view_of, k, renormalise, counts, seg_len):
+        """The grouped pair called directly, not through ``_ENTRIES``: the tables are arguments no other scan has."""
+        _check_current(self, "set")
+        gtab, qmap, ngroups, longest = self.tables(view_of, Q.numel() // DIM, seg_len)
+        lib, G, kk = self.lib, self.gallery.G, () if k is None else (k,)
+        with torch.cuda.device(self.device):
+            Q, F = _queries(lib, self.device, Q, renormalise, counts, seg_len)
+            idx, score = _outputs(self.device, F, k)
+            if F == 0:
+                return idx, score
+            wsz, entry = ((lib.fr_gallery_match_grouped_workspace, lib.fr_gallery_match_grouped_f32) if k is None else
+                          (lib.fr_gallery_topk_grouped_workspace, lib.fr_gallery_topk_grouped_f32))
+            ws = _workspace(self.device, wsz(ngroups, longest, *kk))
+            entry(_lib.ptr(Q), _lib.ptr(G), _lib.ptr(self.slots), _lib.ptr(gtab), _lib.ptr(qmap), F, ngroups, longest,
+                  G.shape[0], DIM, *kk, _lib.ptr(idx), _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.ptr(counts), seg_len,
+                  _lib.stream_ptr())
+        return idx, score
 
     def match_device(self, Q, view_of, renormalise=True, counts=None, seg_len=0):
         """Q: float32 [F,512] device tensor; ``view_of``: a host sequence naming the view (index into ``self.views``;
@@ -622,42 +620,10 @@ class GalleryViewSet:
         ``GalleryMatcher.match_device``.  One fr_l2norm_rows_f32 launch (``renormalise``) plus the grouped entry, and
         nothing is read back from ``counts``; no host synchronisation once the tables of this ``view_of`` are cached
         (``tables``: the first call with a new assignment uploads them).  Always the exact f32 scan (see the class)."""
-        Q, F, (gtab, qmap, ngroups, longest) = self._prepare(Q, view_of, renormalise, counts, seg_len)
-        idx = torch.empty(F, dtype=torch.int64, device=self.device)
-        score = torch.empty(F, dtype=torch.float32, device=self.device)
-        if F == 0:
-            return idx, score
-        g = self.gallery
-        with torch.cuda.device(self.device):
-            ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_match_grouped_workspace(ngroups, longest))
-            self.lib.fr_gallery_match_grouped_f32(_lib.ptr(Q), _lib.ptr(g.G), _lib.ptr(self.slots), _lib.ptr(gtab),
-                                                  _lib.ptr(qmap), F, ngroups, longest, g.capacity, DIM, _lib.ptr(idx),
-                                                  _lib.ptr(score), _lib.ptr(ws), ws.numel(),
-                                                  _lib.ptr(counts) if counts is not None else None, seg_len,
-                                                  _lib.stream_ptr())
-        return idx, score
+        return self._scan(Q, view_of, None, renormalise, counts, seg_len)
 
     def match_topk_device(self, Q, view_of, k, renormalise=True, counts=None, seg_len=0):
         """The ``k`` best rows of every query in ITS view: (idx int64[F,k], score float32[F,k]), per query what
         ``views[v].match_topk_device`` returns, bit for bit; column 0 is ``match_device``.  Arguments as
         ``match_device``.  Always the exact f32 scan: ``last_topk()`` reports "exact"."""
-        k = _check_k(k)
-        Q, F, (gtab, qmap, ngroups, longest) = self._prepare(Q, view_of, renormalise, counts, seg_len)
-        idx = torch.empty((F, k), dtype=torch.int64, device=self.device)
-        score = torch.empty((F, k), dtype=torch.float32, device=self.device)
-        _TLS.topk = {"path": "exact", "flags": None}
-        if F == 0:
-            return idx, score
-        g = self.gallery
-        with torch.cuda.device(self.device):
-            ws = GalleryMatcher._workspace(self, self.lib.fr_gallery_topk_grouped_workspace(ngroups, longest, k))
-            self.lib.fr_gallery_topk_grouped_f32(_lib.ptr(Q), _lib.ptr(g.G), _lib.ptr(self.slots), _lib.ptr(gtab),
-                                                 _lib.ptr(qmap), F, ngroups, longest, g.capacity, DIM, k, _lib.ptr(idx),
-                                                 _lib.ptr(score), _lib.ptr(ws), ws.numel(),
-                                                 _lib.ptr(counts) if counts is not None else None, seg_len,
-                                                 _lib.stream_ptr())
-        return idx, score
-
-    last_topk = property(lambda self: last_topk())
-
-    decide_device = GalleryMatcher.decide_device
+        return self._scan(Q, view_of, _check_k(k), renormalise, counts, seg_len)

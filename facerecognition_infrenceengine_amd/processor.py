@@ -375,13 +375,8 @@ class EmbeddingManager:
         (trainingServer.py:170-200); a company's view is employees then visitors, so the pair it never checks is found
         here.  One lock and one flush; the company's cached view.  Returns [{"a", "b", "score", "a_type", "b_type", "a_name",
         "b_name"}], ordered by the rows' positions in the view."""
-        from .gallery import StaleViewError
-        view, metadata = self.get_matcher_for_company(company_id)
-        try:
-            found = view.find_duplicates(thr=thr)
-        except StaleViewError:                  # a sync on another thread moved the slab on: the current view, once
-            view, metadata = self.get_matcher_for_company(company_id)
-            found = view.find_duplicates(thr=thr)
+        (view, metadata), found = _with_current(lambda: self.get_matcher_for_company(company_id),
+                                                lambda view, metadata: view.find_duplicates(thr=thr))
         return [{"a": a, "b": b, "score": float(s), "a_type": metadata[a]["type"], "b_type": metadata[b]["type"],
                  "a_name": metadata[a]["name"], "b_name": metadata[b]["name"]}
                 for (a, b), s in zip(found.ids, found.scores)]
@@ -471,7 +466,6 @@ class FaceRecognitionProcessor:
         beyond the engine's own.  With a ``gate``, ``keep`` lists the active frames and everything else describes exactly those
         n = len(keep) frames, in order (``keep`` None: all frames, the ungated call's tensors); with none active the slot
         results are None, and galleries / idx / score are None when no active frame's company has a gallery."""
-        from .gallery import StaleViewError
         company_ids = list(company_ids)
         if len(company_ids) != len(frames):
             raise ValueError(f"one company id per frame: {len(frames)} frames, {len(company_ids)} ids")
@@ -493,15 +487,12 @@ class FaceRecognitionProcessor:
                 return _Scan(n, r, keep, view_set, None, None, None)
         cap = r["bbox"].shape[1]
 
-        def scan(vs, of):
+        def scan(vs, _, of):
             if k is None:
                 return vs.match_device(_scan_rows(r), of, counts=r["counts"], seg_len=cap)
             return vs.match_topk_device(_scan_rows(r), of, k, counts=r["counts"], seg_len=cap)
-        try:
-            idx, score = scan(view_set, index_of)
-        except StaleViewError:                    # a sync moved the slab on meanwhile: the current views, once
-            view_set, metadatas, index_of = mgr.get_matchers_for_companies(company_ids)
-            idx, score = scan(view_set, index_of)
+        (view_set, metadatas, index_of), (idx, score) = _with_current(
+            lambda: mgr.get_matchers_for_companies(company_ids), scan, (view_set, metadatas, index_of))
         galleries = [None if v is None else (view_set.views[v].ids, metadatas[v]) for v in index_of]
         return _Scan(n, r, keep, view_set, galleries, idx, score)
 
@@ -1051,19 +1042,25 @@ def _ring_turn(owner, det, frames, pixel_format, matrix):
     return arr, ring, turn
 
 
-def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):
-    """Scan through the company's view; a sync on another thread may have changed the slab's membership since the
-    view was fetched (its generation moved on): fetch the current view once and retry instead of dropping the frame.
-    ``k``: the top-k form (idx / score [F,k]) instead of the single best row."""
+def _with_current(fetch, run, got=None):
+    """``run(*got)`` with ``got`` = what ``fetch()`` returns, a view or view set first (``got`` given: fetched already).  A
+    sync on another thread may have changed the slab's membership since (the generation moved on): on StaleViewError
+    fetch once more and run again instead of dropping the frame.  Returns (what was fetched, what ``run`` returned)."""
     from .gallery import StaleViewError
-
-    def scan(m):
-        return m.match_device(Q) if k is None else m.match_topk_device(Q, k)
+    got = fetch() if got is None else got
     try:
-        idx, score = scan(matcher)
+        return got, run(*got)
     except StaleViewError:
-        matcher, metadata = manager.get_matcher_for_company(company_id)
-        idx, score = scan(matcher)
+        got = fetch()
+        return got, run(*got)
+
+
+def _match_fresh(manager, company_id, matcher, metadata, Q, k=None):
+    """Scan through the company's view, the current one if this one is stale (``_with_current``).  ``k``: the top-k form
+    (idx / score [F,k]) instead of the single best row."""
+    (matcher, metadata), (idx, score) = _with_current(
+        lambda: manager.get_matcher_for_company(company_id),
+        lambda m, _: m.match_device(Q) if k is None else m.match_topk_device(Q, k), (matcher, metadata))
     return matcher, metadata, idx, score
 
 
