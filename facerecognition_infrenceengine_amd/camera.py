@@ -26,7 +26,7 @@ logger = logging.getLogger(__name__)
 
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
-                 dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601"):
+                 dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601", encode=None):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
         ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
         frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
@@ -40,6 +40,9 @@ class CameraManager:
         ``hud``: a ``hud.Hud``; the processed frames are then drawn on the DEVICE (``recognize_faces_batch``: the full HUD, on the
         frames or on ``hud.out_size`` previews) and what is queued are the frames that call returns.  None: the plain box drawn
         on the host frame by ``annotate``, as ever.
+        ``encode``: a ``jpeg.JpegEncoder``, with a ``hud`` (ValueError without one: the encoder works on the device frames the
+        HUD draws on); the drawn frames are then encoded on the DEVICE and what is queued and kept per source is the JPEG
+        ``bytes`` (``latest_jpeg(source)``; None for a frame the encoder turned away).  None: arrays, as ever.
         ``pixel_format`` / ``matrix``: what the captures deliver - ``"nv12"`` / ``"i420"`` frames (``uint8 [H*3/2, W]``) need a
         ``hud``, since the host never holds a BGR picture of them to draw on (ValueError without one).
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
@@ -69,6 +72,11 @@ class CameraManager:
         if pixel_format != "bgr" and hud is None:
             raise ValueError(f"pixel_format={pixel_format!r} needs a hud: the host holds no BGR frame to annotate")
         self.hud, self.pixel_format, self.matrix = hud, pixel_format, matrix
+        if encode is not None and hud is None:
+            raise ValueError("encode needs a hud: the encoder works on the device frames the HUD draws on")
+        self.encode = encode
+        self._jpeg = {}                        # source -> (count of its frames so far, the latest JPEG bytes) (encode only)
+        self._jpeg_new = threading.Condition(self._latest_lock)
 
     def _forget(self, source):
         """A source that is gone: its gate slot and its track slot are freed and its held results dropped."""
@@ -178,7 +186,8 @@ class CameraManager:
         ``stats["gated_frames"]`` counts the frame.  With a ``hud`` the processor call is ``recognize_faces_batch(..., hud,
         return_results=True, held=self._held)`` with the same arguments (and the manager's pixel format when it is YUV): the frames
         it returns - drawn on the device, an unchanged frame with its held results - are what is queued, and ``annotate`` is not
-        called."""
+        called.  With ``encode`` too the call also gets ``encode=``, and what it returns and what is queued is one JPEG ``bytes``
+        per frame, kept per source for ``latest_jpeg``."""
         mixed_ids = isinstance(company_id, (list, tuple))
         if mixed_ids and len(company_id) != len(batch):
             raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
@@ -200,6 +209,8 @@ class CameraManager:
             else:                                     # the same call, then the HUD drawn on the device frames
                 if self.pixel_format != "bgr":
                     gated = dict(gated, pixel_format=self.pixel_format, matrix=self.matrix)
+                if self.encode is not None:
+                    gated = dict(gated, encode=self.encode)
                 drawn, res = self.processor.recognize_faces_batch([batch[k][1] for k in ks], ids[0] if one else ids, self.hud,
                                                                   return_results=True, held=self._held, **gated)
             for j, k in enumerate(ks):
@@ -220,6 +231,10 @@ class CameraManager:
         for (source, frame), res, picture in zip(batch, results, pictures):
             if self.hud is not None:
                 out = picture
+                if self.encode is not None and out is not None:
+                    with self._jpeg_new:
+                        self._jpeg[source] = (self._jpeg.get(source, (0, None))[0] + 1, out)
+                        self._jpeg_new.notify_all()
             else:
                 out = frame if res is None else self.processor.annotate(frame, res)
             try:
@@ -287,6 +302,23 @@ class CameraManager:
         """Last processed frame of ``source`` kept by the default consumer (None before the first result)."""
         with self._latest_lock:
             return self.latest.get(source)
+
+    def latest_jpeg(self, source, after=0, timeout=None):
+        """The JPEG ``bytes`` of the last processed frame of ``source`` (None before the first one, and always without an
+        encoder).  ``after`` / ``timeout``: as ``(count, bytes)``, waiting up to ``timeout`` seconds for a frame whose count -
+        the number of frames the source has produced - is above ``after``; ``(after, None)`` when none came."""
+        with self._jpeg_new:
+            if timeout is None:
+                return self._jpeg.get(source, (0, None))[1]
+            self._jpeg_new.wait_for(lambda: self._jpeg.get(source, (0, None))[0] > after, timeout)
+            count, data = self._jpeg.get(source, (0, None))
+            return (count, data) if count > after else (after, None)
+
+    def source_named(self, text):
+        """the source whose ``str()`` is ``text`` - how a route names one (sources are ints or strings) -, or None"""
+        with self._latest_lock:
+            known = list(self.company_of) + list(self._jpeg) + list(self.latest)
+        return next((s for s in known if str(s) == str(text)), None)
 
     def stop_cameras(self):
         """Stops every camera of every company."""

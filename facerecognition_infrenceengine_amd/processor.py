@@ -599,7 +599,7 @@ class FaceRecognitionProcessor:
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
         return _SlotFaces(r, n, idx, score, tracks, dec).frames([(matcher.ids, metadata)] * n, keep, len(frames))
 
-    def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, **kw):
+    def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, encode=None, **kw):
         """The reference's ``recognize_faces`` for a batch, with the HUD drawn on the DEVICE (``hud``: a ``hud.Hud``): runs
         exactly what ``recognize_batch(frames, company_id, **kw)`` runs (``kw``: ``pixel_format``, ``matrix``, ``gate``,
         ``camera_ids``, ``tracks``, ``quality``), then draws every frame's results into the ring's device frames - the BGR frames
@@ -612,7 +612,12 @@ class FaceRecognitionProcessor:
         A frame without results (no gallery, no face) comes back undrawn.  A frame answered ``UNCHANGED`` is drawn with
         ``held[camera_id]`` when ``held`` (a dict: camera id -> the results of its last processed frame) is given, else undrawn.
         Calls with a HUD are serialised per processor; while one holds its turn, no more than one further batch of the same
-        shape should be started on this processor from other threads (the ring is two slots deep)."""
+        shape should be started on this processor from other threads (the ring is two slots deep).
+
+        ``encode`` (a ``jpeg.JpegEncoder``): the drawn frames - full size, previews, or a det_size engine's arena - are encoded on
+        the device while the turn is still held, and what crosses the link is the offsets and then the JPEG stream.  The call
+        then returns one ``bytes`` per frame in place of the array (None, with a logged warning, for a frame whose coded rows
+        overflowed the encoder's budget).  None: the arrays, as ever."""
         import torch
         if hud is None:
             raise ValueError("recognize_faces_batch draws with a hud.Hud; without one call recognize_batch")
@@ -636,6 +641,12 @@ class FaceRecognitionProcessor:
                     stream = torch.cuda.current_stream(det.device)
                     stream.wait_event(turn.ready)
                     drawn = hud.draw(turn.dev if turn.table is None else (turn.dev, turn.table), per_frame, shapes=shapes)
+                    if encode is not None:
+                        coded = encode.encode_device(drawn if drawn.dim() == 4 else (drawn, turn.table), shapes=shapes)
+                        turn.ring.release(turn.turn)          # behind the queued encoder: it is the last reader of the slot
+                        hold.clear()
+                        out = encode.read_back(*coded)
+                        return (out, results) if return_results else out
                     stage = self._hud_stage(tuple(drawn.shape))
                     stage.copy_(drawn, non_blocking=True)
                     turn.ring.release(turn.turn)              # behind the queued copy: the next upload into the slot waits

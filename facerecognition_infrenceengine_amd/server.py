@@ -1,11 +1,13 @@
 """The four HTTP routes of /root/reference/infrenceServer.py:685-724, byte-compatible JSON and
 status codes, as an app factory with the managers injected (the reference builds module-level
-singletons that connect to a database at import: :682-683)."""
+singletons that connect to a database at import: :682-683) - and two routes the reference has no
+counterpart for (it shows its frames with cv2.imshow, :648-667): the latest processed frame of a
+camera as a JPEG, and the frames as they come as MJPEG, for a manager with a ``jpeg.JpegEncoder``."""
 from threading import Thread
 
 
 def create_app(embedding_manager, camera_manager):
-    from flask import Flask, jsonify, request
+    from flask import Flask, Response, jsonify, request
     app = Flask(__name__)
 
     @app.after_request
@@ -46,5 +48,40 @@ def create_app(embedding_manager, camera_manager):
             return jsonify({"status": "success", "message": "Camera stopped"})
         except Exception as e:
             return jsonify({"status": "error", "message": str(e)}), 500
+
+    def _jpeg_source():
+        """(source, None), or (None, the 404 answer): the manager must encode and know the source the query names"""
+        if getattr(camera_manager, "encode", None) is None:
+            return None, (jsonify({"status": "error", "message": "The camera manager has no JPEG encoder"}), 404)
+        source = camera_manager.source_named(request.args.get("source", "0"))
+        if source is None:
+            return None, (jsonify({"status": "error", "message": "No frame from this source"}), 404)
+        return source, None
+
+    @app.route("/api/camera/snapshot", methods=["GET"])
+    def camera_snapshot():
+        source, refusal = _jpeg_source()
+        data = None if source is None else camera_manager.latest_jpeg(source)
+        if data is None:
+            return refusal or (jsonify({"status": "error", "message": "No frame from this source"}), 404)
+        return Response(data, mimetype="image/jpeg", headers={"Cache-Control": "no-store"})
+
+    @app.route("/api/camera/stream", methods=["GET"])
+    def camera_stream():
+        source, refusal = _jpeg_source()
+        if source is None:
+            return refusal
+
+        def parts():                              # one part per new frame; ends when the cameras have stopped
+            count = 0
+            while True:
+                count, data = camera_manager.latest_jpeg(source, after=count, timeout=1.0)
+                if data is None:
+                    if not getattr(camera_manager, "running", False):
+                        return
+                    continue
+                yield (b"--frame\r\nContent-Type: image/jpeg\r\nContent-Length: " + str(len(data)).encode() + b"\r\n\r\n"
+                       + data + b"\r\n")
+        return Response(parts(), mimetype="multipart/x-mixed-replace; boundary=frame", headers={"Cache-Control": "no-store"})
 
     return app

@@ -50,6 +50,7 @@ typedef void* fr_stream_t;
  * and for fr_track_resolve_quality_i32 (judging face tracks: embed, carry or reject per face, only fit rows enter the bank),
  * and for fr_track_fuse_f32 (track templates: a track's last K shots fused into one scan query),
  * and for fr_hud_draw_u8 / fr_hud_draw_refs_u8 (the device HUD: recognition results drawn into the frames),
+ * and for fr_jpeg_workspace / fr_jpeg_encode_u8 / fr_jpeg_encode_refs_u8 (the device JPEG encoder behind the HUD draw),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -878,6 +879,53 @@ int fr_hud_draw_u8(uint8_t* frames, int N, int H, int W, const int32_t* counts, 
                    const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
 int fr_hud_draw_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* counts, int cap, const int32_t* faces,
                         const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
+
+/* Device JPEG encoder: BGR u8 frames on the device (the drawn frames of the HUD) -> baseline JPEG files, so that a few hundred
+ * KB per 1080p frame cross the link instead of 6.2 MB (the reference shows raw frames with cv2.imshow, one process per camera:
+ * infrenceServer.py:648-667).  The bytes are DEFINED by tests/helpers/jpeg_ref.py and reproduced byte for byte (32-bit integer
+ * arithmetic only): JFIF full-range YCbCr in libjpeg's 16-bit fixed point, the last column and row replicated
+ * to multiples of 16, 4:2:0 chroma (a + b + c + d + 2) >> 2, MCUs of 16 x 16 (Y00 Y01 Y10 Y11 Cb Cr), libjpeg's integer
+ * "islow" forward DCT of samples - 128, sign(c) ((|c| + (qv >> 1)) / qv) with qv = t << 3, the Huffman coding of T.81 F.1.2 with
+ * the Annex K tables, ONE restart interval per MCU row (DRI = ceil(W / 16), DC predictions 0 at the start of a row, the last
+ * byte of a row padded with 1-bits, 0x00 stuffed behind every 0xFF, RSTm with m = row mod 8 behind every row but the last).
+ *
+ * header: DEVICE bytes SOI .. SOS, FR_JPEG_HEADER_BYTES of them, built by the host once per quality (jpeg.py: APP0 JFIF 1.01,
+ *   DQT 0 / 1, SOF0, four DHT, DRI, SOS); the H / W fields of SOF0 (FR_JPEG_AT_H, FR_JPEG_AT_W) and the interval of DRI
+ *   (FR_JPEG_AT_DRI) are patched per frame here, so a ragged batch needs one header.
+ * codes: DEVICE u32 [2][FR_JPEG_CODE_ROW], row 0 luma, row 1 chroma: entry s < 256 the AC code of symbol s (run << 4 | size),
+ *   entry 256 + c the DC code of category c, each code << 8 | length (jpeg_tables.code_table; the library holds no copy).
+ * qtables: DEVICE i32 [3][64]: the luma and the chroma quantisation table of the quality in natural order (1 .. 255), then the
+ *   zigzag position of every natural index.
+ * Two launches.  Rows: one workgroup per (frame, MCU row) codes the row into its segment of the workspace, row_budget bytes
+ * long, and writes the row's byte length; every store is bounded by the budget.  Assemble: per frame the header, the rows back
+ * to back with the RSTm markers between them and EOI are packed into `out`, the frames back to back: frame f is
+ * out[offsets[f] .. offsets[f + 1]), offsets i64 [N + 1] with offsets[0] = 0.  status i32 [N]: FR_JPEG_OK; FR_JPEG_OVERFLOW - a
+ * row of the frame did not fit row_budget, or the frame would end past out_capacity (then so would every frame behind it): the
+ * frame has length 0, nothing of it is written, the other frames are untouched; FR_JPEG_SKIPPED (table form) - an entry with a
+ * non-positive side, a side above 65535 or above max_H / max_W, of 2 GiB or more or with a null pointer: length 0 likewise.
+ * Nothing is written past a row's budget, past out + out_capacity or past ws + ws_bytes.
+ * workspace: fr_jpeg_workspace(N, H, W, row_budget) bytes, H x W the frames' size (the table form: max_H x max_W); 0 for
+ * arguments the entries refuse.  A row of w pixels that is coded as it comes needs at most about 416 bytes per 8 x 8 block;
+ * the host's default budget is the strip's raw BGR size, 16 * 16 ceil(w / 16) * 3.
+ * Refused before any launch: N outside 0 .. 65535, H or W (max_H or max_W) outside 1 .. 65535, a frame of 2 GiB or more,
+ * row_budget < 1, header_len != FR_JPEG_HEADER_BYTES, a negative out_capacity, a workspace that is too small, a null pointer with
+ * N > 0.  N == 0 returns FR_OK and touches nothing.  Any byte alignment of the frames.  Added under ABI 106: no existing
+ * signature changed. */
+#define FR_JPEG_OK 0
+#define FR_JPEG_OVERFLOW 1
+#define FR_JPEG_SKIPPED 2
+#define FR_JPEG_HEADER_BYTES 629
+#define FR_JPEG_AT_H 163
+#define FR_JPEG_AT_W 165
+#define FR_JPEG_AT_DRI 613
+#define FR_JPEG_CODE_ROW 272
+size_t fr_jpeg_workspace(int N, int H, int W, int row_budget);
+int fr_jpeg_encode_u8(const uint8_t* frames, int N, int H, int W, const uint8_t* header, int header_len, const uint32_t* codes,
+                      const int32_t* qtables, int row_budget, uint8_t* out, int64_t out_capacity, int64_t* offsets,
+                      int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+int fr_jpeg_encode_refs_u8(const fr_frame_ref* refs, int nframes, int max_H, int max_W, const uint8_t* header, int header_len,
+                           const uint32_t* codes, const int32_t* qtables, int row_budget, uint8_t* out, int64_t out_capacity,
+                           int64_t* offsets, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- face tracks ----
  * Between detect and align: is this detection a face the camera's previous frame already showed, so that the embedding held
