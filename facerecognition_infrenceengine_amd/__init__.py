@@ -7,4 +7,5 @@ from .tracks import FaceTracks  # noqa: E402,F401
 from .quality import FaceQuality  # noqa: E402,F401
 from .hud import Hud  # noqa: E402,F401
 from .jpeg import JpegEncoder  # noqa: E402,F401
+from .jpeg_decode import JpegDecoder  # noqa: E402,F401
 from .gallery import DuplicateOverflowError, DuplicatePairs, GalleryMatcher  # noqa: E402,F401

@@ -45,6 +45,8 @@ class CameraManager:
         ``bytes`` (``latest_jpeg(source)``; None for a frame the encoder turned away).  None: arrays, as ever.
         ``pixel_format`` / ``matrix``: what the captures deliver - ``"nv12"`` / ``"i420"`` frames (``uint8 [H*3/2, W]``) need a
         ``hud``, since the host never holds a BGR picture of them to draw on (ValueError without one).
+        ``"jpeg"``: the captures deliver JPEG files as ``bytes`` (an MJPEG camera); they are decoded on the device behind the ring's
+        copy and need a ``hud`` for the same reason.
         ``max_wait_s``: how long a turn waits for a first frame before it looks at ``running`` again; a turn never
         waits for slow cameras once it holds a frame (latency stays that of the slowest *present* frame).
         ``reopen_after`` / ``dead_after``: consecutive failed reads before a capture is re-opened / given up."""
@@ -176,6 +178,14 @@ class CameraManager:
             except Exception as e:                         # logged and survived, as the reference's loop (:620-621)
                 logger.error("Error processing cameras %s: %s", [s for s, _ in batch], e)
 
+    def _shape_of(self, frame):
+        """what frames must share to go through the engine together: the array's shape, or a JPEG file's picture size"""
+        if self.pixel_format != "jpeg":
+            return tuple(frame.shape)
+        from .jpeg_decode import parse
+        hd = parse(frame)
+        return ("jpeg", id(frame)) if isinstance(hd, str) else (hd.H, hd.W, 3)     # a file the host must decode goes alone
+
     def process_batch(self, batch, company_id):
         """batch: [(source, frame)].  Frames of one size go through the engine together - all of them in ONE call when the
         processor takes mixed sizes (``accepts_mixed_sizes``: an engine with a ``det_size``); results leave in batch order.
@@ -194,7 +204,7 @@ class CameraManager:
         by_shape = {}
         mixed = getattr(self.processor, "accepts_mixed_sizes", False)
         for k, (_, f) in enumerate(batch):
-            by_shape.setdefault(None if mixed else tuple(f.shape), []).append(k)
+            by_shape.setdefault(None if mixed else self._shape_of(f), []).append(k)
         results, pictures = [None] * len(batch), [None] * len(batch)
         for ks in by_shape.values():
             ids = [company_id[k] for k in ks] if mixed_ids else [company_id]

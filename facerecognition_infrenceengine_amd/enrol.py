@@ -32,11 +32,16 @@ def largest_face_index(faces):
 
 
 class Enroller:
-    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4, quality=None):
+    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4, quality=None, decoder=None):
         """``quality`` (a ``quality.FaceQuality``): ``process_image`` has the engine judge the aligned faces, and ``enrol`` refuses a
         job whose pose image shows an unfit largest face (``{"status": "low_quality", "image": i, "reasons": [...]}``) - a gallery
         row lives for years.  ``enrol_batch`` and ``enrol_slots`` of such an Enroller raise ValueError: the batch kernel
-        (fr_enrol_batch_f32) picks the largest face on the device and takes no mask yet.  None: no face is judged, as ever."""
+        (fr_enrol_batch_f32) picks the largest face on the device and takes no mask yet.  None: no face is judged, as ever.
+
+        ``decoder`` (a ``jpeg_decode.JpegDecoder`` on the engine's device): ``enrol_batch`` decodes encoded images on the device
+        in one call, image by image falling back to the host decoder for what the device does not take; the pixels are the
+        same pixels, so every job's result is that of the host-decoded run.  None: decoded on the host, as ever."""
+        self.decoder = decoder
         self.app, self.similarity_threshold, self.duplicate_threshold = face_analysis, similarity_threshold, duplicate_threshold
         self.quality = quality
         self.lib = _lib.load()
@@ -180,7 +185,7 @@ class Enroller:
 
     def _engine_pass(self, images):
         """One ``detect_embed_slots`` call per image shape (one call in all with a ``det_size`` engine), grouped as
-        camera.CameraManager.process_batch groups frames.  images: BGR arrays, None for what did not decode.
+        camera.CameraManager.process_batch groups frames.  images: BGR arrays (or device tensors), None for what did not decode.
         Returns (slot dicts, image index of every input image)."""
         mixed = getattr(self.app, "det_size", None) is not None
         by_shape = {}
@@ -189,8 +194,12 @@ class Enroller:
                 by_shape.setdefault(None if mixed else tuple(im.shape), []).append(k)
         parts, index, base = [], [None] * len(images), 0
         for ks in by_shape.values():
-            frames = [np.ascontiguousarray(images[k]) for k in ks]
-            frames = self.app._to_device(frames if mixed else np.stack(frames))
+            if any(torch.is_tensor(images[k]) for k in ks):     # decoded on the device (``decoder``): they are there already
+                frames = self.app._to_device([images[k] for k in ks])
+                frames = frames if mixed else torch.stack(frames)
+            else:
+                frames = [np.ascontiguousarray(images[k]) for k in ks]
+                frames = self.app._to_device(frames if mixed else np.stack(frames))
             parts.append(self.app.detect_embed_slots(frames))
             for n, k in enumerate(ks):
                 index[k] = base + n
@@ -231,13 +240,16 @@ class Enroller:
         if not jobs:
             result.view = gallery if commit else None
             return result
-        images = []
-        for job in jobs:
-            for im in job:
-                if isinstance(im, (bytes, bytearray, memoryview)):
-                    from .ingest import decode_image
-                    im = decode_image(im)
-                images.append(im)
+        images = [im for job in jobs for im in job]
+        encoded = [k for k, im in enumerate(images) if isinstance(im, (bytes, bytearray, memoryview))]
+        if encoded and self.decoder is not None:                     # one device decode for all of them, falling back per image
+            with torch.cuda.device(self.device):
+                decoded = self.decoder.decode_frames([images[k] for k in encoded])
+        else:
+            from .ingest import decode_image
+            decoded = [decode_image(images[k]) for k in encoded]
+        for k, im in zip(encoded, decoded):
+            images[k] = im
         job_images, k = [], 0
         with torch.cuda.device(self.device):
             parts, index = self._engine_pass(images)

@@ -719,6 +719,37 @@ class FaceAnalysis:
         with self._lock, torch.cuda.device(self.device):
             return self._faces_of(self.detect_embed_device(yuv420_to_bgr(yuv, pixel_format, matrix)))
 
+    def get_batch_jpeg(self, blobs, decoder=None):
+        """``get_batch`` for JPEG files (one ``bytes`` per frame: an MJPEG camera's frames, enrolment photos): the files cross
+        the link as they are and are decoded on the device (csrc/jpeg_decode.hip); from there on the call IS ``get_batch`` on
+        the decoded frames - which are libjpeg's pixels, byte for byte - so the faces are those of
+        ``get_batch`` on the host-decoded pictures, bit for bit.  Pictures of one size, or under ``det_size`` of any sizes.  A
+        file the device decoder does not take (progressive, CMYK, not a JPEG at all ...) is decoded by ``ingest.decode_image``
+        on the host; a blob that does not decode either way is a frame without faces.  ``decoder``: a
+        ``jpeg_decode.JpegDecoder`` on this device (default: the engine's own).  Runs eagerly: ``enable_graphs`` does not cover
+        this entry point."""
+        if self.det is None:
+            raise _lib.FrError("FaceAnalysis.prepare() has not been called")
+        blobs = list(blobs)
+        if decoder is None:
+            decoder = self.__dict__.get("_jpeg_decoder")
+            if decoder is None:
+                from .jpeg_decode import JpegDecoder
+                decoder = self._jpeg_decoder = JpegDecoder(self.device)
+        with self._lock, torch.cuda.device(self.device):
+            frames = decoder.decode_frames(blobs)
+            live = [k for k, f in enumerate(frames) if f is not None]
+            res = [[] for _ in frames]
+            if live:
+                batch = [frames[k] for k in live]
+                if all(f.shape == batch[0].shape for f in batch):
+                    batch = torch.stack(batch)
+                elif self.det_size is None:
+                    raise ValueError("frames of differing sizes need a detection canvas: prepare(det_size=(w, h))")
+                for k, faces in zip(live, self._faces_of(self.detect_embed_device(batch))):
+                    res[k] = faces
+        return res
+
     def get_yuv(self, frame, pixel_format="nv12", matrix="bt601", max_num=0):
         """``get`` for one YUV 4:2:0 frame (``uint8 [H*3/2, W]``, host array or device tensor): see ``get_batch_yuv``.  Runs
         eagerly, whatever ``enable_graphs`` says."""

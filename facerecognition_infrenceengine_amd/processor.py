@@ -543,6 +543,11 @@ class FaceRecognitionProcessor:
         BGR's bytes and are converted on the device behind the copy; the results are those of the converted BGR frames.
         ``annotate`` draws on BGR host frames and does not take YUV.
 
+        ``pixel_format="jpeg"``: one ``bytes`` per frame, a JPEG file each.  The files go into the pinned ring as they are and are
+        decoded on the device behind the copy; a file the device decoder does not take is decoded by
+        ``ingest.decode_image`` on the host, a blob that does not decode at all is a black frame - no faces.  The results are those
+        of the decoded BGR frames, bit for bit.
+
         ``gate`` (an ``activity.ActivityGate``) with ``camera_ids`` (one hashable id per frame, none repeated): the frames go
         through the same ring, the gate judges the ring's device frames (one small device-to-host copy and one
         synchronisation more), and the engine pass, the scan and the decision run on the ACTIVE frames only - a device
@@ -635,7 +640,7 @@ class FaceRecognitionProcessor:
                 per_frame = list(results) if isinstance(results, list) else [None] * len(turn.arr)
                 if held is not None and kw.get("camera_ids") is not None:
                     per_frame = [held.get(c) if r is UNCHANGED else r for r, c in zip(per_frame, kw["camera_ids"])]
-                yuv = kw.get("pixel_format", "bgr") != "bgr"
+                yuv = kw.get("pixel_format", "bgr") in ("nv12", "i420")
                 shapes = [(a.shape[0] * 2 // 3, a.shape[1]) if yuv else a.shape[:2] for a in turn.arr]
                 with torch.cuda.device(det.device):
                     stream = torch.cuda.current_stream(det.device)
@@ -955,15 +960,11 @@ def _detect_embed_batch_gated(owner, det, frames, pixel_format="bgr", matrix="bt
     arr, ring, turn = _ring_turn(owner, det, frames, pixel_format, matrix)
     n, det_size = len(arr), getattr(det, "det_size", None)
     with det._lock, torch.cuda.device(det.device):
+        _fill_turn(ring, turn, arr, det_size)
         if det_size is None:
-            host = ring.host_buffer(turn)
-            for i, a in enumerate(arr):
-                host[i] = a
             dev, ready = ring.upload(turn)
             ragged = {}
         else:                                         # one arena, one copy, one engine pass whatever the frames' sizes
-            for i, a in enumerate(arr):
-                ring.host_frame(turn, i)[...] = a
             dev, table, ready = ring.upload(turn)
             ragged = {"table": table, "det_scale": ring.det_scale}
         if hold is not None:
@@ -1006,16 +1007,51 @@ def _upload_turn(owner, det, frames, pixel_format, matrix):
     import torch
     arr, ring, turn = _ring_turn(owner, det, frames, pixel_format, matrix)
     with det._lock, torch.cuda.device(det.device):
+        _fill_turn(ring, turn, arr, getattr(det, "det_size", None))
         if getattr(det, "det_size", None) is None:
-            host = ring.host_buffer(turn)
-            for i, a in enumerate(arr):
-                host[i] = a
             dev, ready = ring.upload(turn)
             return _HeldTurn(ring, turn, arr, dev, None, ready)
-        for i, a in enumerate(arr):
-            ring.host_frame(turn, i)[...] = a
         dev, table, ready = ring.upload(turn)
         return _HeldTurn(ring, turn, arr, dev, table, ready)
+
+
+# One JPEG file of a batch (``pixel_format="jpeg"``): its bytes, the (H, W, 3) of its picture, what ``jpeg_decode.parse`` made of
+# its header and - where the device does not take it - the host's decode (None: it does not decode, a black frame)
+_Encoded = collections.namedtuple("_Encoded", "data shape header image")
+
+
+def _encoded_frames(frames):
+    """The files of a JPEG batch as ``_Encoded``.  A file the device decoder does not take is decoded here, by
+    ``ingest.decode_image``, since its size is needed before a ring can be chosen; a blob that does not decode at all takes the
+    size of the batch's first picture (16 x 16 when there is none) and goes through the engine as a black frame - no faces."""
+    from .ingest import decode_image
+    from .jpeg_decode import parse
+    out = []
+    for f in frames:
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise ValueError("jpeg frames of a batch must be bytes, one file per frame")
+        hd = parse(f)
+        if isinstance(hd, str):
+            img = decode_image(f)
+            out.append(_Encoded(f, None if img is None else img.shape, hd, img))
+        else:
+            out.append(_Encoded(f, (hd.H, hd.W, 3), hd, None))
+    first = next((e.shape for e in out if e.shape is not None), (16, 16, 3))
+    return [e if e.shape is not None else e._replace(shape=first) for e in out]
+
+
+def _fill_turn(ring, turn, arr, det_size):
+    """the frames of a batch into the ring's pinned slot"""
+    if arr and isinstance(arr[0], _Encoded):
+        for i, e in enumerate(arr):
+            ring.put(turn, i, e.data, header=e.header, decoded=e.image)
+    elif det_size is None:
+        host = ring.host_buffer(turn)
+        for i, a in enumerate(arr):
+            host[i] = a
+    else:
+        for i, a in enumerate(arr):
+            ring.host_frame(turn, i)[...] = a
 
 
 def _ring_turn(owner, det, frames, pixel_format, matrix):
@@ -1024,10 +1060,13 @@ def _ring_turn(owner, det, frames, pixel_format, matrix):
     the engine's lock."""
     from .colour import check_pixel_format, check_yuv_shape
     from .ingest import FrameIngest, RaggedIngest
-    arr = [np.ascontiguousarray(np.asarray(f)) for f in frames]
     det_size = getattr(det, "det_size", None)
-    yuv = check_pixel_format(pixel_format, matrix)[0] is not None
-    if yuv:
+    jpeg = pixel_format == "jpeg"
+    arr = _encoded_frames(frames) if jpeg else [np.ascontiguousarray(np.asarray(f)) for f in frames]
+    yuv = not jpeg and check_pixel_format(pixel_format, matrix)[0] is not None
+    if jpeg:
+        shapes = tuple(e.shape[:2] for e in arr)
+    elif yuv:
         if any(a.ndim != 2 or a.dtype != np.uint8 for a in arr):
             raise ValueError(f"{pixel_format} frames of a batch must be uint8 [H*3/2, W]")
         shapes = tuple(check_yuv_shape(a.shape) for a in arr)
@@ -1040,9 +1079,11 @@ def _ring_turn(owner, det, frames, pixel_format, matrix):
         raise ValueError("frames of a batch must be uint8 [H,W,3] of one size (any sizes with prepare(det_size=...))")
     stages = owner.__dict__.setdefault("_stages", {})
     key = (n, h, w) if det_size is None else (shapes, det_size)
-    fmt = {"pixel_format": pixel_format, "matrix": matrix} if yuv else {}
+    fmt = {"pixel_format": pixel_format, "matrix": matrix} if yuv else {"pixel_format": "jpeg"} if jpeg else {}
     if yuv:                                           # the BGR rings keep the keys they always had
         key += (pixel_format, matrix)
+    elif jpeg:
+        key += ("jpeg",)
     if key not in stages:
         while len(stages) >= 8:                       # a few (cameras present, frame size) shapes at most: drop the oldest ring
             stages.pop(next(iter(stages)))

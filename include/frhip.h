@@ -51,6 +51,8 @@ typedef void* fr_stream_t;
  * and for fr_track_fuse_f32 (track templates: a track's last K shots fused into one scan query),
  * and for fr_hud_draw_u8 / fr_hud_draw_refs_u8 (the device HUD: recognition results drawn into the frames),
  * and for fr_jpeg_workspace / fr_jpeg_encode_u8 / fr_jpeg_encode_refs_u8 (the device JPEG encoder behind the HUD draw),
+ * and for fr_jpeg_decode_workspace / fr_jpeg_decode_refs_u8 / fr_jpeg_blank_bad_refs_u8 (the device JPEG decoder in front of the
+ * engine pass),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -926,6 +928,62 @@ int fr_jpeg_encode_u8(const uint8_t* frames, int N, int H, int W, const uint8_t*
 int fr_jpeg_encode_refs_u8(const fr_frame_ref* refs, int nframes, int max_H, int max_W, const uint8_t* header, int header_len,
                            const uint32_t* codes, const int32_t* qtables, int row_budget, uint8_t* out, int64_t out_capacity,
                            int64_t* offsets, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+
+/* Device JPEG decoder: baseline JPEG files on the device (an MJPEG camera's frames, enrolment photos) -> BGR u8 frames, so
+ * that the encoded bytes cross the link and the host never decodes (the reference decodes on the CPU: infrenceServer.py:573-601,
+ * trainingServer.py:219-221).  The pixels are DEFINED by tests/helpers/jpeg_decode_ref.py and reproduced byte for byte (32-bit
+ * integer arithmetic only); the definition is libjpeg's arithmetic: T.81 F.2.2 with the file's own tables,
+ * coef * q, the "islow" inverse DCT, "fancy" chroma upsampling (replication for a component at most 2 samples wide), the 16-bit
+ * fixed-point colour transform.  Baseline sequential, 8 bit, one interleaved scan, 3 components at 4:4:4 / 4:2:2 / 4:2:0 or 1
+ * component, any restart interval or none.  The HOST parses SOI .. SOS (jpeg_decode.py) and never touches the entropy data.
+ *
+ * data: DEVICE bytes, the files (or only their scans) back to back, data_bytes of them.  frames: a DEVICE table, one entry per
+ *   file: [scan_off, scan_off + scan_len) the entropy data - from behind SOS to the end of the file; the scan ends at the first
+ *   marker that is no RSTm -, H x W, sampling FR_JPEGD_444 / _422 / _420 / _GRAY, restart the MCUs of a restart interval (0:
+ *   none), and per component the tables: qsel an index into qtables, dcsel / acsel into htables.
+ * qtables: DEVICE i32 [nq][64], natural order.  htables: DEVICE i32 [nh][FR_JPEGD_HUFF_ROW], one Huffman table each: [0, 512)
+ *   the next 9 bits -> length << 8 | symbol (0: a longer code or none), [512, 530) maxcode by length (-1: no code of that
+ *   length), [530, 548) valptr - mincode by length, [548, 804) HUFFVAL (jpeg_decode.huffman_row).  natural: DEVICE i32 [64],
+ *   zigzag position -> natural index (jpeg_tables.ZIGZAG; the library holds no copy).
+ * refs: a DEVICE frame table; entry f names the destination of file f, its H x W the file's.  status i32 [nframes]:
+ *   FR_JPEGD_OK; FR_JPEGD_BAD_STREAM - the scan broke off, holds a code no table has, runs a coefficient index past 63, has a
+ *   restart marker out of order or another number of intervals or blocks than the header implies: the frame's pixels are not
+ *   written; FR_JPEGD_SKIPPED - an entry the launches cannot follow (a null destination, sizes that differ from the
+ *   destination's or exceed max_H x max_W, an unknown sampling, a table index out of range, a scan outside data or of 2^28
+ *   bytes and more, more restart intervals than max_segments): nothing of it is read or written.  The other frames are untouched
+ *   either way, and no load or store leaves the scan, the workspace or the destination.
+ * workspace: fr_jpeg_decode_workspace(nframes, max_H, max_W, max_segments) bytes on a 16-byte boundary (0 for arguments no
+ *   decode exists for); max_segments: the most restart intervals any file has (1 without DRI).
+ * Four launches on `stream`, no allocation, no synchronisation.  FR_E_INVALID before any launch for nframes outside 0 .. 65535,
+ * max_H or max_W outside 1 .. 65535, max_H * max_W * 3 >= 2^31, max_segments outside 1 .. 2^24, nq or nh outside 1 .. 65535, a
+ * negative data_bytes, a workspace that is too small or misaligned, a null pointer with nframes > 0.  nframes == 0 returns
+ * FR_OK and touches nothing.  Added under ABI 106: no existing signature changed. */
+#define FR_JPEGD_OK 0
+#define FR_JPEGD_BAD_STREAM 1
+#define FR_JPEGD_SKIPPED 2
+#define FR_JPEGD_444 0
+#define FR_JPEGD_422 1
+#define FR_JPEGD_420 2
+#define FR_JPEGD_GRAY 3
+#define FR_JPEGD_HUFF_ROW 804
+typedef struct {
+    int64_t scan_off;
+    int32_t scan_len;
+    int32_t H, W, sampling, restart;
+    int32_t qsel[3], dcsel[3], acsel[3];
+} fr_jpeg_frame;
+size_t fr_jpeg_decode_workspace(int nframes, int max_H, int max_W, int max_segments);
+int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes, int max_H, int max_W,
+                           int max_segments, const int32_t* qtables, int nq, const int32_t* htables, int nh, const int32_t* natural,
+                           const fr_frame_ref* refs, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* Behind fr_jpeg_decode_refs_u8, for destinations that are REUSED (a ring's device frames): zeroes the H * W * 3 bytes of every
+ * frame whose status is FR_JPEGD_BAD_STREAM, so that a file whose scan broke off is a black frame and not the picture its
+ * destination held before.  Frames with another status, and null or empty entries, are left alone.  One launch on `stream`, no
+ * synchronisation.  FR_E_INVALID for nframes outside 0 .. 65535 or a null pointer with nframes > 0.  Added under ABI 106.
+ * The workspace of fr_jpeg_decode_refs_u8 also holds, for whoever measures the entropy launch: in frame f's slot (slots of
+ * fr_jpeg_decode_workspace(1, max_H, max_W, max_segments) bytes each), i32 [2 max_segments + k] the most rounds behind round 0
+ * that any chunk of restart interval k needed. */
+int fr_jpeg_blank_bad_refs_u8(const fr_frame_ref* refs, const int32_t* status, int nframes, fr_stream_t stream);
 
 /* ---------------------------------------------------------------- face tracks ----
  * Between detect and align: is this detection a face the camera's previous frame already showed, so that the embedding held
