@@ -158,6 +158,7 @@ SIGNATURES = {
     "fr_jpeg_encode_refs_u8": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _L, _P, _P, _P, _Z, _P]),
     "fr_jpeg_decode_workspace": (_Z, [_I, _I, _I, _I]),
     "fr_jpeg_decode_refs_u8": (_I, [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _Z, _P]),
+    "fr_jpeg_decode_oriented_refs_u8": (_I, [_P, _L, _P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _Z, _P]),
     "fr_jpeg_blank_bad_refs_u8": (_I, [_P, _P, _I, _P]),
     "fr_track_associate_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P]),
     "fr_track_commit_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),

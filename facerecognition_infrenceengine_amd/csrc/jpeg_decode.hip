@@ -27,6 +27,9 @@
 // jpegd_colour: a lane per output pixel reads the planes (chroma through the triangle filter on the component cropped to its
 //   real size, or replicated when the component is at most 2 samples wide, as libjpeg does) and writes BGR through the frame
 //   table - the destination form fr_yuv420_to_bgr_refs_u8 writes.
+// jpegd_colour_oriented: the last launch of fr_jpeg_decode_oriented_refs_u8 in its place: the same pixels, written where each
+//   frame's EXIF orientation (1 .. 8, a device word per frame) puts them; 5 .. 8 turn a tile in LDS so that the stores run along
+//   destination rows.
 // Plain vector loads and stores, LDS atomics only, byte offsets in int64, nothing allocated, nothing synchronised.
 #include "common.h"
 #include <algorithm>
@@ -90,6 +93,7 @@ struct DecodeArgs {
     const int32_t* qtables;
     const int32_t* htables;
     const fr_frame_ref* refs;
+    const int32_t* orient;      // EXIF orientation per frame, 1 .. 8; null: all 1
     int32_t* status;
     uint8_t* ws;
     int nq, nh, max_H, max_W, max_segments;
@@ -107,19 +111,22 @@ __device__ __forceinline__ uint8_t* slot_planes(const DecodeArgs& a, int f) {
     return a.ws + f * s.total() + s.seg_bytes + s.coef_bytes;
 }
 
+__device__ __forceinline__ int orientation_of(const DecodeArgs& a, int f) { return a.orient ? a.orient[f] : 1; }
+
 __device__ __forceinline__ int intervals_of(const fr_jpeg_frame& d, const Geometry& g) {
     return d.restart > 0 ? (g.mcus + d.restart - 1) / d.restart : 1;
 }
 
 // is the entry one the launches may follow?  Every index and range the kernels use is judged here, once.
-__device__ bool frame_usable(const DecodeArgs& a, const fr_jpeg_frame& d, const fr_frame_ref& r) {
+__device__ bool frame_usable(const DecodeArgs& a, const fr_jpeg_frame& d, const fr_frame_ref& r, int o) {
+    if (o < 1 || o > 8) return false;
     if (d.H < 1 || d.W < 1 || d.H > a.max_H || d.W > a.max_W) return false;
     if (d.sampling < FR_JPEGD_444 || d.sampling > FR_JPEGD_GRAY) return false;
     if (d.restart < 0 || d.restart > 65535) return false;
     if (d.scan_off < 0 || d.scan_len < 0 || d.scan_len >= JD_MAX_SCAN || d.scan_off > a.stream_bytes ||
         d.scan_len > a.stream_bytes - d.scan_off)
         return false;
-    if (!r.data || r.H != d.H || r.W != d.W) return false;
+    if (!r.data || r.H != (o > 4 ? d.W : d.H) || r.W != (o > 4 ? d.H : d.W)) return false;   // 5 .. 8 turn the picture: W x H
     const int nc = d.sampling == FR_JPEGD_GRAY ? 1 : 3;
     for (int c = 0; c < nc; ++c)
         if (d.qsel[c] < 0 || d.qsel[c] >= a.nq || d.dcsel[c] < 0 || d.dcsel[c] >= a.nh || d.acsel[c] < 0 || d.acsel[c] >= a.nh)
@@ -148,7 +155,7 @@ __global__ __launch_bounds__(JD_LANES) void jpegd_segments(DecodeArgs a) {
     __shared__ int term, bad;
     const int f = blockIdx.x, tid = threadIdx.x;
     const fr_jpeg_frame d = a.frames[f];
-    if (!frame_usable(a, d, a.refs[f])) {                 // block-uniform
+    if (!frame_usable(a, d, a.refs[f], orientation_of(a, f))) {                 // block-uniform
         if (tid == 0) a.status[f] = FR_JPEGD_SKIPPED;
         return;
     }
@@ -588,22 +595,11 @@ __global__ __launch_bounds__(JD_LANES) void jpegd_idct(DecodeArgs a) {
 }
 
 // ---------------------------------------------------------------- upsample + colour
-__global__ __launch_bounds__(JD_LANES) void jpegd_colour(DecodeArgs a) {
-    const int f = blockIdx.y;
-    if (a.status[f] != FR_JPEGD_OK) return;
-    const fr_jpeg_frame d = a.frames[f];
-    const int64_t idx = (int64_t)blockIdx.x * JD_LANES + threadIdx.x;
-    if (idx >= (int64_t)d.H * d.W) return;
-    const int y = (int)(idx / d.W), x = (int)(idx - (int64_t)y * d.W);
-    const Geometry g = geometry(d.H, d.W, d.sampling);
-    const Planes p = planes_of(g);
-    const uint8_t* __restrict__ pl = slot_planes(a, f);
+// pixel (y, x) of a frame from its planes `pl`: B | G << 8 | R << 16
+__device__ __forceinline__ unsigned pixel_bgr(const fr_jpeg_frame& d, const Geometry& g, const Planes& p, const uint8_t* __restrict__ pl,
+                                              int y, int x) {
     const int Y = pl[p.off[0] + (int64_t)y * p.pitch[0] + x];
-    uint8_t* __restrict__ out = const_cast<uint8_t*>(a.refs[f].data) + idx * 3;
-    if (d.sampling == FR_JPEGD_GRAY) {
-        out[0] = out[1] = out[2] = (uint8_t)Y;
-        return;
-    }
+    if (d.sampling == FR_JPEGD_GRAY) return (unsigned)Y * 0x010101u;
     int ch[2];
     const int cw = (d.W + g.hs - 1) / g.hs, chh = (d.H + g.vs - 1) / g.vs;       // the chroma component's real size
     const int cx = x / g.hs, cy = y / g.vs;
@@ -630,9 +626,67 @@ __global__ __launch_bounds__(JD_LANES) void jpegd_colour(DecodeArgs a) {
     const int r = Y + ((91881 * cr + 32768) >> 16);
     const int gg = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
     const int b = Y + ((116130 * cb + 32768) >> 16);
-    out[0] = (uint8_t)min(max(b, 0), 255);
-    out[1] = (uint8_t)min(max(gg, 0), 255);
-    out[2] = (uint8_t)min(max(r, 0), 255);
+    return (unsigned)min(max(b, 0), 255) | (unsigned)min(max(gg, 0), 255) << 8 | (unsigned)min(max(r, 0), 255) << 16;
+}
+
+__device__ __forceinline__ void store_bgr(uint8_t* __restrict__ out, unsigned v) {
+    out[0] = (uint8_t)v;
+    out[1] = (uint8_t)(v >> 8);
+    out[2] = (uint8_t)(v >> 16);
+}
+
+__global__ __launch_bounds__(JD_LANES) void jpegd_colour(DecodeArgs a) {
+    const int f = blockIdx.y;
+    if (a.status[f] != FR_JPEGD_OK) return;
+    const fr_jpeg_frame d = a.frames[f];
+    const int64_t idx = (int64_t)blockIdx.x * JD_LANES + threadIdx.x;
+    if (idx >= (int64_t)d.H * d.W) return;
+    const int y = (int)(idx / d.W), x = (int)(idx - (int64_t)y * d.W);
+    const Geometry g = geometry(d.H, d.W, d.sampling);
+    store_bgr(const_cast<uint8_t*>(a.refs[f].data) + idx * 3, pixel_bgr(d, g, planes_of(g), slot_planes(a, f), y, x));
+}
+
+// The same pixels written where the EXIF orientation puts them (tests/helpers/orient_ref.py): 2 .. 4 mirror, 5 .. 8 also swap
+// rows and columns, and the destination is W x H.  A workgroup takes a JD_TILE x JD_TILE tile of the SOURCE and reads the planes
+// along source rows.  For 1 .. 4 a source row is a destination row and the lanes store at once.  For 5 .. 8 the tile's pixels
+// wait in LDS, one word each, and are read back turned, so that consecutive lanes store along a DESTINATION row: a run of up to
+// 3 JD_TILE bytes, where a lane per source pixel would scatter 3-byte stores a destination row apart.  The pitch of JD_TILE + 1
+// words keeps both the row-wise ds_write_b32 and the column-wise ds_read_b32 of a 32-lane group on 32 different banks.
+constexpr int JD_TILE = 32;
+
+__global__ __launch_bounds__(JD_LANES) void jpegd_colour_oriented(DecodeArgs a) {
+    __shared__ unsigned tile[JD_TILE * (JD_TILE + 1)];
+    const int f = blockIdx.y;
+    if (a.status[f] != FR_JPEGD_OK) return;               // block-uniform, as is every branch on `o` below
+    const fr_jpeg_frame d = a.frames[f];
+    const int tiles_x = (d.W + JD_TILE - 1) / JD_TILE, tiles_y = (d.H + JD_TILE - 1) / JD_TILE;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    if (ty >= tiles_y) return;
+    const int o = orientation_of(a, f);                   // 1 .. 8: the segments launch judged it
+    const bool turn = o > 4, flip_x = o == 2 || o == 3 || o == 7 || o == 8, flip_y = o == 3 || o == 4 || o == 6 || o == 7;
+    const Geometry g = geometry(d.H, d.W, d.sampling);
+    const Planes p = planes_of(g);
+    const uint8_t* __restrict__ pl = slot_planes(a, f);
+    uint8_t* __restrict__ out = const_cast<uint8_t*>(a.refs[f].data);
+    const int x0 = tx * JD_TILE, y0 = ty * JD_TILE;
+    const int lx = threadIdx.x % JD_TILE, ly = threadIdx.x / JD_TILE;
+#pragma unroll
+    for (int r = ly; r < JD_TILE; r += JD_LANES / JD_TILE) {
+        const int y = y0 + r, x = x0 + lx;
+        if (y >= d.H || x >= d.W) continue;
+        const unsigned v = pixel_bgr(d, g, p, pl, y, x);
+        if (turn) tile[r * (JD_TILE + 1) + lx] = v;
+        else store_bgr(out + ((int64_t)(flip_y ? d.H - 1 - y : y) * d.W + (flip_x ? d.W - 1 - x : x)) * 3, v);
+    }
+    if (!turn) return;
+    __syncthreads();
+    // destination row <- source column x0 + c, destination column <- source row y0 + lx
+#pragma unroll
+    for (int c = ly; c < JD_TILE; c += JD_LANES / JD_TILE) {
+        const int y = y0 + lx, x = x0 + c;
+        if (y >= d.H || x >= d.W) continue;
+        store_bgr(out + ((int64_t)(flip_x ? d.W - 1 - x : x) * d.H + (flip_y ? d.H - 1 - y : y)) * 3, tile[lx * (JD_TILE + 1) + c]);
+    }
 }
 
 typedef int4v int4v_any __attribute__((aligned(1)));               // 16-byte store at any byte address
@@ -663,11 +717,12 @@ extern "C" size_t fr_jpeg_decode_workspace(int N, int max_H, int max_W, int max_
     return (size_t)N * (size_t)slot_of(max_H, max_W, max_segments).total();
 }
 
-extern "C" int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes,
-                                      int max_H, int max_W, int max_segments, const int32_t* qtables, int nq, const int32_t* htables,
-                                      int nh, const int32_t* natural, const fr_frame_ref* refs, int32_t* status, void* workspace,
-                                      size_t workspace_bytes, fr_stream_t stream) {
-    const char* who = "fr_jpeg_decode_refs_u8";
+namespace {
+
+int decode_refs(const char* who, const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes, int max_H,
+                int max_W, int max_segments, const int32_t* qtables, int nq, const int32_t* htables, int nh, const int32_t* natural,
+                const fr_frame_ref* refs, const int32_t* orient, int32_t* status, void* workspace, size_t workspace_bytes,
+                fr_stream_t stream) {
     FR_REQUIRE(nframes >= 0 && nframes <= 65535, "%s: bad size (0 .. 65535 frames)", who);
     FR_REQUIRE(max_H >= 1 && max_H <= 65535 && max_W >= 1 && max_W <= 65535, "%s: bad size (max_H and max_W 1 .. 65535)", who);
     FR_REQUIRE((int64_t)max_H * max_W * 3 < (1ll << 31), "%s: a %d x %d frame is beyond 2 GiB", who, max_H, max_W);
@@ -679,8 +734,8 @@ extern "C" int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, c
     FR_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu bytes, %zu needed)", who, workspace_bytes, need);
     FR_REQUIRE(data && frames && qtables && htables && natural && refs && status && workspace, "%s: null pointer", who);
     FR_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "%s: workspace not on a 16-byte boundary", who);
-    const DecodeArgs a{data, data_bytes, frames, qtables, htables, refs, status, static_cast<uint8_t*>(workspace),
-                       nq,           nh,         max_H,  max_W,   max_segments};
+    const DecodeArgs a{data, data_bytes, frames, qtables, htables, refs, orient, status, static_cast<uint8_t*>(workspace),
+                       nq,   nh,         max_H,  max_W,   max_segments};
     hipStream_t s = fr_stream(stream);
     jpegd_segments<<<(unsigned)nframes, JD_LANES, 0, s>>>(a);
     FR_CHECK_LAUNCH("jpegd_segments");
@@ -689,10 +744,35 @@ extern "C" int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, c
     const int64_t blocks = max_blocks(max_H, max_W);
     jpegd_idct<<<dim3((unsigned)((blocks + 31) / 32), (unsigned)nframes), JD_LANES, 0, s>>>(a);
     FR_CHECK_LAUNCH("jpegd_idct");
-    const int64_t px = (int64_t)max_H * max_W;
-    jpegd_colour<<<dim3((unsigned)((px + JD_LANES - 1) / JD_LANES), (unsigned)nframes), JD_LANES, 0, s>>>(a);
-    FR_CHECK_LAUNCH("jpegd_colour");
+    if (orient) {                                         // tiles of the coded geometry
+        const int64_t tiles = (int64_t)((max_H + JD_TILE - 1) / JD_TILE) * ((max_W + JD_TILE - 1) / JD_TILE);
+        jpegd_colour_oriented<<<dim3((unsigned)tiles, (unsigned)nframes), JD_LANES, 0, s>>>(a);
+        FR_CHECK_LAUNCH("jpegd_colour_oriented");
+    } else {
+        const int64_t px = (int64_t)max_H * max_W;
+        jpegd_colour<<<dim3((unsigned)((px + JD_LANES - 1) / JD_LANES), (unsigned)nframes), JD_LANES, 0, s>>>(a);
+        FR_CHECK_LAUNCH("jpegd_colour");
+    }
     return FR_OK;
+}
+
+}  // namespace
+
+extern "C" int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes,
+                                      int max_H, int max_W, int max_segments, const int32_t* qtables, int nq, const int32_t* htables,
+                                      int nh, const int32_t* natural, const fr_frame_ref* refs, int32_t* status, void* workspace,
+                                      size_t workspace_bytes, fr_stream_t stream) {
+    return decode_refs("fr_jpeg_decode_refs_u8", data, data_bytes, frames, nframes, max_H, max_W, max_segments, qtables, nq, htables,
+                       nh, natural, refs, nullptr, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fr_jpeg_decode_oriented_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes,
+                                               int max_H, int max_W, int max_segments, const int32_t* qtables, int nq,
+                                               const int32_t* htables, int nh, const int32_t* natural, const fr_frame_ref* refs,
+                                               const int32_t* orient, int32_t* status, void* workspace, size_t workspace_bytes,
+                                               fr_stream_t stream) {
+    return decode_refs("fr_jpeg_decode_oriented_refs_u8", data, data_bytes, frames, nframes, max_H, max_W, max_segments, qtables, nq,
+                       htables, nh, natural, refs, orient, status, workspace, workspace_bytes, stream);
 }
 
 extern "C" int fr_jpeg_blank_bad_refs_u8(const fr_frame_ref* refs, const int32_t* status, int nframes, fr_stream_t stream) {

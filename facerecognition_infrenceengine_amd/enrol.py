@@ -32,7 +32,7 @@ def largest_face_index(faces):
 
 
 class Enroller:
-    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4, quality=None, decoder=None):
+    def __init__(self, face_analysis, similarity_threshold=0.4, duplicate_threshold=0.4, quality=None, decoder=None, orient=False):
         """``quality`` (a ``quality.FaceQuality``): ``process_image`` has the engine judge the aligned faces, and ``enrol`` refuses a
         job whose pose image shows an unfit largest face (``{"status": "low_quality", "image": i, "reasons": [...]}``) - a gallery
         row lives for years.  ``enrol_batch`` and ``enrol_slots`` of such an Enroller raise ValueError: the batch kernel
@@ -40,7 +40,15 @@ class Enroller:
 
         ``decoder`` (a ``jpeg_decode.JpegDecoder`` on the engine's device): ``enrol_batch`` decodes encoded images on the device
         in one call, image by image falling back to the host decoder for what the device does not take; the pixels are the
-        same pixels, so every job's result is that of the host-decoded run.  None: decoded on the host, as ever."""
+        same pixels, so every job's result is that of the host-decoded run.  None: decoded on the host, as ever.
+
+        ``orient=True``: encoded images are turned as their EXIF orientation says before the detector sees them - the picture
+        ``cv2.imdecode`` hands the reference's worker (trainingServer.py:219-221), where the default passes an upright phone photo
+        on as coded, lying on its side.  Host decode (``process_image``, ``enrol``) and device decode (``enrol_batch`` through ``decoder``,
+        and its host fallback) honour it alike; a ``decoder`` built with another ``orient`` raises ValueError here."""
+        self.orient = bool(orient)
+        if decoder is not None and bool(getattr(decoder, "orient", False)) != self.orient:
+            raise ValueError(f"Enroller(orient={self.orient}) with a decoder built with orient={bool(getattr(decoder, 'orient', False))}")
         self.decoder = decoder
         self.app, self.similarity_threshold, self.duplicate_threshold = face_analysis, similarity_threshold, duplicate_threshold
         self.quality = quality
@@ -57,7 +65,7 @@ class Enroller:
         """The Face ``process_image`` takes its embedding from, or None; with ``quality`` it carries the verdict."""
         if isinstance(image, (bytes, bytearray, memoryview)):
             from .ingest import decode_image
-            image = decode_image(image)
+            image = decode_image(image, orient=getattr(self, "orient", False))
             if image is None:
                 return None
         faces = self.app.get(image) if self.quality is None else self.app.get(image, quality=self.quality)
@@ -247,7 +255,7 @@ class Enroller:
                 decoded = self.decoder.decode_frames([images[k] for k in encoded])
         else:
             from .ingest import decode_image
-            decoded = [decode_image(images[k]) for k in encoded]
+            decoded = [decode_image(images[k], orient=getattr(self, "orient", False)) for k in encoded]
         for k, im in zip(encoded, decoded):
             images[k] = im
         job_images, k = [], 0

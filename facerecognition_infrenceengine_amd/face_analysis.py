@@ -719,23 +719,29 @@ class FaceAnalysis:
         with self._lock, torch.cuda.device(self.device):
             return self._faces_of(self.detect_embed_device(yuv420_to_bgr(yuv, pixel_format, matrix)))
 
-    def get_batch_jpeg(self, blobs, decoder=None):
+    def get_batch_jpeg(self, blobs, decoder=None, orient=False):
         """``get_batch`` for JPEG files (one ``bytes`` per frame: an MJPEG camera's frames, enrolment photos): the files cross
         the link as they are and are decoded on the device (csrc/jpeg_decode.hip); from there on the call IS ``get_batch`` on
         the decoded frames - which are libjpeg's pixels, byte for byte - so the faces are those of
         ``get_batch`` on the host-decoded pictures, bit for bit.  Pictures of one size, or under ``det_size`` of any sizes.  A
         file the device decoder does not take (progressive, CMYK, not a JPEG at all ...) is decoded by ``ingest.decode_image``
         on the host; a blob that does not decode either way is a frame without faces.  ``decoder``: a
-        ``jpeg_decode.JpegDecoder`` on this device (default: the engine's own).  Runs eagerly: ``enable_graphs`` does not cover
-        this entry point."""
+        ``jpeg_decode.JpegDecoder`` on this device (default: the engine's own).  ``orient=True``: every picture is turned as
+        its EXIF orientation says (a phone's upright photo; what ``cv2.imdecode`` gives the reference), on the device in the
+        decoder's last launch, and the faces' coordinates are the turned picture's; a ``decoder`` passed in must have been built
+        with the same ``orient`` (ValueError).  Runs eagerly: ``enable_graphs`` does not cover this entry point."""
         if self.det is None:
             raise _lib.FrError("FaceAnalysis.prepare() has not been called")
         blobs = list(blobs)
         if decoder is None:
-            decoder = self.__dict__.get("_jpeg_decoder")
+            name = "_jpeg_decoder_oriented" if orient else "_jpeg_decoder"
+            decoder = self.__dict__.get(name)
             if decoder is None:
                 from .jpeg_decode import JpegDecoder
-                decoder = self._jpeg_decoder = JpegDecoder(self.device)
+                decoder = JpegDecoder(self.device, orient=bool(orient))
+                setattr(self, name, decoder)
+        elif bool(getattr(decoder, "orient", False)) != bool(orient):
+            raise ValueError(f"get_batch_jpeg(orient={bool(orient)}) with a decoder built with orient={decoder.orient}")
         with self._lock, torch.cuda.device(self.device):
             frames = decoder.decode_frames(blobs)
             live = [k for k, f in enumerate(frames) if f is not None]

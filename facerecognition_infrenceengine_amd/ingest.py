@@ -19,19 +19,32 @@ import torch
 from . import _lib
 
 
-def decode_image(data):
+def decode_image(data, orient=False):
     """Encoded image bytes (JPEG / PNG ...) -> ``uint8 [H,W,3]`` BGR, or None when the bytes do not decode: the
     ``cv2.imdecode(np.frombuffer(blob, np.uint8), cv2.IMREAD_COLOR)`` of the enrolment worker
     (/root/reference/trainingServer.py:219-224), with Pillow standing in for OpenCV (absent from the image).  Host
     side by design (decode stays on the CPU); JPEG decoders differ in their IDCT rounding, so
-    pixel values can differ from OpenCV's by a unit - the lossless formats decode identically."""
+    pixel values can differ from OpenCV's by a unit - the lossless formats decode identically.
+
+    ``orient=True``: the picture as its EXIF orientation turns it, which is what ``cv2.imdecode`` returns (OpenCV applies the
+    tag unless told IMREAD_IGNORE_ORIENTATION): a JPEG's through ``jpeg_decode.exif_orientation`` - so a file decoded here and
+    one decoded on the device give the same array -, another format's through Pillow's ``getexif``.  Default: as coded."""
+    turn = 1
     try:
         from PIL import Image
-        with Image.open(io.BytesIO(bytes(data))) as im:
+        data = bytes(data)
+        with Image.open(io.BytesIO(data)) as im:
             rgb = np.asarray(im.convert("RGB"), dtype=np.uint8)
+            if orient:
+                from .jpeg_decode import exif_orientation
+                turn = exif_orientation(data) if im.format in ("JPEG", "MPO") else im.getexif().get(0x0112, 1)
     except Exception:                        # the reference logs "Failed to decode" and skips the image
         return None
-    return np.ascontiguousarray(rgb[:, :, ::-1])
+    bgr = rgb[:, :, ::-1]
+    if turn in (2, 3, 4, 5, 6, 7, 8):
+        from .jpeg_decode import orient as turned
+        bgr = turned(bgr, turn)
+    return np.ascontiguousarray(bgr)
 
 
 class _JpegSlots:
@@ -41,7 +54,11 @@ class _JpegSlots:
     device is allocated here, once: staging, status words, the decoder's workspace.  A blob the device cannot take (``parse``
     turned it away, another size than its frame, longer than the slot has room for) is decoded by ``decode_image`` into a pinned
     BGR side buffer (made on first need) and copied into its device frame behind the decode launches; a blob that does not
-    decode at all is a black frame."""
+    decode at all is a black frame.
+
+    The rings (``FrameIngest`` / ``RaggedIngest`` with ``pixel_format="jpeg"``) IGNORE an EXIF orientation tag: their frames
+    have fixed sizes and they serve cameras, which write none.  Photos that carry one go through
+    ``JpegDecoder(..., orient=True)`` (enrolment, ``get_batch_jpeg``)."""
 
     def __init__(self, device, depth, shapes, offsets, nbytes, max_frame_bytes):
         from .jpeg_decode import FRAME, JpegDecoder
@@ -149,7 +166,8 @@ class FrameIngest:
         stream: no gain / -5 %, profiles/r04_ingest_ab.txt; the knobs are gone).  ``pixel_format`` ``"nv12"`` / ``"i420"`` with
         ``matrix`` (colour.MATRICES): YUV 4:2:0 slots, H and W even, converted on the device by ``upload``.  ``pixel_format="jpeg"``
         (``max_frame_bytes``: room for one file's scan, default H * W * 3 / 2): the slots hold encoded bytes, written with ``put``,
-        and ``upload`` decodes them on the device behind the copy (``_JpegSlots``)."""
+        and ``upload`` decodes them on the device behind the copy (``_JpegSlots``); an EXIF orientation tag is ignored (the
+        frames have one fixed size, and cameras write none)."""
         from .colour import check_pixel_format, check_yuv_size
         _lib.require_gpu()
         self.device = torch.device(device)
@@ -252,7 +270,8 @@ class RaggedIngest:
     ``pixel_format="nv12"`` / ``"i420"`` (``shapes`` stay the frames' (H, W), both even): the pinned arena holds the YUV 4:2:0
     frames (``[H*3/2, W]`` each, at 16-byte-aligned offsets of their own), ``upload`` copies it to ONE device staging arena
     and converts the whole table in one launch behind the copy; the device arena, the tables and ``det_scale`` are those of
-    the BGR ring."""
+    the BGR ring.  ``pixel_format="jpeg"``: as ``FrameIngest``'s (``_JpegSlots``); an EXIF orientation tag is ignored, the frames
+    keep the sizes given here."""
 
     def __init__(self, shapes, det_size=None, device="cuda:0", depth=3, pixel_format="bgr", matrix="bt601", max_frame_bytes=None):
         from .colour import check_pixel_format, check_yuv_size

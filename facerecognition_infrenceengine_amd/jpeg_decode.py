@@ -9,7 +9,11 @@ file.  The host reads SOI .. SOS only (``parse``: a walk over segment lengths); 
 Supported: baseline sequential (SOF0), 8 bit, one interleaved scan, 3 components at 4:4:4 / 4:2:2 / 4:2:0 or 1 component, any
 DQT / DHT contents, any restart interval or none.  Everything else - progressive, arithmetic coding, 16-bit DQT, CMYK, other
 sampling factors, several scans - ``parse`` names as a reason string without a launch, and the caller falls back to
-``decode_image``."""
+``decode_image``.
+
+EXIF orientation (``exif_orientation``, ``orient``; ``JpegDecoder(..., orient=True)``): a phone held upright writes the sensor's
+landscape picture and says in an Exif tag how to turn it.  ``cv2.imdecode`` applies the tag; with ``orient=True`` so does the
+device decoder, in the launch that writes the pixels.  Off by default: the pixels as coded."""
 import collections
 import logging
 import struct
@@ -143,6 +147,76 @@ def parse(data):
     return Header(h, w, sampling, restart, pos, tuple(qtables), tuple(huffman), (mcus + restart - 1) // restart if restart else 1)
 
 
+def exif_orientation(data):
+    """The EXIF orientation a JPEG file carries, 1 .. 8; 1 (as coded) for a file without one.  Walks SOI .. SOS by segment
+    lengths as ``parse`` does and takes the FIRST ``APP1`` segment whose payload begins ``Exif\\0\\0``: the TIFF header (``II`` /
+    ``MM``, 42, the offset of IFD0), then IFD0's entries up to tag 0x0112, of type SHORT (count 1 or 2) or LONG (count 1); its
+    first value when that is 1 .. 8.  Everything else is 1: no such segment or tag, another type or count, another value, an
+    offset or entry count that leaves the segment, a file cut short.  Never raises, never reads the entropy data."""
+    try:
+        data = memoryview(data).cast("B")
+    except TypeError:
+        return 1
+    n = len(data)
+    if n < 2 or data[0] != 0xFF or data[1] != 0xD8:
+        return 1
+    pos = 2
+    while pos + 4 <= n and data[pos] == 0xFF:
+        marker = data[pos + 1]
+        if marker == 0xFF:                               # a fill byte
+            pos += 1
+            continue
+        if marker in (0xDA, 0xD9, 0x01) or 0xD0 <= marker <= 0xD7:
+            return 1
+        length = data[pos + 2] << 8 | data[pos + 3]
+        if length < 2 or pos + 2 + length > n:
+            return 1
+        if marker == 0xE1 and length >= 8 and bytes(data[pos + 4:pos + 10]) == b"Exif\0\0":
+            return _tiff_orientation(bytes(data[pos + 10:pos + 2 + length]))
+        pos += 2 + length
+    return 1
+
+
+def _tiff_orientation(tiff):
+    """tag 0x0112 of IFD0 of a TIFF structure (the payload of an Exif segment behind its six-byte name), or 1"""
+    if len(tiff) < 8 or tiff[:2] not in (b"II", b"MM"):
+        return 1
+    order = "<" if tiff[:2] == b"II" else ">"
+    magic, ifd = struct.unpack(order + "HI", tiff[2:8])
+    if magic != 42 or ifd + 2 > len(tiff):
+        return 1
+    count, = struct.unpack_from(order + "H", tiff, ifd)
+    if ifd + 2 + 12 * count > len(tiff):
+        return 1
+    for e in range(count):
+        tag, kind, values = struct.unpack_from(order + "HHI", tiff, ifd + 2 + 12 * e)
+        if tag != 0x0112:
+            continue
+        if kind == 3 and values in (1, 2):
+            value, = struct.unpack_from(order + "H", tiff, ifd + 10 + 12 * e)
+        elif kind == 4 and values == 1:
+            value, = struct.unpack_from(order + "I", tiff, ifd + 10 + 12 * e)
+        else:
+            return 1
+        return value if 1 <= value <= 8 else 1
+    return 1
+
+
+def orient(img, o):
+    """``[H,W,C]`` array -> the picture EXIF orientation ``o`` (1 .. 8) asks for, as a view: ``[H,W,C]`` for 1 .. 4, ``[W,H,C]``
+    for 5 .. 8.  What ``PIL.ImageOps.exif_transpose`` does, and ``cv2.imdecode``; tests/helpers/orient_ref.py is its twin."""
+    if o in (2, 3, 7, 8):
+        img = img[:, ::-1]
+    if o in (3, 4, 6, 7):
+        img = img[::-1]
+    return img.transpose(1, 0, 2) if o > 4 else img
+
+
+def oriented_shape(shape, o):
+    """(H, W) of a coded picture -> (H, W) of the picture orientation ``o`` turns it into"""
+    return (shape[1], shape[0]) if o > 4 else tuple(shape)
+
+
 def _view(blob):
     try:
         return memoryview(blob).cast("B")
@@ -181,14 +255,21 @@ def huffman_row(table):
 
 class JpegDecoder:
     """Decodes batches of JPEG files on ``device``.  The quantisation and Huffman tables go to the device once per distinct
-    table, cached by the bytes of their DQT / DHT segments: a camera sends the same ones in every frame."""
+    table, cached by the bytes of their DQT / DHT segments: a camera sends the same ones in every frame.
+
+    ``orient=True``: every file is written as its EXIF orientation turns it (``exif_orientation``; what ``cv2.imdecode`` returns),
+    so ``shapes`` and the frames are the ORIENTED ones - W x H for orientations 5 .. 8 - and ``last_orientations`` says what each
+    file of the last call carried.  The turn happens in the launch that writes the pixels (jpegd_colour_oriented): no second
+    pass, no second buffer; a batch without a turned file takes the path of ``orient=False``, launch for launch."""
 
     MAX_TABLES = 1024                                    # of either kind; past it the cache starts again
     STAGES = 3                                           # pinned staging buffers in rotation
 
-    def __init__(self, device="cuda:0"):
+    def __init__(self, device="cuda:0", orient=False):
         import torch
         self.device = torch.device(device)
+        self.orient = bool(orient)
+        self.last_orientations = []                      # per blob of the last call: 1 .. 8 (all 1 without ``orient``)
         self.last_fallbacks = {}                         # frame index -> why the device did not take it (the last call's)
         self._quant, self._huff = {}, {}                 # table bytes -> row
         self._qrows, self._hrows = [], []
@@ -223,8 +304,10 @@ class JpegDecoder:
     def describe(self, blobs):
         """``parse`` of every blob -> ``(frames, headers)``: a ``FRAME`` record array (``scan_off`` still 0, ``scan_len`` the
         bytes behind SOS) and the list of headers, None where the device does not take the blob (``last_fallbacks`` says
-        why; its record stays zero, which the kernel skips)."""
+        why; its record stays zero, which the kernel skips).  With ``orient`` also ``exif_orientation`` of every blob, into
+        ``last_orientations``."""
         self.trim_tables()
+        self.last_orientations = [exif_orientation(b) for b in blobs] if self.orient else [1] * len(blobs)
         frames = np.zeros(len(blobs), FRAME)
         headers, self.last_fallbacks = [], {}
         for f, blob in enumerate(blobs):
@@ -290,7 +373,8 @@ class JpegDecoder:
           is a device ``uint8 [n,H,W,3]`` BGR batch;
         - otherwise ``frames`` is ``(arena, table)``: a device arena holding the frames back to back at 16-byte-aligned
           offsets and their frame table (include/frhip.h fr_frame_ref, what ``RaggedIngest.upload`` returns);
-        - ``shapes``: the (H, W) of every frame, None for a blob ``parse`` turned away (``last_fallbacks`` says why);
+        - ``shapes``: the (H, W) of every frame, None for a blob ``parse`` turned away (``last_fallbacks`` says why); with
+          ``orient`` the ORIENTED (H, W), which is also the shape ``out`` must have and the destinations get;
         - ``status``: device ``int32 [n]``, ``OK`` / ``BAD_STREAM`` / ``SKIPPED``; a frame that is not ``OK`` was not written.
 
         The one-shot form: every call allocates its device staging, its status words and (without ``out``) its frames, and may
@@ -305,7 +389,10 @@ class JpegDecoder:
             return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=self.device), [], torch.empty(0, dtype=torch.int32, device=self.device)
         views = [_view(b) for b in blobs]
         frames, headers = self.describe(views)
-        shapes = [None if hd is None else (hd.H, hd.W) for hd in headers]
+        coded = [(hd.H, hd.W) for hd in headers if hd is not None]
+        turns = self.last_orientations
+        turned = any(o != 1 for o, hd in zip(turns, headers) if hd is not None)
+        shapes = [None if hd is None else oriented_shape((hd.H, hd.W), o) for hd, o in zip(headers, turns)]
         real = [s for s in shapes if s is not None]
         if out is not None:
             if out.dim() != 4 or out.shape[0] != n or out.shape[3] != 3 or out.dtype != torch.uint8 or not out.is_contiguous():
@@ -329,8 +416,9 @@ class JpegDecoder:
                 arena = torch.empty(max(off, 16), dtype=torch.uint8, device=self.device)
                 refs, _ = frame_table([arena.data_ptr() + o if s else 0 for o, s in zip(offsets, shapes)],
                                       [s or (0, 0) for s in shapes])
-            # staging: the descriptors, the frame table, then the scans at 16-byte-aligned offsets
-            at = 96 * n
+            # staging: the descriptors, the frame table, the orientation words of a batch that has a turned file, then the
+            # scans at 16-byte-aligned offsets
+            at = (100 * n + 15) // 16 * 16 if turned else 96 * n
             for f, hd in enumerate(headers):
                 if hd is not None:
                     frames["scan_off"][f] = at
@@ -340,6 +428,8 @@ class JpegDecoder:
             host = slot[0].numpy()
             host[:64 * n] = frames.view(np.uint8)
             host[64 * n:96 * n] = refs
+            if turned:
+                host[96 * n:100 * n] = np.asarray(turns, "<i4").view(np.uint8)
             for f, hd in enumerate(headers):
                 if hd is not None:
                     o, ln = int(frames["scan_off"][f]), int(frames["scan_len"][f])
@@ -349,20 +439,25 @@ class JpegDecoder:
             slot[1] = torch.cuda.Event()
             slot[1].record()
             status = torch.empty(n, dtype=torch.int32, device=self.device)
-            max_h, max_w = max([s[0] for s in real] + [1]), max([s[1] for s in real] + [1])
+            max_h, max_w = max([s[0] for s in coded] + [1]), max([s[1] for s in coded] + [1])    # the launches' geometry: coded
             segments = max([hd.segments for hd in headers if hd is not None] + [1])
             qt, ht = self._tables_on_device()
             ws, ws_bytes = self._workspace(lib, n, max_h, max_w, segments)
             base = dev.data_ptr()
-            lib.fr_jpeg_decode_refs_u8(base, total, base, n, max_h, max_w, segments, _lib.ptr(qt), int(qt.shape[0]), _lib.ptr(ht),
-                                       int(ht.shape[0]), _lib.ptr(self._natural), base + 64 * n, _lib.ptr(status), _lib.ptr(ws),
-                                       ws_bytes, _lib.stream_ptr())
+            if turned:
+                lib.fr_jpeg_decode_oriented_refs_u8(base, total, base, n, max_h, max_w, segments, _lib.ptr(qt), int(qt.shape[0]),
+                                                    _lib.ptr(ht), int(ht.shape[0]), _lib.ptr(self._natural), base + 64 * n,
+                                                    base + 96 * n, _lib.ptr(status), _lib.ptr(ws), ws_bytes, _lib.stream_ptr())
+            else:
+                lib.fr_jpeg_decode_refs_u8(base, total, base, n, max_h, max_w, segments, _lib.ptr(qt), int(qt.shape[0]), _lib.ptr(ht),
+                                           int(ht.shape[0]), _lib.ptr(self._natural), base + 64 * n, _lib.ptr(status), _lib.ptr(ws),
+                                           ws_bytes, _lib.stream_ptr())
         return (out if dense is not None else (arena, dev[64 * n:96 * n])), shapes, status
 
     def decode_frames(self, blobs, fallback=True):
         """``decode_device`` and one synchronisation for the flags: one device ``uint8 [H,W,3]`` BGR tensor per blob.  A blob the
         device did not take (``last_fallbacks[f]`` says why) is decoded by ``ingest.decode_image`` and copied up when
-        ``fallback``; None for what does not decode either way."""
+        ``fallback`` (with this decoder's ``orient``); None for what does not decode either way."""
         import torch
         blobs = list(blobs)
         if not blobs:
@@ -382,7 +477,7 @@ class JpegDecoder:
                 img = None
                 if fallback:
                     from .ingest import decode_image
-                    img = decode_image(bytes(_view(blobs[f])))
+                    img = decode_image(bytes(_view(blobs[f])), orient=self.orient)
                 out.append(None if img is None else torch.from_numpy(img).to(self.device))
             off += (size + 15) // 16 * 16
         return out

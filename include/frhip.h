@@ -53,6 +53,7 @@ typedef void* fr_stream_t;
  * and for fr_jpeg_workspace / fr_jpeg_encode_u8 / fr_jpeg_encode_refs_u8 (the device JPEG encoder behind the HUD draw),
  * and for fr_jpeg_decode_workspace / fr_jpeg_decode_refs_u8 / fr_jpeg_blank_bad_refs_u8 (the device JPEG decoder in front of the
  * engine pass),
+ * and for fr_jpeg_decode_oriented_refs_u8 (the same decoder writing each frame as its EXIF orientation turns it),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -976,6 +977,19 @@ size_t fr_jpeg_decode_workspace(int nframes, int max_H, int max_W, int max_segme
 int fr_jpeg_decode_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes, int max_H, int max_W,
                            int max_segments, const int32_t* qtables, int nq, const int32_t* htables, int nh, const int32_t* natural,
                            const fr_frame_ref* refs, int32_t* status, void* workspace, size_t workspace_bytes, fr_stream_t stream);
+/* fr_jpeg_decode_refs_u8 with an EXIF orientation per frame (what cv2.imdecode applies for the reference's enrolment worker,
+ * trainingServer.py:219-221).  orient: DEVICE i32 [nframes], 1 .. 8, defined by tests/helpers/orient_ref.py: 1 as coded, 2
+ * mirrored left-right, 3 turned by 180 degrees, 4 mirrored top-bottom, 5 transposed, 6 turned clockwise, 7 transposed about the
+ * other diagonal, 8 turned counter-clockwise; a null pointer means all 1 and IS fr_jpeg_decode_refs_u8, launch for launch.
+ * refs entry f names the ORIENTED destination: H x W for 1 .. 4, W x H for 5 .. 8.  An orientation word outside 1 .. 8 or a
+ * destination of the other shape is FR_JPEGD_SKIPPED.  frames, max_H, max_W and the workspace stay in CODED sizes.  The first
+ * three launches are fr_jpeg_decode_refs_u8's; the last one writes every pixel once where its frame's orientation puts it, the
+ * transposing ones through a tile in LDS so that stores run along destination rows.  Errors as fr_jpeg_decode_refs_u8.  Added
+ * under ABI 106: no existing signature changed. */
+int fr_jpeg_decode_oriented_refs_u8(const uint8_t* data, int64_t data_bytes, const fr_jpeg_frame* frames, int nframes, int max_H,
+                                    int max_W, int max_segments, const int32_t* qtables, int nq, const int32_t* htables, int nh,
+                                    const int32_t* natural, const fr_frame_ref* refs, const int32_t* orient, int32_t* status,
+                                    void* workspace, size_t workspace_bytes, fr_stream_t stream);
 /* Behind fr_jpeg_decode_refs_u8, for destinations that are REUSED (a ring's device frames): zeroes the H * W * 3 bytes of every
  * frame whose status is FR_JPEGD_BAD_STREAM, so that a file whose scan broke off is a black frame and not the picture its
  * destination held before.  Frames with another status, and null or empty entries, are left alone.  One launch on `stream`, no
