@@ -26,7 +26,8 @@ logger = logging.getLogger(__name__)
 
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
-                 dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601", encode=None):
+                 dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601", encode=None,
+                 redact=None):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
         ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
         frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
@@ -43,6 +44,10 @@ class CameraManager:
         ``encode``: a ``jpeg.JpegEncoder``, with a ``hud`` (ValueError without one: the encoder works on the device frames the
         HUD draws on); the drawn frames are then encoded on the DEVICE and what is queued and kept per source is the JPEG
         ``bytes`` (``latest_jpeg(source)``; None for a frame the encoder turned away).  None: arrays, as ever.
+        ``redact``: a ``redact.Redactor``, with a ``hud`` (ValueError without one, by the same rule: it masks the device frames
+        the HUD draws on); faces are then masked on the DEVICE before the HUD is drawn and before anything is encoded, the
+        sources being the keys of its ``linger`` history, and ``latest_frame``, ``latest_jpeg`` and the snapshot and stream
+        routes serve masked pictures.  None: nothing is masked, as ever.
         ``pixel_format`` / ``matrix``: what the captures deliver - ``"nv12"`` / ``"i420"`` frames (``uint8 [H*3/2, W]``) need a
         ``hud``, since the host never holds a BGR picture of them to draw on (ValueError without one).
         ``"jpeg"``: the captures deliver JPEG files as ``bytes`` (an MJPEG camera); they are decoded on the device behind the ring's
@@ -77,11 +82,20 @@ class CameraManager:
         if encode is not None and hud is None:
             raise ValueError("encode needs a hud: the encoder works on the device frames the HUD draws on")
         self.encode = encode
+        if redact is not None and hud is None:
+            raise ValueError("redact needs a hud: the redactor masks the device frames the HUD draws on")
+        self.redact = redact
         self._jpeg = {}                        # source -> (count of its frames so far, the latest JPEG bytes) (encode only)
         self._jpeg_new = threading.Condition(self._latest_lock)
 
     def _forget(self, source):
-        """A source that is gone: its gate slot and its track slot are freed and its held results dropped."""
+        """A source that is gone: its gate slot and its track slot are freed, its held results and its redaction history
+        dropped."""
+        if self.redact is not None:
+            try:
+                self.redact.forget(source)
+            except Exception as e:
+                logger.error("Camera %s: the redactor did not forget it: %s", source, e)
         if self.tracks is not None:
             try:
                 self.tracks.forget(source)
@@ -197,7 +211,8 @@ class CameraManager:
         return_results=True, held=self._held)`` with the same arguments (and the manager's pixel format when it is YUV): the frames
         it returns - drawn on the device, an unchanged frame with its held results - are what is queued, and ``annotate`` is not
         called.  With ``encode`` too the call also gets ``encode=``, and what it returns and what is queued is one JPEG ``bytes``
-        per frame, kept per source for ``latest_jpeg``."""
+        per frame, kept per source for ``latest_jpeg``.  With ``redact`` the call also gets ``redact=`` and the frames' sources as
+        ``redact_keys=``."""
         mixed_ids = isinstance(company_id, (list, tuple))
         if mixed_ids and len(company_id) != len(batch):
             raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
@@ -221,6 +236,8 @@ class CameraManager:
                     gated = dict(gated, pixel_format=self.pixel_format, matrix=self.matrix)
                 if self.encode is not None:
                     gated = dict(gated, encode=self.encode)
+                if self.redact is not None:
+                    gated = dict(gated, redact=self.redact, redact_keys=[batch[k][0] for k in ks])
                 drawn, res = self.processor.recognize_faces_batch([batch[k][1] for k in ks], ids[0] if one else ids, self.hud,
                                                                   return_results=True, held=self._held, **gated)
             for j, k in enumerate(ks):

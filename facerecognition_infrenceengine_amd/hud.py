@@ -160,7 +160,36 @@ class Hud:
         self._tables[key] = dev_tab
         return dev_tab
 
-    def draw(self, frames, results_per_frame, shapes=None):
+    def _frames(self, frames, shapes):
+        """``frames`` as ``draw`` takes them -> (arena, table or None, shapes, device)"""
+        import torch
+        if isinstance(frames, (tuple, list)):
+            arena, table = frames
+            if shapes is None:
+                raise ValueError("a frame table needs shapes: the (H, W) of its frames")
+            return arena, table, [(int(h), int(w)) for h, w in shapes], arena.device
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
+            raise ValueError("frames must be a contiguous device uint8 [n,H,W,3]")
+        return frames, None, [(int(frames.shape[1]), int(frames.shape[2]))] * int(frames.shape[0]), frames.device
+
+    def canvas(self, frames, shapes=None):
+        """The first step of ``draw`` on its own: with ``out_size=(w, h)`` the frames resized into a new ``uint8 [n,h,w,3]``
+        (fr_letterbox_u8: top-left, zero padded) on the current stream; None without ``out_size`` or without frames.  What it
+        returns goes to ``draw(..., canvas=...)``, so that something else - the redaction - can work on the previews between
+        the two launches."""
+        import torch
+        from . import _lib
+        arena, table, shapes, device = self._frames(frames, shapes)
+        if self.out_size is None or not shapes:
+            return None
+        n, (w, h) = len(shapes), self.out_size
+        with torch.cuda.device(device):
+            refs = self._preview_table(arena, table, shapes)
+            canvas = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
+            _lib.load().fr_letterbox_u8(_lib.ptr(refs), n, _lib.ptr(canvas), h, w, _lib.stream_ptr())
+        return canvas
+
+    def draw(self, frames, results_per_frame, shapes=None, canvas=None):
         """Draws the HUD of every frame's results, on the current stream, and returns the drawn frames on the device.
 
         ``frames``: a device ``uint8 [n,H,W,3]`` BGR batch, or ``(arena, table)`` - a device arena holding frames of differing
@@ -170,36 +199,24 @@ class Hud:
 
         Without ``out_size`` the frames are drawn IN PLACE and returned (the batch tensor, or the arena).  With
         ``out_size=(w, h)`` the frames are first resized into a new ``uint8 [n,h,w,3]`` (fr_letterbox_u8: top-left, zero
-        padded), the HUD is drawn on that, boxes mapped by ``records``, and the frames given stay as they were."""
+        padded), the HUD is drawn on that, boxes mapped by ``records``, and the frames given stay as they were.  ``canvas``:
+        the previews ``canvas(frames, shapes)`` made of these frames; they are drawn on instead of a resize of their own."""
         import torch
         from . import _lib
         lib = _lib.load()
-        ragged = isinstance(frames, (tuple, list))
-        if ragged:
-            arena, table = frames
-            if shapes is None:
-                raise ValueError("a frame table needs shapes: the (H, W) of its frames")
-            shapes = [(int(h), int(w)) for h, w in shapes]
-            device = arena.device
-        else:
-            if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
-                raise ValueError("frames must be a contiguous device uint8 [n,H,W,3]")
-            arena, table = frames, None
-            shapes = [(int(frames.shape[1]), int(frames.shape[2]))] * int(frames.shape[0])
-            device = frames.device
+        arena, table, shapes, device = self._frames(frames, shapes)
+        ragged = table is not None
         n = len(shapes)
         if len(results_per_frame) != n:
             raise ValueError(f"one results entry per frame: {n} frames, {len(results_per_frame)} entries")
         if n == 0:
             return arena
+        if canvas is not None and (self.out_size is None or tuple(canvas.shape) != (n, self.out_size[1], self.out_size[0], 3)):
+            raise ValueError("canvas must be what canvas(frames, shapes) returns for these frames")
         with torch.cuda.device(device):
             stream = _lib.stream_ptr()
-            canvas = None
-            if self.out_size is not None:
-                w, h = self.out_size
-                refs = self._preview_table(arena, table, shapes)
-                canvas = torch.empty((n, h, w, 3), dtype=torch.uint8, device=device)
-                lib.fr_letterbox_u8(_lib.ptr(refs), n, _lib.ptr(canvas), h, w, stream)
+            if self.out_size is not None and canvas is None:
+                canvas = self.canvas(frames, shapes)
             if not any(isinstance(r, (list, tuple)) and len(r) for r in results_per_frame):
                 return canvas if canvas is not None else arena
             buf, cap, at_faces, at_text = self.pack(results_per_frame, shapes)

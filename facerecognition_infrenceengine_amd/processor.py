@@ -604,7 +604,8 @@ class FaceRecognitionProcessor:
         dec = matcher.decide_device(idx, score, self.recognition_threshold)
         return _SlotFaces(r, n, idx, score, tracks, dec).frames([(matcher.ids, metadata)] * n, keep, len(frames))
 
-    def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, encode=None, **kw):
+    def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, encode=None, redact=None,
+                              redact_keys=None, **kw):
         """The reference's ``recognize_faces`` for a batch, with the HUD drawn on the DEVICE (``hud``: a ``hud.Hud``): runs
         exactly what ``recognize_batch(frames, company_id, **kw)`` runs (``kw``: ``pixel_format``, ``matrix``, ``gate``,
         ``camera_ids``, ``tracks``, ``quality``), then draws every frame's results into the ring's device frames - the BGR frames
@@ -622,7 +623,15 @@ class FaceRecognitionProcessor:
         ``encode`` (a ``jpeg.JpegEncoder``): the drawn frames - full size, previews, or a det_size engine's arena - are encoded on
         the device while the turn is still held, and what crosses the link is the offsets and then the JPEG stream.  The call
         then returns one ``bytes`` per frame in place of the array (None, with a logged warning, for a frame whose coded rows
-        overflowed the encoder's budget).  None: the arrays, as ever."""
+        overflowed the encoder's budget).  None: the arrays, as ever.
+
+        ``redact`` (a ``redact.Redactor``): faces are masked on the device before anything is drawn or encoded.
+        The engine pass sees the unmasked pixels; behind it the order is: resize to previews (``hud.out_size``), REDACT, draw the
+        HUD, encode or copy out - so the HUD lies on top of the mosaic and no unmasked picture of a masked face crosses the
+        link.  The regions come from this call's results, ``held`` standing in for ``UNCHANGED`` frames as for the HUD; a frame
+        nothing ran for (no gallery, ``UNCHANGED`` with nothing held) is masked as a whole unless the redactor says ``"pass"``.
+        ``redact_keys``: one id per frame for the redactor's ``linger`` history; defaults to ``camera_ids``.  None: nothing is
+        masked, and the call runs what it ran before."""
         import torch
         if hud is None:
             raise ValueError("recognize_faces_batch draws with a hud.Hud; without one call recognize_batch")
@@ -645,7 +654,17 @@ class FaceRecognitionProcessor:
                 with torch.cuda.device(det.device):
                     stream = torch.cuda.current_stream(det.device)
                     stream.wait_event(turn.ready)
-                    drawn = hud.draw(turn.dev if turn.table is None else (turn.dev, turn.table), per_frame, shapes=shapes)
+                    src = turn.dev if turn.table is None else (turn.dev, turn.table)
+                    if redact is None:
+                        drawn = hud.draw(src, per_frame, shapes=shapes)
+                    else:
+                        keys = redact_keys if redact_keys is not None else kw.get("camera_ids")
+                        canvas = hud.canvas(src, shapes)                  # the previews, when the HUD draws on previews
+                        if canvas is None:
+                            redact.apply(src, per_frame, shapes=shapes, keys=keys)
+                        else:
+                            redact.apply(canvas, per_frame, shapes=shapes, out_hws=[hud.out_hw(hw) for hw in shapes], keys=keys)
+                        drawn = hud.draw(src, per_frame, shapes=shapes, canvas=canvas)
                     if encode is not None:
                         coded = encode.encode_device(drawn if drawn.dim() == 4 else (drawn, turn.table), shapes=shapes)
                         turn.ring.release(turn.turn)          # behind the queued encoder: it is the last reader of the slot

@@ -54,6 +54,7 @@ typedef void* fr_stream_t;
  * and for fr_jpeg_decode_workspace / fr_jpeg_decode_refs_u8 / fr_jpeg_blank_bad_refs_u8 (the device JPEG decoder in front of the
  * engine pass),
  * and for fr_jpeg_decode_oriented_refs_u8 (the same decoder writing each frame as its EXIF orientation turns it),
+ * and for fr_redact_u8 / fr_redact_refs_u8 (face redaction: regions pixelated or filled in place in front of the HUD draw),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -882,6 +883,35 @@ int fr_hud_draw_u8(uint8_t* frames, int N, int H, int W, const int32_t* counts, 
                    const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
 int fr_hud_draw_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* counts, int cap, const int32_t* faces,
                         const uint8_t* text, int max_chars, const uint8_t* font, int scale, fr_stream_t stream);
+
+/* Face redaction: rectangles of BGR u8 frames on the device pixelated or filled IN PLACE, behind the engine pass and in front of
+ * fr_hud_draw_u8 and the JPEG encoder, so that no unmasked picture of a masked face leaves the device.  The picture is defined by
+ * tests/helpers/redact_ref.py and reproduced byte for byte (32-bit integer arithmetic only):
+ *   cells   block x block, anchored at the picture's origin: pixel (x, y) lies in cell (x / block, y / block); the cells of the
+ *           last column and row are cut at W and H, so a cell has n = cw ch <= block^2 pixels
+ *   held    a pixel is held when at least one of its frame's regions contains it; a region is an inclusive rectangle
+ *           x1 y1 x2 y2, ordered by the host, anywhere (negative, past the picture; clamped to +-2^20)
+ *   mode 0  pixelate: a held pixel takes, per channel, (S + n / 2) / n, S the sum of the ORIGINAL bytes of its whole cell - the
+ *           cell's pixels that no region holds included
+ *   mode 1  fill: a held pixel takes the colour bgr (B in bits 0 .. 7, G in 8 .. 15, R in 16 .. 23)
+ * A pixel no region holds is never written.  The grid does not depend on the regions: overlapping regions, a region listed twice
+ * and any order of the list give the bytes of the union.
+ *
+ * counts i32 [n]; regions i32 [n][cap][4].  Slots j >= counts[f] are never read (counts is clamped to 0 .. cap).
+ * One launch on the caller's stream, nothing allocated, nothing synchronised, no global atomics.  Work is cut by cell: a tile is
+ * block rows x block * (64 / block) pixels, owned by one workgroup that reads all of it before it stores any of it and reads
+ * nothing else; a tile that no region meets is neither read nor written.  Any byte alignment of the frames.
+ *
+ * fr_redact_u8: a uniform batch u8 [N,H,W,3].  fr_redact_refs_u8: a DEVICE frame table (data - written here, the const of the
+ * struct notwithstanding -, H and W are read); an entry with a non-positive side, of 2 GiB or more or with a null pointer is
+ * skipped as a whole.  Refused before any launch: more than 65535 frames or a negative count of them, cap outside
+ * 1 .. FR_REDACT_MAX_CAP, block outside 2 .. 64, mode other than 0 / 1, non-positive H or W, a frame of 2 GiB or more, a null
+ * pointer with n > 0.  n == 0 returns FR_OK and reads nothing.  Added under ABI 106: no existing signature changed. */
+#define FR_REDACT_MAX_CAP 64
+int fr_redact_u8(uint8_t* frames, int N, int H, int W, const int32_t* counts, int cap, const int32_t* regions,
+                 int block, int mode, uint32_t bgr, fr_stream_t stream);
+int fr_redact_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* counts, int cap, const int32_t* regions,
+                      int block, int mode, uint32_t bgr, fr_stream_t stream);
 
 /* Device JPEG encoder: BGR u8 frames on the device (the drawn frames of the HUD) -> baseline JPEG files, so that a few hundred
  * KB per 1080p frame cross the link instead of 6.2 MB (the reference shows raw frames with cv2.imshow, one process per camera:
