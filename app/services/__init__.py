@@ -10,6 +10,7 @@ from facerecognition_infrenceengine_amd.tracks import FaceTracks  # noqa: F401
 from facerecognition_infrenceengine_amd.quality import FaceQuality  # noqa: F401
 from facerecognition_infrenceengine_amd.hud import Hud  # noqa: F401
 from facerecognition_infrenceengine_amd.redact import Redactor  # noqa: F401
+from facerecognition_infrenceengine_amd.chips import FaceChips  # noqa: F401
 from facerecognition_infrenceengine_amd.jpeg import JpegEncoder  # noqa: F401
 from facerecognition_infrenceengine_amd.processor import UNCHANGED  # noqa: F401
 from facerecognition_infrenceengine_amd.server import create_app  # noqa: F401

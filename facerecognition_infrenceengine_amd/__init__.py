@@ -7,6 +7,7 @@ from .tracks import FaceTracks  # noqa: E402,F401
 from .quality import FaceQuality  # noqa: E402,F401
 from .hud import Hud  # noqa: E402,F401
 from .redact import Redactor  # noqa: E402,F401
+from .chips import FaceChips  # noqa: E402,F401
 from .jpeg import JpegEncoder  # noqa: E402,F401
 from .jpeg_decode import JpegDecoder  # noqa: E402,F401
 from .gallery import DuplicateOverflowError, DuplicatePairs, GalleryMatcher  # noqa: E402,F401

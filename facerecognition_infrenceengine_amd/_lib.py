@@ -155,6 +155,8 @@ SIGNATURES = {
     "fr_hud_draw_refs_u8": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _P]),
     "fr_redact_u8": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P]),           # bgr: uint32_t, 24 bits used
     "fr_redact_refs_u8": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    "fr_face_chips_u8": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _P, _P]),          # bgr_fill: uint32_t, 24 bits used
+    "fr_face_chips_refs_u8": (_I, [_P, _I, _P, _I, _I, _I, _P, _P]),
     "fr_jpeg_workspace": (_Z, [_I, _I, _I, _I]),
     "fr_jpeg_encode_u8": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _L, _P, _P, _P, _Z, _P]),
     "fr_jpeg_encode_refs_u8": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _L, _P, _P, _P, _Z, _P]),

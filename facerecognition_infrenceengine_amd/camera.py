@@ -27,7 +27,7 @@ logger = logging.getLogger(__name__)
 class CameraManager:
     def __init__(self, embedding_manager, processor=None, capture_factory=None, max_wait_s=0.005, reopen_after=20,
                  dead_after=200, gate=None, tracks=None, quality=None, hud=None, pixel_format="bgr", matrix="bt601", encode=None,
-                 redact=None):
+                 redact=None, chips=None):
         """``processor``: a ``FaceRecognitionProcessor`` (built lazily from ``embedding_manager`` when None).
         ``gate``: an ``activity.ActivityGate``; the engine then runs only for the frames that differ from the last processed
         frame of their source (the sources are its camera ids), and a frame of an unchanged scene is annotated with the
@@ -48,6 +48,10 @@ class CameraManager:
         the HUD draws on); faces are then masked on the DEVICE before the HUD is drawn and before anything is encoded, the
         sources being the keys of its ``linger`` history, and ``latest_frame``, ``latest_jpeg`` and the snapshot and stream
         routes serve masked pictures.  None: nothing is masked, as ever.
+        ``chips``: a ``chips.FaceChips``, with or without a ``hud``; the processor call then gets ``chips=`` and every face dict it
+        returns carries ``"chip"`` - the face's thumbnail, cut on the DEVICE from the full-size, unmasked, undrawn frame (a face
+        the ``redact`` masks has none unless the object says ``masked=True``).  Each source's latest face dicts are kept:
+        ``latest_faces(source)``, and the ``GET /api/camera/faces`` route.  None: no chips, as ever.
         ``pixel_format`` / ``matrix``: what the captures deliver - ``"nv12"`` / ``"i420"`` frames (``uint8 [H*3/2, W]``) need a
         ``hud``, since the host never holds a BGR picture of them to draw on (ValueError without one).
         ``"jpeg"``: the captures deliver JPEG files as ``bytes`` (an MJPEG camera); they are decoded on the device behind the ring's
@@ -85,6 +89,8 @@ class CameraManager:
         if redact is not None and hud is None:
             raise ValueError("redact needs a hud: the redactor masks the device frames the HUD draws on")
         self.redact = redact
+        self.chips = chips
+        self._faces = {}                       # source -> the face dicts of its last processed frame, with their chips (chips only)
         self._jpeg = {}                        # source -> (count of its frames so far, the latest JPEG bytes) (encode only)
         self._jpeg_new = threading.Condition(self._latest_lock)
 
@@ -101,6 +107,9 @@ class CameraManager:
                 self.tracks.forget(source)
             except Exception as e:
                 logger.error("Camera %s: the tracks did not forget it: %s", source, e)
+        if self.chips is not None:
+            with self._latest_lock:
+                self._faces.pop(source, None)
         if self.gate is not None:
             self._held.pop(source, None)
             try:
@@ -212,7 +221,9 @@ class CameraManager:
         it returns - drawn on the device, an unchanged frame with its held results - are what is queued, and ``annotate`` is not
         called.  With ``encode`` too the call also gets ``encode=``, and what it returns and what is queued is one JPEG ``bytes``
         per frame, kept per source for ``latest_jpeg``.  With ``redact`` the call also gets ``redact=`` and the frames' sources as
-        ``redact_keys=``."""
+        ``redact_keys=``.  With ``chips`` the call - either of the two - also gets ``chips=``, and the face dicts of every frame
+        the engine ran for are kept per source for ``latest_faces``; a frame answered ``UNCHANGED`` leaves its source's as they
+        are."""
         mixed_ids = isinstance(company_id, (list, tuple))
         if mixed_ids and len(company_id) != len(batch):
             raise ValueError(f"one company id per frame: {len(batch)} frames, {len(company_id)} ids")
@@ -229,6 +240,8 @@ class CameraManager:
                 gated = dict(gated, tracks=self.tracks, camera_ids=[batch[k][0] for k in ks])
             if self.quality is not None:
                 gated = dict(gated, quality=self.quality)
+            if self.chips is not None:
+                gated = dict(gated, chips=self.chips)
             if self.hud is None:
                 res = self.processor.recognize_batch([batch[k][1] for k in ks], ids[0] if one else ids, **gated)
             else:                                     # the same call, then the HUD drawn on the device frames
@@ -244,6 +257,11 @@ class CameraManager:
                 results[k] = None if res is None else res[j]
                 if self.hud is not None:
                     pictures[k] = drawn[j]
+        if self.chips is not None:                    # before held results stand in: those faces' chips are already kept
+            with self._latest_lock:
+                for k, (source, _) in enumerate(batch):
+                    if isinstance(results[k], list):
+                        self._faces[source] = results[k]
         if self.gate is not None:
             from .processor import UNCHANGED
             for k, (source, _) in enumerate(batch):
@@ -341,10 +359,16 @@ class CameraManager:
             count, data = self._jpeg.get(source, (0, None))
             return (count, data) if count > after else (after, None)
 
+    def latest_faces(self, source):
+        """The face dicts of the last frame of ``source`` the engine ran for, each with its ``"chip"`` (None before the first
+        one, and always without ``chips``)."""
+        with self._latest_lock:
+            return self._faces.get(source)
+
     def source_named(self, text):
         """the source whose ``str()`` is ``text`` - how a route names one (sources are ints or strings) -, or None"""
         with self._latest_lock:
-            known = list(self.company_of) + list(self._jpeg) + list(self.latest)
+            known = list(self.company_of) + list(self._jpeg) + list(self.latest) + list(self._faces)
         return next((s for s in known if str(s) == str(text)), None)
 
     def stop_cameras(self):

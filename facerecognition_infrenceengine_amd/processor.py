@@ -508,22 +508,26 @@ class FaceRecognitionProcessor:
         return _SlotFaces(got.r, got.n, got.idx, got.score, tracks, dec).frames(got.galleries, got.keep, len(frames), min_score)
 
     def identify_batch(self, frames, company_id, k=5, min_score=None, pixel_format="bgr", matrix="bt601", gate=None,
-                       camera_ids=None, tracks=None, quality=None):
+                       camera_ids=None, tracks=None, quality=None, chips=None):
         """``identify`` for a batch of frames (sizes as ``recognize_batch``): ``company_id`` is one id for all frames or a
         list / tuple with one id per frame.  ONE engine pass, one grouped top-K scan in which every frame is ranked
         through its own company's view, one host synchronisation.  Returns a list with, per frame, what ``identify``
         returns for it - None for a frame whose company has no gallery.  The grouped scan is the exact f32 scan
         whatever ``scan`` the manager was built with: the bits of ``identify``'s exact path.  ``pixel_format`` / ``matrix``,
         ``gate`` / ``tracks`` / ``camera_ids`` / ``quality``: as ``recognize_batch``; a face judged unfit has no candidates - under tracks that
-        judge, a REJECTED face has none and a carried one is ranked on its held row."""
+        judge, a REJECTED face has none and a carried one is ranked on its held row.  ``chips``: as ``recognize_batch`` (a face
+        dict here has no ``person_info``: to a ``who`` given as types every face counts as unknown)."""
         if not 1 <= int(k) <= 16:
             raise ValueError(f"k must be 1..16 (got {k})")
         camera_ids = _check_gate(gate, camera_ids, len(frames), tracks, quality)
         ids = list(company_id) if isinstance(company_id, (list, tuple)) else [company_id] * len(frames)
-        return self._serve_mixed(frames, ids, int(k), min_score, pixel_format, matrix, gate, camera_ids, tracks, quality)
+        if chips is None:
+            return self._serve_mixed(frames, ids, int(k), min_score, pixel_format, matrix, gate, camera_ids, tracks, quality)
+        return self._with_chips(chips, lambda hold: self._serve_mixed(frames, ids, int(k), min_score, pixel_format, matrix, gate,
+                                                                      camera_ids, tracks, quality, hold))
 
     def recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
-                        quality=None):
+                        quality=None, chips=None):
         """Batch form for the camera batcher (``camera.CameraManager``): ``frames`` = list of BGR uint8 frames (one per
         camera), of one size - or of any sizes when the engine has a ``det_size`` (``accepts_mixed_sizes``; ``bbox`` is
         in each frame's own pixels either way).  ONE pass of the sync-free slot pipeline over the whole batch (pinned staging ->
@@ -580,8 +584,39 @@ class FaceRecognitionProcessor:
         with its track's template - the unit mean of the track's last K embedded shots that agreed with one another - instead
         of this frame's row alone; a shot that does not agree with the template restarts it and is scanned as it is.  Each face
         dict gains ``"template_shots"`` (the shots behind the scanned row, 0: the face's own row), and ``tracks.stats`` counts
-        ``"joined"`` and ``"restarted"`` shots.  The same holds for ``identify_batch`` and for mixed-company batches."""
-        return self._recognize_batch(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks, quality)
+        ``"joined"`` and ``"restarted"`` shots.  The same holds for ``identify_batch`` and for mixed-company batches.
+
+        ``chips`` (a ``chips.FaceChips``): the call keeps its ring turn, and once the results are on the host one launch cuts a
+        square around every face the object selects out of the ring's FULL-SIZE device frames - BGR as uploaded, converted from
+        YUV or decoded from JPEG - and resamples it to a thumbnail; every face dict gains ``"chip"``: JPEG
+        ``bytes`` encoded on the device, a ``uint8 [S,S,3]`` array with ``encode=None``, None for a face that is not selected.
+        Every other key is what the call returns without chips.  A frame answered ``UNCHANGED`` or None yields no chips.  Calls
+        with chips are serialised per processor, with the calls that draw a HUD; while one holds its turn, no more than one
+        further batch of the same shape should be started on this processor from other threads (the ring is two slots deep).
+        None: the call runs the code it ran before."""
+        if chips is None:
+            return self._recognize_batch(frames, company_id, pixel_format, matrix, gate, camera_ids, tracks, quality)
+        return self._with_chips(chips, lambda hold: self._recognize_batch(frames, company_id, pixel_format, matrix, gate,
+                                                                          camera_ids, tracks, quality, hold))
+
+    def _with_chips(self, chips, call):
+        """``call(hold)`` - an engine pass that leaves its ring turn in ``hold`` - and, behind it, the chips of its results cut
+        from the ring's device frames; the turn is released when the chips have been read back."""
+        import torch
+        lock = self.__dict__.setdefault("_hud_lock", threading.Lock())
+        hold = []
+        with lock:
+            try:
+                results = call(hold)
+                if hold and isinstance(results, list):
+                    turn, det = hold[0], self.face_detector
+                    with torch.cuda.device(det.device):
+                        torch.cuda.current_stream(det.device).wait_event(turn.ready)
+                        chips.cut(turn.dev if turn.table is None else (turn.dev, turn.table), results, n=len(turn.arr))
+            finally:
+                for t in hold:
+                    t.ring.release(t.turn)
+        return results
 
     def _recognize_batch(self, frames, company_id, pixel_format="bgr", matrix="bt601", gate=None, camera_ids=None, tracks=None,
                          quality=None, hold=None):
@@ -605,7 +640,7 @@ class FaceRecognitionProcessor:
         return _SlotFaces(r, n, idx, score, tracks, dec).frames([(matcher.ids, metadata)] * n, keep, len(frames))
 
     def recognize_faces_batch(self, frames, company_id, hud, return_results=False, held=None, encode=None, redact=None,
-                              redact_keys=None, **kw):
+                              redact_keys=None, chips=None, **kw):
         """The reference's ``recognize_faces`` for a batch, with the HUD drawn on the DEVICE (``hud``: a ``hud.Hud``): runs
         exactly what ``recognize_batch(frames, company_id, **kw)`` runs (``kw``: ``pixel_format``, ``matrix``, ``gate``,
         ``camera_ids``, ``tracks``, ``quality``), then draws every frame's results into the ring's device frames - the BGR frames
@@ -631,7 +666,13 @@ class FaceRecognitionProcessor:
         link.  The regions come from this call's results, ``held`` standing in for ``UNCHANGED`` frames as for the HUD; a frame
         nothing ran for (no gallery, ``UNCHANGED`` with nothing held) is masked as a whole unless the redactor says ``"pass"``.
         ``redact_keys``: one id per frame for the redactor's ``linger`` history; defaults to ``camera_ids``.  None: nothing is
-        masked, and the call runs what it ran before."""
+        masked, and the call runs what it ran before.
+
+        ``chips`` (a ``chips.FaceChips``): as ``recognize_batch``; the chips are cut from the full-size frames strictly BEFORE the
+        preview resize, the redactor and the HUD draw - the order on the stream is engine pass, chips, previews, redact, HUD,
+        frame encoder - so they show the undrawn, unmasked pixels, and they are read back behind the pictures.  A face this
+        call's ``redact`` masks gets ``"chip": None`` unless the object says ``masked=True``.  Only this call's own results are
+        chipped: ``held`` results are drawn, not chipped again."""
         import torch
         if hud is None:
             raise ValueError("recognize_faces_batch draws with a hud.Hud; without one call recognize_batch")
@@ -655,6 +696,9 @@ class FaceRecognitionProcessor:
                     stream = torch.cuda.current_stream(det.device)
                     stream.wait_event(turn.ready)
                     src = turn.dev if turn.table is None else (turn.dev, turn.table)
+                    pending = None
+                    if chips is not None and isinstance(results, list):   # in front of everything that writes the frames
+                        pending = chips.begin(src, results, n=len(turn.arr), redact=redact)
                     if redact is None:
                         drawn = hud.draw(src, per_frame, shapes=shapes)
                     else:
@@ -670,12 +714,16 @@ class FaceRecognitionProcessor:
                         turn.ring.release(turn.turn)          # behind the queued encoder: it is the last reader of the slot
                         hold.clear()
                         out = encode.read_back(*coded)
+                        if pending is not None:
+                            chips.finish(pending)
                         return (out, results) if return_results else out
                     stage = self._hud_stage(tuple(drawn.shape))
                     stage.copy_(drawn, non_blocking=True)
                     turn.ring.release(turn.turn)              # behind the queued copy: the next upload into the slot waits
                     hold.clear()
                     stream.synchronize()
+                    if pending is not None:
+                        chips.finish(pending)
                 host = stage.numpy()
                 if drawn.dim() == 4:
                     out = [host[i].copy() for i in range(len(shapes))]
@@ -806,7 +854,7 @@ class CameraProcessor:
                                              for i in range(len(banks))]
         return list(zip(banks, masks))
 
-    def process_batch(self, frames, camera_ids, quality=None):
+    def process_batch(self, frames, camera_ids, quality=None, chips=None):
         """Batch form of ``process_frame``: ``frames`` = list of BGR uint8 frames (of one size, or of any sizes when the
         engine has a ``det_size``), ``camera_ids`` = their cameras.  ONE pass of the slot pipeline over the batch,
         whole-gallery scan, the 0.45 / 0.35 decision and - with ``unknown_clusters`` - the clustering of the unknown
@@ -822,7 +870,30 @@ class CameraProcessor:
         ``quality`` (a ``quality.FaceQuality``): the engine pass judges every aligned face and embeds the fit ones only.  A
         rejected face is taken out of the unknown mask before ``assign_batch`` - it opens and joins no cluster - and reaches
         neither ``process_detection`` nor the unknown fan-out; it still counts under ``"faces"``, and every stats dict gains
-        ``"low_quality"``, the number of such faces of the frame."""
+        ``"low_quality"``, the number of such faces of the frame.
+
+        ``chips`` (a ``chips.FaceChips``): the call keeps its ring turn and, with the decisions on the host, cuts a thumbnail of
+        every face the object selects out of the ring's full-size device frames.  ``who`` is given the dict
+        ``{"bbox", "person_info": metadata | {"type": "unknown"}, "recognition_score", "cluster", "is_new"}`` of a face that
+        reaches the manager (``cluster`` None without one), so ``who=lambda r: r.get("is_new")`` gives one thumbnail per new
+        unknown cluster.  Each stats dict gains ``"chips": [(face index, chip), ...]``, and a manager that defines
+        ``process_face_chip(camera_id, timestamp, person_id, cluster, bbox, chip)`` gets that call right behind the face's
+        detection call (``person_id`` None for an unknown, ``cluster`` None without one); every other call is unchanged.  A face
+        rejected by ``quality`` gets no chip.  Calls with chips are serialised per processor; while one holds its turn, no more
+        than one further batch of the same shape should be started on this processor from other threads (the ring is two slots
+        deep).  None: the call runs the code it ran before."""
+        if chips is None:
+            return self._process_batch(frames, camera_ids, quality)
+        hold = []
+        with self.__dict__.setdefault("_hud_lock", threading.Lock()):
+            try:
+                return self._process_batch(frames, camera_ids, quality, chips, hold)
+            finally:
+                for t in hold:
+                    t.ring.release(t.turn)
+
+    def _process_batch(self, frames, camera_ids, quality=None, chips=None, hold=None):
+        """``process_batch``; with ``chips``, ``hold`` (a list) receives the ring turn, which the caller releases."""
         import torch
         from . import _lib
         if self.face_detector is None:
@@ -832,14 +903,18 @@ class CameraProcessor:
             raise ValueError(f"{n} frames but {len(camera_ids)} camera ids")
         clustered = self.unknown_clusters is not None
         stats = [dict({"faces": 0, "recognized": 0, "unknown": 0}, **({"unknown_clusters": []} if clustered else {}),
-                      **({"low_quality": 0} if quality is not None else {})) for _ in range(n)]
+                      **({"low_quality": 0} if quality is not None else {}), **({"chips": []} if chips is not None else {}))
+                 for _ in range(n)]
         matcher, metadata = self.embedding_manager.get_matcher_for_company(None)
         if len(matcher) == 0 or n == 0:
             return stats
         timestamp = datetime.utcnow()
         try:
             det = self.face_detector
-            n, r = _detect_embed_batch(self, det, frames, quality=quality)
+            if chips is None:
+                n, r = _detect_embed_batch(self, det, frames, quality=quality)
+            else:
+                n, r, _ = _detect_embed_batch_gated(self, det, frames, quality=quality, hold=hold)
             E = r["normed_embedding"]
             matcher, metadata, idx, score = _match_fresh(self.embedding_manager, None, matcher, metadata, E)
             dec = matcher.decide_device(idx, score, self.recognition_threshold, self.unknown_threshold)
@@ -879,6 +954,29 @@ class CameraProcessor:
             if not use_cb or unbanked:                                                # the embeddings travel as well
                 e = (E if qn is None else qn).cpu().numpy()
                 q = e / np.linalg.norm(e, axis=1, keepdims=True) if qn is None else e
+            chip_of = {}                                                              # slot -> chip (chips only)
+            if chips is not None:
+                chosen, slots = [[] for _ in range(n)], [[] for _ in range(n)]
+                for f in range(n):
+                    for s in range(f * cap, f * cap + int(counts[f])):
+                        if (verdict_h is not None and verdict_h[s] != 0) or dec_h[s] not in (0, 1):
+                            continue                                                  # no call reaches the manager for it
+                        cl = int(trip_h[0, s]) if trip_h is not None and dec_h[s] == 0 else -1
+                        chosen[f].append({"bbox": bb[s].tolist(),
+                                          "person_info": metadata[matcher.ids[idx_h[s]]] if dec_h[s] == 1 else {"type": "unknown"},
+                                          "recognition_score": float(score_h[s]), "cluster": cl if cl >= 0 else None,
+                                          "is_new": bool(trip_h[1, s]) if cl >= 0 else False})
+                        slots[f].append(s)
+                turn = hold[0]
+                with torch.cuda.device(det.device):
+                    torch.cuda.current_stream(det.device).wait_event(turn.ready)
+                    chips.cut(turn.dev if turn.table is None else (turn.dev, turn.table), chosen, n=len(turn.arr))
+                for f in range(n):
+                    for d, s in zip(chosen[f], slots[f]):
+                        if d["chip"] is not None:
+                            chip_of[s] = d["chip"]
+                            stats[f]["chips"].append((s - f * cap, d["chip"]))
+            chip_cb = chips is not None and hasattr(self.manager, "process_face_chip")
             refused = 0
             for f in range(n):
                 st, cam = stats[f], camera_ids[f]
@@ -889,6 +987,8 @@ class CameraProcessor:
                     elif dec_h[s] == 1:
                         pid = matcher.ids[idx_h[s]]
                         self.manager.process_detection(pid, metadata[pid], cam, timestamp, float(score_h[s]))
+                        if chip_cb and s in chip_of:
+                            self.manager.process_face_chip(cam, timestamp, pid, None, bb[s].tolist(), chip_of[s])
                         st["recognized"] += 1
                     elif dec_h[s] == 0:
                         cl = int(trip_h[0, s]) if trip_h is not None else -1
@@ -903,6 +1003,8 @@ class CameraProcessor:
                             if q is None:                 # only a refused row needs its embedding here: a second, rare copy
                                 q = qn.cpu().numpy()
                             self.manager.process_unknown_detection(cam, timestamp, q[s], bb[s].tolist())
+                        if chip_cb and s in chip_of:
+                            self.manager.process_face_chip(cam, timestamp, None, cl if cl >= 0 else None, bb[s].tolist(), chip_of[s])
                         st["unknown"] += 1
             if refused:
                 logger.warning("Unknown-person clusters full: %d faces of this batch were not clustered", refused)

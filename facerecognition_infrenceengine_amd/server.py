@@ -2,7 +2,9 @@
 status codes, as an app factory with the managers injected (the reference builds module-level
 singletons that connect to a database at import: :682-683) - and two routes the reference has no
 counterpart for (it shows its frames with cv2.imshow, :648-667): the latest processed frame of a
-camera as a JPEG, and the frames as they come as MJPEG, for a manager with a ``jpeg.JpegEncoder``."""
+camera as a JPEG, and the frames as they come as MJPEG, for a manager with a ``jpeg.JpegEncoder`` - and the faces of that frame
+with their thumbnails, for a manager with ``chips.FaceChips``."""
+import base64
 from threading import Thread
 
 
@@ -83,5 +85,23 @@ def create_app(embedding_manager, camera_manager):
                 yield (b"--frame\r\nContent-Type: image/jpeg\r\nContent-Length: " + str(len(data)).encode() + b"\r\n\r\n"
                        + data + b"\r\n")
         return Response(parts(), mimetype="multipart/x-mixed-replace; boundary=frame", headers={"Cache-Control": "no-store"})
+
+    def camera_faces():
+        """the faces of the source's last processed frame: a list of {bbox, person_info, recognition_score, detection_score,
+        chip}, chip the thumbnail's JPEG in base64 or null"""
+        source = camera_manager.source_named(request.args.get("source", "0"))
+        faces = None if source is None else camera_manager.latest_faces(source)
+        if faces is None:
+            return jsonify({"status": "error", "message": "No faces from this source"}), 404
+        out = []
+        for r in faces:
+            chip = r.get("chip")
+            out.append({"bbox": [int(v) for v in r["bbox"]], "person_info": r.get("person_info"),
+                        "recognition_score": float(r.get("recognition_score") or 0), "detection_score": float(r.get("det_score") or 0),
+                        "chip": base64.b64encode(chip).decode("ascii") if isinstance(chip, (bytes, bytearray)) else None})
+        return jsonify(out)
+
+    if hasattr(camera_manager, "latest_faces"):   # a manager that keeps faces (CameraManager): one that does not has no such route
+        app.add_url_rule("/api/camera/faces", view_func=camera_faces, methods=["GET"])
 
     return app

@@ -55,6 +55,7 @@ typedef void* fr_stream_t;
  * engine pass),
  * and for fr_jpeg_decode_oriented_refs_u8 (the same decoder writing each frame as its EXIF orientation turns it),
  * and for fr_redact_u8 / fr_redact_refs_u8 (face redaction: regions pixelated or filled in place in front of the HUD draw),
+ * and for fr_face_chips_u8 / fr_face_chips_refs_u8 (face chips: a square around each face cut and resampled to a thumbnail),
  * ADDED under 106 likewise.  fr_version() returns the value the library was built
  * with: a caller compiled against another header must refuse to go on (the Python binding does, _lib.load()). */
 #define FR_ABI_VERSION 106
@@ -912,6 +913,42 @@ int fr_redact_u8(uint8_t* frames, int N, int H, int W, const int32_t* counts, in
                  int block, int mode, uint32_t bgr, fr_stream_t stream);
 int fr_redact_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* counts, int cap, const int32_t* regions,
                       int block, int mode, uint32_t bgr, fr_stream_t stream);
+
+/* Face chips: a square around each face, cut out of the full-size BGR u8 frames on the device and resampled to size x size
+ * bytes - the thumbnail of an unknown-person event, a recognition log or a watch-list dashboard - in front of the redactor and
+ * the HUD draw, so that a chip shows the unmasked, undrawn pixels.  The picture is defined by tests/helpers/chip_ref.py and
+ * reproduced byte for byte (integers only).
+ *
+ * chips i32 [F][4], one record per chip: frame, x0, y0, side - the square [x0, x0 + side) x [y0, y0 + side) of that frame, in
+ * frame pixels, partly or wholly outside the frame if it likes; a pixel outside the frame reads as the colour bgr_fill (B in
+ * bits 0 .. 7, G in 8 .. 15, R in 16 .. 23).  With L = side and S = size, on one axis output j weighs source position p
+ * (relative to the square's origin):
+ *   box      L >= S, the exact area average: a source pixel is S units long, an output pixel L;
+ *            w = min((j + 1) L, (p + 1) S) - max(j L, p S) where that is positive; the weights of an output sum to T = L
+ *   bilinear L < S, half-pixel centres: n = (2 j + 1) L - S, p = floor(n / 2 S) (toward minus infinity: -1 at the leading
+ *            edge), t = n - 2 S p; taps p (weight 2 S - t) and p + 1 (weight t), NOT clamped to the square: -1 and L read the
+ *            frame's own neighbouring pixels, or the fill colour outside the frame; T = 2 S
+ *   byte     (sum_y sum_x w_y w_x pix + T^2 / 2) / T^2 per channel, T^2 / 2 an integer division: round half up, the identity
+ *            at L == S.  The largest sum, 255 * 4096^2 + 4096^2 / 2, fits an UNSIGNED 32-bit accumulator and no signed one.
+ * Limits: 1 <= side <= FR_CHIP_MAX_SIDE, 16 <= size <= 256, |x0|, |y0| <= 2^20.  Records are device data and are checked on the
+ * device: a record whose frame index is outside the batch, whose side is out of range, with a coordinate beyond the limit, or
+ * whose frame-table entry is null, non-positive or of 2 GiB or more gives a chip of pure fill colour - never a fault, never a
+ * gap in out.
+ *
+ * One launch on the caller's stream (grid: chip x band of output rows), nothing allocated, nothing synchronised, no global state.
+ * Nothing outside [data, data + H*W*3) of a frame is read - any byte alignment of the frames and their rows - and nothing outside
+ * out[0 : F * size * size * 3) is written.
+ *
+ * fr_face_chips_u8: a uniform batch u8 [N,H,W,3].  fr_face_chips_refs_u8: a DEVICE frame table (data, H and W are read; the
+ * table a RaggedIngest hands out serves as it is).  Refused before any launch: N / nframes outside 0 .. 65535, non-positive H or
+ * W, a frame of 2 GiB or more, F outside 0 .. 2^20, size outside 16 .. 256, a null pointer with F > 0 (frames / refs may be null
+ * with no frames: every chip is fill then).  F == 0 returns FR_OK and reads nothing.  Added under ABI 106: no existing signature
+ * changed. */
+#define FR_CHIP_MAX_SIDE 4096
+int fr_face_chips_u8(const uint8_t* frames, int N, int H, int W, const int32_t* chips, int F, int size, uint32_t bgr_fill,
+                     uint8_t* out, fr_stream_t stream);
+int fr_face_chips_refs_u8(const fr_frame_ref* refs, int nframes, const int32_t* chips, int F, int size, uint32_t bgr_fill,
+                          uint8_t* out, fr_stream_t stream);
 
 /* Device JPEG encoder: BGR u8 frames on the device (the drawn frames of the HUD) -> baseline JPEG files, so that a few hundred
  * KB per 1080p frame cross the link instead of 6.2 MB (the reference shows raw frames with cv2.imshow, one process per camera:
